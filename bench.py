@@ -19,6 +19,15 @@ one all-gather per migration.  Started by a launcher (RANK / WORLD_SIZE in the e
 the process is one rank; started bare with N > 1 it spawns its N ranks itself -- as fresh child processes, before this
 process has touched the GPU.
 
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only what the headline figure needs: it sets up, warms up, times
+the K steps and prints the result line.  Everything else this program measures -- the roofline of the dominant kernel (HIP
+events; an instrumented repeat for the other workloads), the untimed accuracy leg, the CPU baseline, the other SURVEY 8(d)
+rows and, at N > 1, the sharded rows of the 8-GPU configs -- runs with --full.
+
+--dump-outputs DIR: after the timed steps, what the timed path computed in its last step (the particle state a caller of
+demc_step receives) is written as DIR/<name>.npy in float64, at most 64 MB in all (a fixed, seeded sample of the particles
+when the state is larger).  The inputs depend on the arguments alone, so two builds can be compared output for output.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -60,7 +69,7 @@ def parse(argv=None):
                                                                  "and hierarchical examples use 0.1): runs the snooker instances of the kernels")
     ap.add_argument("--beta", type=float, default=None, help="override beta, the probability of a mutation sweep (main.jl:199-207; default 0.1)")
     ap.add_argument("--fuse", type=int, default=0, help="demc_config.fuse (0 auto, 1 never, 2 per phase)")
-    ap.add_argument("--accuracy-iters", type=int, default=1500, help="length of the untimed accuracy leg (0: skip)")
+    ap.add_argument("--accuracy-iters", type=int, default=1500, help="length of the untimed accuracy leg of --full (0: skip)")
     ap.add_argument("--async-migration", action="store_true",
                     help="groups an exchange does not select update while the all-gather is in flight (SURVEY 8f #3)")
     ap.add_argument("--collective", default="library", choices=["library", "torch"],
@@ -76,13 +85,21 @@ def parse(argv=None):
                     help="posterior: start the particles tightly around the generating parameters (the converged regime a long run "
                          "spends its time in) instead of from prior draws")
     ap.add_argument("--rows", default=None,
-                    help="the other SURVEY 8(d) rows, measured after the headline's timed region and appended as `rows` to the JSON line: "
-                         "`all` (default for the plain `bench.py [--gpus 1]` headline command), `none`, or a comma list of row names")
+                    help="the other SURVEY 8(d) rows of --full, measured after the headline's timed region and appended as `rows` to the JSON "
+                         "line: `all` (default for the headline command `bench.py --full [--gpus 1]`), `none`, or a comma list of row names")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: roofline, accuracy leg, CPU baseline, `rows` (without it: "
+                         "set up, warm up, time --steps steps, print the result line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the state the last step computed as DIR/<name>.npy (float64, at most 64 MB)")
     ap.add_argument("--deadline", type=float, default=540.0,
                     help="seconds after which a multi-rank run is ended with evidence (parent: all ranks; a rank: itself)")
     ap.add_argument("--init-timeout", type=float, default=150.0,
                     help="seconds a rank may spend between the start of the id exchange and the end of communicator creation")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
 
 
 EXIT_INIT = 17    # a rank gave up while the communicator was being created (id exchange, ncclCommInitRank)
@@ -1327,8 +1344,39 @@ def emit(out):
     print(compact_line(out), flush=True)
 
 
+DUMP_LIMIT = 64 << 20   # bytes of --dump-outputs, all ranks together
+DUMP_SEED = 20260007    # the particles kept when the state is larger than that
+
+
+def write_outputs(out_dir, theta, per_particle, rank=0, world=1, limit=DUMP_LIMIT):
+    """--dump-outputs: theta [P, D] and the per-particle vectors (name -> [P]) as float64 .npy files under out_dir.  A rank's share
+    of `limit` is limit / world; if the rows do not fit, the same fixed, seeded sample of particles (sorted slot numbers, written
+    as `sample_rows`) is taken from every array.  Several ranks name their files <name>_rank<r>.npy.  Returns the names written."""
+    import numpy as np
+    theta = np.asarray(theta, dtype=np.float64)
+    P, D = theta.shape
+    cols = {k: np.asarray(v, dtype=np.float64).reshape(P) for k, v in per_particle.items()}
+    arrays = dict(theta=theta, **cols)
+    row_bytes = 8 * (D + len(cols))
+    budget = limit // world
+    if P * row_bytes > budget:
+        keep = max(1, budget // (row_bytes + 8))  # (+ 8: the sample's own index vector)
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(P, size=min(P, keep), replace=False))
+        arrays = {k: v[rows] for k, v in arrays.items()}
+        arrays["sample_rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    names = []
+    for k, v in arrays.items():
+        name = k if world == 1 else f"{k}_rank{rank}"
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(v, dtype=np.float64))
+        names.append(name)
+    return names
+
+
 def main():
     a = parse()
+    if not a.full:  # a plain run: set up, warm up, time the K steps, print the line -- the rest is --full's
+        a.no_roofline, a.no_cpu_baseline, a.accuracy_iters, a.rows = True, True, 0, "none"
     if a.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         spawn_ranks(a)  # does not return
     rank = int(os.environ.get("RANK", "0"))
@@ -1422,13 +1470,20 @@ def main():
     if not a.no_roofline and not split:
         eng.timing_enable(True)  # HIP events on the handle's stream around every launch of the timed iterations
     stage("timed", max(120.0, a.deadline / 3))
-    sclk = SclkSampler(local)
-    sclk.start()
+    sclk = None
+    if not a.no_roofline:
+        sclk = SclkSampler(local)
+        sclk.start()
     t0 = time.perf_counter()
     step(it0 + a.warmup, a.steps)
     sync()
     dt_own = time.perf_counter() - t0
-    a.sclk_sysfs = sclk.result()
+    a.sclk_sysfs = None if sclk is None else sclk.result()
+    if a.dump_outputs:  # the state the last timed step left (before a multi-rank --full repeats the steps on this engine)
+        last = a.n_initial + a.warmup + a.steps - 1
+        th_out, w_out, ids_out = eng.get_state()
+        _, acc_out, _, _ = eng.get_history(last, last + 1)
+        write_outputs(a.dump_outputs, th_out, dict(log_weight=w_out, ids=ids_out, accepted=acc_out[0]), rank, world)
     a.clock = None
     tm = None
     if split and not multi:  # (two_pass: the same K steps of the same chain on a fresh engine, with the events on)
@@ -1471,7 +1526,8 @@ def main():
     value = P * world * sweeps * a.steps / dt
 
     out = None
-    if rank == 0:
+    timed_chain = None
+    if rank == 0 and a.full:
         k_last = min(10, a.steps)
         th_h, acc_h, _, _ = eng.get_history(n_rows - k_last, n_rows)
         th_now, w_now, ids = eng.get_state()
@@ -1499,10 +1555,12 @@ def main():
         wd.stop()  # what follows is rank 0's own CPU work (accuracy leg); the other ranks wait in the last barrier at most
 
     if rank == 0:
-        acc = accuracy_leg(a, w, demc_amd, local, np.random.default_rng(20260003))
-        accuracy = dict(timed_chain=timed_chain)
-        if acc is not None:
-            accuracy.update(acc)
+        accuracy = None
+        if a.full:
+            acc = accuracy_leg(a, w, demc_amd, local, np.random.default_rng(20260003))
+            accuracy = dict(timed_chain=timed_chain)
+            if acc is not None:
+                accuracy.update(acc)
         rows = sharded
         plain_headline = is_plain_headline(a)
         if world == 1 and not multi and a.rows != "none" and (a.rows is not None or plain_headline) and not a.no_roofline:

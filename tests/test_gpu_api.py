@@ -458,7 +458,7 @@ def test_bench_contract_on_a_small_workload(mode):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--mode", mode,
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "1", "--steps", "6", "--warmup", "2", "--mode", mode,
                           "--n-groups", "16", "--np", "32", "--nobs", "4000", "--dim", "8", "--accuracy-iters", "300", "--burnin", "100"],
                          capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -491,6 +491,33 @@ def test_bench_contract_on_a_small_workload(mode):
     assert r["accuracy"]["posterior_mean_l1_rel"] is not None and r["accuracy"]["accept_rate"] is not None
 
 
+def test_bench_plain_run_and_its_dumped_outputs(tmp_path):
+    """without --full the run times its K steps and prints the contract's line, nothing else measured (no roofline, CPU baseline,
+    accuracy leg or rows); --dump-outputs writes the state of the last timed step, the same bits from run to run"""
+    import json
+    import os
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for rep in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2", "--n-groups", "16",
+                              "--np", "32", "--nobs", "4000", "--dim", "8", "--dump-outputs", str(tmp_path / rep)],
+                             capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        r, det = json.loads(lines[-1]), json.loads(lines[0])["detail"]
+        assert r["steps"] == 7 and r["warmup"] == 2 and r["dtype"] == "f64" and r["higher_is_better"] is True and r["value"] > 0
+        assert abs(det["value"] - 16 * 32 * 7 / (det["ms_per_step"] * 7e-3)) <= 1e-6 * det["value"]
+        assert r["roofline"] is None and r["cpu_baseline"] is None and r["rows"] is None and det["accuracy"] is None
+        dumps.append({n: np.load(str(tmp_path / rep / (n + ".npy"))) for n in ("theta", "log_weight", "ids", "accepted")})
+    d = dumps[0]
+    assert d["theta"].shape == (16 * 32, 8) and all(v.dtype == np.float64 for v in d.values())
+    assert np.isfinite(d["log_weight"]).all() and len(np.unique(d["ids"])) == 16 * 32 and set(np.unique(d["accepted"])) <= {0.0, 1.0}
+    assert all(np.array_equal(d[n], dumps[1][n]) for n in d)
+
+
 @pytest.mark.parametrize("config,extra", [("cfg1", []), ("cfg3", ["--mode", "direct", "--n-groups", "16", "--np", "32", "--nobs", "4000", "--dim", "8"]),
                                           ("cfg2", ["--mode", "streaming", "--nobs", "2000"]), ("cfg4", ["--nobs", "600", "--n-groups", "4", "--np", "8"]),
                                           ("cfg5", ["--nobs", "500", "--n-groups", "4", "--np", "16"])])
@@ -501,7 +528,7 @@ def test_bench_lines_of_the_other_configs(config, extra):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--config", config,
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "1", "--steps", "6", "--warmup", "2", "--config", config,
                           "--accuracy-iters", "0"] + extra, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -518,7 +545,7 @@ def test_bench_lines_of_the_other_configs(config, extra):
 
 
 def test_bench_rows_and_the_row_flags(tmp_path):
-    """the driver's command (`python bench.py`, here with fewer steps) appends `rows`: every named row is there with a roofline
+    """the full command (`python bench.py --full`, here with fewer steps) appends `rows`: every named row is there with a roofline
     fraction in (0, 1] and the kernels it ran; and the flags behind two of the newer rows run by hand -- DE-MC_Z past burn-in
     (ONE lean kernel) and the LBA from a converged population"""
     import json
@@ -528,7 +555,7 @@ def test_bench_rows_and_the_row_flags(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     sys.path.insert(0, root)
     import bench
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "10", "--warmup", "3",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "10", "--warmup", "3",
                           "--accuracy-iters", "0", "--rows", "cfg3_streaming,cfg3_suffstat,cfg3_suffstat_history_partners_post_burnin,"
                                                             "cfg3_suffstat_history_partners_snooker,cfg4_share,cfg5_share_converged"],
                          capture_output=True, text=True, timeout=900)

@@ -377,7 +377,7 @@ def test_bench_sharded_rows_of_the_8_gpu_configs_at_world_one(collective):
     env = dict(os.environ, DEMC_FORCE_DIST="1")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "10", "--warmup", "3",
-                          "--accuracy-iters", "0", "--no-cpu-baseline", "--collective", collective], capture_output=True, text=True, timeout=900,
+                          "--accuracy-iters", "0", "--no-cpu-baseline", "--collective", collective, "--full"], capture_output=True, text=True, timeout=900,
                          env=env)  # (torch: the road the run takes when the library's communicator cannot be created -- same rows)
     assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-1500:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

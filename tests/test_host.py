@@ -488,6 +488,49 @@ def test_bench_rank_files_merge_into_one_short_line():
     assert abs(line["rows"][0]["value"] / (8 * 512 * 2 * 40 / 0.0059) - 1) < 1e-4 and line["rows"][0]["all_gathers_per_rank"] == [4] * 8
 
 
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """a plain run is lean -- everything but the headline's own figure is --full's -- and its line keeps the contract's fields
+    with roofline / cpu_baseline / rows empty; --dump-outputs writes float64 .npy files within 64 MB, a fixed, seeded sample of
+    the particles when the state does not fit, each rank its own share"""
+    import json
+    import numpy as np
+    bench = _bench_module()
+    a = bench.parse([])
+    assert not a.full and a.dump_outputs is None and a.steps == 200
+    a = bench.parse(["--full", "--dump-outputs", str(tmp_path), "--steps", "7"])
+    assert a.full and a.dump_outputs == str(tmp_path) and a.steps == 7
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+    out = _fake_bench_result(bench)
+    out.update(roofline=None, cpu_baseline=None, rows=None, headline_context=None, accuracy=None)
+    line = json.loads(bench.compact_line(out))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"):
+        assert line[k] == bench.sig(out[k]), k
+    assert line["roofline"] is None and line["cpu_baseline"] is None and line["rows"] is None
+    rng = np.random.default_rng(3)
+    P, D = 64, 5
+    th, lw, ids, acc = rng.normal(size=(P, D)), rng.normal(size=P), rng.permutation(P), rng.integers(0, 2, P).astype(np.uint8)
+    names = bench.write_outputs(str(tmp_path / "all"), th, dict(log_weight=lw, ids=ids, accepted=acc))
+    assert names == ["theta", "log_weight", "ids", "accepted"]
+    got = {n: np.load(str(tmp_path / "all" / (n + ".npy"))) for n in names}
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert np.array_equal(got["theta"], th) and np.array_equal(got["ids"], ids) and np.array_equal(got["accepted"], acc)
+    # over the limit: the same seeded rows from every array, twice the same; with two ranks each writes its own files in half the room
+    limit = 20 * 8 * (D + 3 + 1)
+    for rep in ("s1", "s2"):
+        names = bench.write_outputs(str(tmp_path / rep), th, dict(log_weight=lw, ids=ids, accepted=acc), limit=limit)
+        assert "sample_rows" in names
+    s1 = {n: np.load(str(tmp_path / "s1" / (n + ".npy"))) for n in names}
+    s2 = {n: np.load(str(tmp_path / "s2" / (n + ".npy"))) for n in names}
+    rows = s1["sample_rows"].astype(int)
+    assert len(rows) == 20 and np.all(np.diff(rows) > 0) and all(np.array_equal(s1[n], s2[n]) for n in names)
+    assert np.array_equal(s1["theta"], th[rows]) and np.array_equal(s1["ids"], ids[rows])
+    assert sum(os.path.getsize(str(tmp_path / "s1" / (n + ".npy"))) - 128 for n in names) <= limit
+    names = bench.write_outputs(str(tmp_path / "r1"), th, dict(log_weight=lw), rank=1, world=2, limit=limit)
+    assert names == ["theta_rank1", "log_weight_rank1", "sample_rows_rank1"]
+    assert len(np.load(str(tmp_path / "r1" / "theta_rank1.npy"))) == limit // 2 // (8 * (D + 1) + 8)
+
+
 def test_bench_reads_the_traffic_shape_roof_of_the_long_row_kernel():
     """cfg4's rows are also quoted against what a bare kernel of the long-row kernel's traffic shape reaches
     (tools/longrow_traffic_probe.hip; the committed output of its run on the box): the average of a subject-sweep and a

@@ -14,7 +14,7 @@ var, values = sys.argv[1], sys.argv[2].split(",")
 args = sys.argv[sys.argv.index("--") + 1:]
 def code_for(lib):
     return ("import sys, runpy; sys.path.insert(0, %r); import demc_amd; "
-            "demc_amd._ffi.LIB_PATH = %r; sys.argv = ['bench.py'] + %r; runpy.run_path(%r, run_name='__main__')"
+            "demc_amd._ffi.LIB_PATH = %r; sys.argv = ['bench.py', '--full'] + %r; runpy.run_path(%r, run_name='__main__')"
             % (ROOT, os.path.join(ROOT, "differentialevolutionmcmc.jl_amd", lib), args, os.path.join(ROOT, "bench.py")))
 
 

@@ -4,8 +4,8 @@
     python3 tools/collect_profiles.py gpurun_out/profiles_rNN [row ...]     # summaries are also installed under profiles/rNN/
 
 A row is `headline` (the default command) or a name of bench.ROWS (default: all of them); the profiled command is
-`python3 bench.py <the row's flags> --rows none --no-cpu-baseline --accuracy-iters 0 --no-roofline` (the iterations once, without
-HIP events: the un-profiled line at the end drops `--no-roofline`), i.e. what the driver's
+`python3 bench.py <the row's flags> --full --rows none --no-cpu-baseline --accuracy-iters 0 --no-roofline` (the iterations once,
+without HIP events: the un-profiled line at the end drops `--no-roofline`), i.e. what the driver's
 `python3 bench.py --gpus 1` measures for that row.  For each row:
   * `rocprofv3 --kernel-trace --stats`                              -> bench_<row>_kernel_stats.csv
   * `--kernel-trace --pmc FETCH_SIZE` and `--pmc WRITE_SIZE`  (separate passes, as MI355X_MICROARCH.md prescribes; FETCH_SIZE
@@ -126,7 +126,7 @@ def main():
         n_iters = over.get("steps", 20) + over.get("warmup", 5)
         pattern = dominant_pattern(over)
         print(f"{tag}: {over}", flush=True)
-        args = bench.row_flags(over) + ["--rows", "none", "--no-cpu-baseline", "--accuracy-iters", "0"]
+        args = bench.row_flags(over) + ["--full", "--rows", "none", "--no-cpu-baseline", "--accuracy-iters", "0"]
         # the profiled passes run the iterations ONCE (--no-roofline: no HIP events, no instrumented repeat -- bench.two_pass);
         # the un-profiled line at the end is the plain command
         prof = args + ["--no-roofline"]
