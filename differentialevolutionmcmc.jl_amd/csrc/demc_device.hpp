@@ -249,15 +249,12 @@ constexpr double kPhiS = (double)kPhiPerUnit;
 constexpr double kPhiHalf = kPhiZmax * kPhiPerUnit;              // 8.5 S: an integer
 constexpr double kPhiMagic = 6755399441055744.0 + kPhiHalf;      // 1.5 * 2^52 + 8.5 S (exactly representable)
 static_assert(kPhiZmax == 8.5 && (kPhiPerUnit & 1) == 0 && kPhiRow >= kPhiDeg + 1 && (kPhiRow & 1) == 0, "table shape");
-// RS = doubles from one row of the LDS copy to the next: kPhiRow (rows packed, any lane may read any copy) or 16 (rows of
-// 128 bytes in the eight-copy layout of k_lba_loglike, where `tab` is the LANE'S OWN copy -- see that kernel).
-template <int RS = kPhiRow>
 __device__ __forceinline__ void phiS_Phi_table(const double* tab, double zs, double& phS, double& Ph) {
     const double zc = fmin(fmax(zs, -kPhiHalf), kPhiHalf);
     const double t = zc + kPhiMagic;              // = round(zc + 8.5 S) + 1.5 * 2^52
     const double u = zc - (t - kPhiMagic);        // t - magic = row - 8.5 S, exactly
     const int row = __double2loint(t);            // low word of the sum = the row
-    const double* a = RS == 16 ? tab + (row << 4) : tab + __mul24(row, RS);
+    const double* a = tab + __mul24(row, kPhiRow);
     double P = a[kPhiDeg], dP = a[kPhiDeg];
     P = fma(P, u, a[kPhiDeg - 1]);
 #pragma unroll
@@ -301,13 +298,12 @@ __device__ __forceinline__ double log_Phi_neg_table(const double* tab, double z)
 // proposals at the same trial): `win` is a scalar branch.  Everything arrives scaled by S (the table's argument scale):
 // vS = S v, c1 = S k/t, c2 = S b/t, so m1 = S n1, m2 = S n2; the table returns q = phi/S.  With dq = q1 - q2:
 //   f = (1/A) [ v (P2 - P1) + S dq ],      1 - F = (t / S A) [ (m2 P2 - m1 P1) - S^2 dq ].
-template <int RS = kPhiRow>
 __device__ __forceinline__ double lba_factor(const double* tab, bool win, double v, double vS, double c1, double c2, double inv_A,
                                              double t_inv_SA) {
     const double m1 = c1 - vS, m2 = c2 - vS;
     double q1, P1, q2, P2;
-    phiS_Phi_table<RS>(tab, m1, q1, P1);
-    phiS_Phi_table<RS>(tab, m2, q2, P2);
+    phiS_Phi_table(tab, m1, q1, P1);
+    phiS_Phi_table(tab, m2, q2, P2);
     const double dq = q1 - q2;
     if (win) return inv_A * fma(kPhiS, dq, v * (P2 - P1));
     return t_inv_SA * fma(-(kPhiS * kPhiS), dq, fma(m2, P2, -(m1 * P1)));
@@ -324,7 +320,7 @@ __device__ __forceinline__ double recip_pos(double x) {
 // nuS = S nu, kS = S k, bS = S b, inv_SA = 1 / (S A)
 // (C = int: the winner as a wave-uniform index, k_obs_loglike; C = double: as it lies in the data, one per lane -- k_lba_wave --
 // compared without a conversion instruction)
-template <int NA, int RS = kPhiRow, typename C = int>
+template <int NA, typename C = int>
 __device__ __forceinline__ double lba_trial(const double* tab, int na_rt, const double* nu, const double* nuS, double kS, double bS,
                                             double tau, double inv_A, double inv_SA, double inv_norm, C c, double rt) {
     const int na = NA > 0 ? NA : na_rt;
@@ -333,7 +329,7 @@ __device__ __forceinline__ double lba_trial(const double* tab, int na_rt, const 
     double den = inv_norm;
 #pragma unroll
     for (int a = 0; a < (NA > 0 ? NA : 8); ++a)
-        if (a < na) den *= lba_factor<RS>(tab, (C)(a + 1) == c, nu[a], nuS[a], c1, c2, inv_A, t_inv_SA);
+        if (a < na) den *= lba_factor(tab, (C)(a + 1) == c, nu[a], nuS[a], c1, c2, inv_A, t_inv_SA);
     const double floored = fmax(den, 1e-10);  // (a NaN density is caught below)
     // The table clamps its argument with v_max / v_min, which read a NaN as -8.5: a NaN ARGUMENT would no longer reach `den`.
     // The arguments can only become NaN through 1/t of a denormal t (rcp = Inf, 0 * Inf in the Newton steps); decision times

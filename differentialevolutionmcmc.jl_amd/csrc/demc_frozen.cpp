@@ -6,6 +6,5 @@
 namespace demc {
 #define DEMC_X_(...) template __global__ void k_frozen_sweep<__VA_ARGS__>(KParams);
 DEMC_FROZEN_INSTANCES(DEMC_X_)
-DEMC_FROZEN_INSTANCES_EXP(DEMC_X_)
 #undef DEMC_X_
 }  // namespace demc

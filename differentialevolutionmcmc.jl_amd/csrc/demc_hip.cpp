@@ -83,7 +83,6 @@ struct demc_handle {
     int direct_wgs_per_cu = 0;  // ... resident workgroups of its kernel per CU (asked once)
     int obs_wgs_per_cu = 0;     // the same for k_obs_loglike
     int lba_wave_wgs_per_cu = 0;  // ... and k_lba_wave
-    bool lba_wide_ok = false;   // k_lba_loglike's 140 KB of dynamic LDS were granted (demc_create)
     double *data = nullptr, *Ainv = nullptr, *Ypad = nullptr, *Xf = nullptr, *sx = nullptr, *xbar = nullptr;
     size_t data2_off = 0;
     // user plug-in (demc_set_model_source): JIT-compiled module, kernel and its hyper-parameters
@@ -123,8 +122,6 @@ struct demc_handle {
     long long frozen_iter0 = 0;
     int frozen_iters = 0;
     int st_C = 0, st_nact_max = 0, st_rows = 0, st_x_lds = 0, st_chunk_tiles = 0, st_lpp = 0, st_scr_doubles = 0, st_wg = 512;
-    // the lean streaming kernel's own cut of the observation tiles (plan_lean): st_C, or twice that with two workgroups per CU
-    int lean_st_C = 0, lean_st_chunk_tiles = 0, lean_st_x_lds = 0, lean_st_occ = 1;
     size_t st_lds = 0;
     unsigned long long* st_gran = nullptr;  // hand-over granules (device)
     unsigned* st_err = nullptr;             // time-out flag (host-mapped, zero-copy)
@@ -217,17 +214,6 @@ int32_t guarded(demc_handle* h, F&& body) noexcept {
     } catch (...) {
         return fail(h, DEMC_EHIP, "internal error (unknown exception)");
     }
-}
-
-// A/B switches for kernel experiments (tools/, profiles/README.md).  They exist only in a build made with
-// -DDEMC_EXPERIMENTS (make EXPERIMENTS=1); the product library never reads the environment.
-inline const char* experiment(const char* name) {
-#ifdef DEMC_EXPERIMENTS
-    return std::getenv(name);
-#else
-    (void)name;
-    return nullptr;
-#endif
 }
 
 #define HIPCHK(expr)                                                                                         \
@@ -553,58 +539,28 @@ int launch_loglike(demc_handle* h, KParams& k) {
                 h->obs_wgs_per_cu = nb > 0 ? nb : 1;
             }
             int n_chunks = chunks_filling_rounds((n_prop + 255) / 256, cap, (double)h->obs_wgs_per_cu * h->n_cus);
-            if (const char* e = experiment("DEMC_OBS_CHUNKS")) {  // A/B experiments
-                std::fprintf(stderr, "k_obs_loglike: %d workgroups per CU, %d chunks chosen\n", h->obs_wgs_per_cu, n_chunks);
-                if (std::atoi(e) > 0 && std::atoi(e) <= cap) n_chunks = std::atoi(e);
-            }
-            // (A/B build only: k_lba_loglike, eight shifted copies of the Phi table with 128-byte rows -- measured 4 % SLOWER
-            // than the packed single copy: 1.584 vs 1.522 ms per launch on cfg5, profiles/r04/ab_experiments.txt)
-            bool lba_wide = false;
-            if (const char* e = experiment("DEMC_LBA_WIDE")) lba_wide = h->family == FAM_LBA && h->lba_wide_ok && e[0] == '1';
-#ifdef DEMC_EXPERIMENTS
-            if (lba_wide) {
-                // the conflict-free eight-copy table (k_lba_loglike): 140 KB of LDS, one workgroup of 512 per CU
-                n_chunks = chunks_filling_rounds((n_prop + 511) / 512, cap, (double)h->n_cus);
-                if (const char* e = experiment("DEMC_OBS_CHUNKS"))
-                    if (std::atoi(e) > 0 && std::atoi(e) <= cap) n_chunks = std::atoi(e);
-                h->last.k2 = 7;
-                tick(h, 2, true);
-                LAUNCH_T(h, k_lba_loglike<512>, dim3((unsigned)((n_prop + 511) / 512), (unsigned)n_chunks), dim3(512), kLbaTableBytes, k,
-                         n_chunks);
-                tick(h, 2, false);
-                k.n_partials = n_chunks;
-                break;
-            }
-#endif
-            (void)lba_wide;
             if (h->family == FAM_LBA) {
                 // a wave per proposal, lanes across the (sorted) trials: k_lba_wave.  Chunks of whole batches (512 trials), at least two a chunk.
-                bool on = true;
-                if (const char* e = experiment("DEMC_LBA_WAVE")) on = e[0] == '1';  // A/B experiments
-                if (on) {
-                    if (h->lba_wave_wgs_per_cu == 0) {
-                        int nb = 0;
-                        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)k_lba_wave<3>, 256, 0));
-                        h->lba_wave_wgs_per_cu = nb > 0 ? nb : 1;
-                    }
-                    long long capw = h->N / 1024;
-                    if (capw > h->partial_cap) capw = h->partial_cap;
-                    if (capw < 1) capw = 1;
-                    int nc = chunks_filling_rounds((n_prop + 3) / 4, capw, (double)h->lba_wave_wgs_per_cu * h->n_cus);
-                    if (const char* e = experiment("DEMC_OBS_CHUNKS"))  // A/B experiments
-                        if (std::atoi(e) > 0 && std::atoi(e) <= capw) nc = std::atoi(e);
-                    h->last.k2 = 8;
-                    unsigned long long* clk = nullptr;  // timing on: the clock the vector pipe held (demc_timing_clock)
-                    if (int rc = clock_buffer(h, (size_t)((n_prop + 3) / 4) * (size_t)nc, &clk)) return rc;
-                    tick(h, 2, true);
-                    const dim3 grid((unsigned)((n_prop + 3) / 4), (unsigned)nc);
-                    if (h->n_acc == 3) LAUNCH_T(h, k_lba_wave<3>, grid, dim3(256), 0, k, nc, clk);
-                    else if (h->n_acc == 2) LAUNCH_T(h, k_lba_wave<2>, grid, dim3(256), 0, k, nc, clk);
-                    else LAUNCH_T(h, k_lba_wave<0>, grid, dim3(256), 0, k, nc, clk);
-                    tick(h, 2, false);
-                    k.n_partials = nc;
-                    break;
+                if (h->lba_wave_wgs_per_cu == 0) {
+                    int nb = 0;
+                    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)k_lba_wave<3>, 256, 0));
+                    h->lba_wave_wgs_per_cu = nb > 0 ? nb : 1;
                 }
+                long long capw = h->N / 1024;
+                if (capw > h->partial_cap) capw = h->partial_cap;
+                if (capw < 1) capw = 1;
+                int nc = chunks_filling_rounds((n_prop + 3) / 4, capw, (double)h->lba_wave_wgs_per_cu * h->n_cus);
+                h->last.k2 = 8;
+                unsigned long long* clk = nullptr;  // timing on: the clock the vector pipe held (demc_timing_clock)
+                if (int rc = clock_buffer(h, (size_t)((n_prop + 3) / 4) * (size_t)nc, &clk)) return rc;
+                tick(h, 2, true);
+                const dim3 grid((unsigned)((n_prop + 3) / 4), (unsigned)nc);
+                if (h->n_acc == 3) LAUNCH_T(h, k_lba_wave<3>, grid, dim3(256), 0, k, nc, clk);
+                else if (h->n_acc == 2) LAUNCH_T(h, k_lba_wave<2>, grid, dim3(256), 0, k, nc, clk);
+                else LAUNCH_T(h, k_lba_wave<0>, grid, dim3(256), 0, k, nc, clk);
+                tick(h, 2, false);
+                k.n_partials = nc;
+                break;
             }
             h->last.k2 = 2;
             tick(h, 2, true);
@@ -678,7 +634,6 @@ void set_tail_flags(demc_handle* h, KParams& k) {
     // statistics and a phase writes only rows that no other workgroup reads (two_colour, or the identity pass)
     k.fuse_prep = is_mvn(h->family) ? 1 : 0;
     k.prep_mfma = (h->family == FAM_MVN_FULL && k.lpp >= 4 && k.lpp <= 16 && h->d <= 32) ? 1 : 0;
-    if (const char* e = experiment("DEMC_PREP_MFMA")) k.prep_mfma = k.prep_mfma && e[0] == '1';  // A/B experiments
     k.sx = (k.fuse_prep && suff) ? h->sx : nullptr;
     k.Ainv = (h->family == FAM_MVN_FULL) ? h->Ainv : nullptr;
     // small-N scalar-data families: the sub-group of a particle sums the per-observation terms itself
@@ -731,8 +686,7 @@ int launch_phase(demc_handle* h, KParams k) {
     const int wg = k.lpp > 256 ? 512 : 256;  // K1 workgroup: 512 threads when one particle takes 512 lanes
     const int ppp = wg / k.lpp, ppp3 = 256 / k.lpp3;
     const int max_split = (k.n_act + ppp - 1) / ppp;
-    int target_wgs = 512;
-    if (const char* e = experiment("DEMC_K1_WGS")) target_wgs = std::atoi(e);  // A/B experiments
+    const int target_wgs = 512;
     int n_split = (target_wgs + k.n_groups - 1) / k.n_groups;
     if (n_split > max_split) n_split = max_split;
     if (n_split < 1) n_split = 1;
@@ -746,7 +700,6 @@ int launch_phase(demc_handle* h, KParams k) {
     k.tile_rows = k.pool_n + (k.own_in_pool ? 0 : (int)per_split);
     const size_t lds_tile = h->k1_lds - h->k1_tile_bytes + (size_t)k.tile_rows * c.D * sizeof(double);  // <= k1_lds
     k.plan = (tile && k.mode == MODE_STEP && k.lpp >= 4 && k.lpp <= 64 && lds_tile + plan_bytes <= kMaxDynLds && !h->rp_active) ? 1 : 0;
-    if (const char* e = experiment("DEMC_K1_PLAN")) k.plan = k.plan && e[0] == '1';  // A/B experiments
     // long rows of a hierarchical family, whole update fused: the dedicated one-pass kernel (demc_longrow.hpp)
     const size_t cdf_doubles = k.pool_n > 256 ? (size_t)k.pool_n + ((size_t)k.pool_n + 15) / 16 : 0;
     const size_t lr_lds = ((((size_t)c.D + 1) & ~(size_t)1) + cdf_doubles) * sizeof(double);
@@ -764,19 +717,16 @@ int launch_phase(demc_handle* h, KParams k) {
     if (!k.fuse_accept && k.mode == MODE_STEP && c.schedule == DEMC_SCHED_SYNCHRONOUS && c.partner_kind == DEMC_PARTNER_HISTORY &&
         c.proposal_kind == 0 && k.iter <= c.burnin && (h->tf_cheap_obs || suff_mvn) && c.fuse == 0 && !k.trace && !h->rp_active &&
         k.theta == h->theta) {
-        bool on = true;
-        if (const char* e = experiment("DEMC_LR_SNAPSHOT")) on = e[0] == '1';  // A/B experiments
-        if (on) {  // (the copies follow the choice of the kernel: a frozen sweep reads its base row at the block's scalars only)
-            snapshot = true;
-            k.base_theta = h->prop; k.base_weight = h->prop_prior;
-            k.fuse_obs = h->tf_cheap_obs ? 1 : 0; k.fuse_accept = 1; k.write_prop = 0;
-            // ... and when the sweep before this one was a frozen sweep over the whole population, it left this snapshot behind
-            if (h->snap2 && h->snap2_iter == (int64_t)k.iter && h->snap2_sweep == (int)k.sweep && !h->cur_glist) {
-                h->snap2_iter = -1;  // (used once: by the sweep it was written for, in the demc_step call that wrote it)
-                snapshot = false;
-                have_snap2 = true;
-                k.base_theta = h->snap2; k.base_weight = h->snap2_w;
-            }
+        // (the copies follow the choice of the kernel: a frozen sweep reads its base row at the block's scalars only)
+        snapshot = true;
+        k.base_theta = h->prop; k.base_weight = h->prop_prior;
+        k.fuse_obs = h->tf_cheap_obs ? 1 : 0; k.fuse_accept = 1; k.write_prop = 0;
+        // ... and when the sweep before this one was a frozen sweep over the whole population, it left this snapshot behind
+        if (h->snap2 && h->snap2_iter == (int64_t)k.iter && h->snap2_sweep == (int)k.sweep && !h->cur_glist) {
+            h->snap2_iter = -1;  // (used once: by the sweep it was written for, in the demc_step call that wrote it)
+            snapshot = false;
+            have_snap2 = true;
+            k.base_theta = h->snap2; k.base_weight = h->snap2_w;
         }
     }
     auto take_snapshot = [&](bool block_only) -> int {
@@ -813,25 +763,14 @@ int launch_phase(demc_handle* h, KParams k) {
         // (a long run inside the block -- the subject block -- takes the BIG instance: proposals formed on the fly, four scalars
         // per thread and round behind 16-byte loads, which the hierarchical Binomial family's even rows allow)
         bool big = longest > 256;
-        long long min_particles = 2LL * h->n_cus;
-        if (const char* e = experiment("DEMC_FROZEN_MIN")) min_particles = std::atoll(e);  // A/B experiments
-        bool on = inside >= 1 && (long long)h->geo_groups * k.n_act >= min_particles;
-        if (big) {
+        bool on = inside >= 1 && (long long)h->geo_groups * k.n_act >= 2LL * h->n_cus;
+        if (big)
             on = on && h->family == FAM_HIER_BINOMIAL && (c.D & 1) == 0;
-            if (const char* e = experiment("DEMC_FROZEN_BIG")) on = on && e[0] == '1';  // A/B experiments
-        } else
+        else
             on = on && inside <= kFrozenMax;
-        if (const char* e = experiment("DEMC_FROZEN")) on = on && e[0] == '1';  // A/B experiments
-        if (const char* e = experiment("DEMC_FROZEN_EXT"))  // A/B experiments: only what round 5's first form of the kernel served
-            if (e[0] == '0') on = on && !k.base_theta && c.theta_snooker == 0.0 && c.partner_kind == DEMC_PARTNER_CURRENT;
         if (on) {
-            if (snapshot) {
-                bool cols = true;
-                if (const char* e = experiment("DEMC_FROZEN_SNAP_COLS")) cols = e[0] == '1';  // A/B experiments
-                if (int rc = take_snapshot(cols)) return rc;
-            }
-            int wg_f = 256;
-            if (const char* e = experiment("DEMC_FROZEN_WG")) wg_f = std::atoi(e);  // A/B experiments
+            if (snapshot)
+                if (int rc = take_snapshot(true)) return rc;
             if (!k.glist && h->frozen_order_d && k.iter >= h->frozen_iter0 && k.iter < h->frozen_iter0 + h->frozen_iters &&
                 (int)k.sweep < c.n_blocks)
                 k.glist = h->frozen_order_d + ((size_t)(k.iter - h->frozen_iter0) * c.n_blocks + k.sweep) * (size_t)c.n_groups;
@@ -839,52 +778,16 @@ int launch_phase(demc_handle* h, KParams k) {
             // row passes through the kernel once) -- when it moves the whole population and does not itself read the buffer
             const int n_sweeps = c.n_blocks > 0 ? c.n_blocks : 1;
             if (!big && snapshot && !have_snap2 && (int)k.sweep + 1 < n_sweeps && !h->cur_glist && k.a_lo == 0 && k.n_act == c.Np &&
-                k.n_groups == c.n_groups) {
-                bool on2 = true;
-                if (const char* e = experiment("DEMC_FROZEN_SNAP2")) on2 = e[0] == '1';  // A/B experiments
-                if (on2 && h->snap2) {  // (allocated at plan time -- plan_snap2 -- never inside an enqueued step)
-                    k.snap_theta = h->snap2; k.snap_weight = h->snap2_w;
-                    h->snap2_iter = (int64_t)k.iter; h->snap2_sweep = (int)k.sweep + 1;
-                }
+                k.n_groups == c.n_groups && h->snap2) {  // (allocated at plan time -- plan_snap2 -- never inside an enqueued step)
+                k.snap_theta = h->snap2; k.snap_weight = h->snap2_w;
+                h->snap2_iter = (int64_t)k.iter; h->snap2_sweep = (int)k.sweep + 1;
             }
             h->last = demc_handle::LastPlan();
-            h->last.k1 = 5; h->last.wg = wg_f; h->last.big = big;
+            h->last.k1 = 5; h->last.wg = 256; h->last.big = big;
             tick(h, 0, true);
-            if (big) {
-#ifdef DEMC_EXPERIMENTS
-                if (wg_f == 512)
-                    LAUNCH_T(h, (k_frozen_sweep<512, 2, 2, true>), dim3((unsigned)n_prop), dim3(512), 0, k);
-                else if (wg_f == 1024)
-                    LAUNCH_T(h, (k_frozen_sweep<1024, 4, 2, true>), dim3((unsigned)n_prop), dim3(1024), 0, k);
-                else if (wg_f == 2562)
-                    LAUNCH_T(h, (k_frozen_sweep<256, 2, 2, true>), dim3((unsigned)n_prop), dim3(256), 0, k);
-                else
-#endif
-                    LAUNCH_T(h, (k_frozen_sweep<256, 3, 2, true>), dim3((unsigned)n_prop), dim3(256), 0, k);
-                tick(h, 0, false);
-                return DEMC_OK;
-            }
-#ifdef DEMC_EXPERIMENTS  // (A/B builds: other workgroup sizes, register budgets and pairs per round -- profiles/r05/NOTES.md section 8)
-            if (wg_f == 64)
-                LAUNCH_T(h, k_frozen_sweep<64>, dim3((unsigned)n_prop), dim3(64), 0, k);
-            else if (wg_f == 128)
-                LAUNCH_T(h, k_frozen_sweep<128>, dim3((unsigned)n_prop), dim3(128), 0, k);
-            else if (wg_f == 512)
-                LAUNCH_T(h, k_frozen_sweep<512>, dim3((unsigned)n_prop), dim3(512), 0, k);
-            else if (wg_f == 768)
-                LAUNCH_T(h, k_frozen_sweep<768>, dim3((unsigned)n_prop), dim3(768), 0, k);
-            else if (wg_f == 1024)
-                LAUNCH_T(h, (k_frozen_sweep<1024, 4>), dim3((unsigned)n_prop), dim3(1024), 0, k);
-            else if (wg_f == 2564)  // 256 threads, four waves per SIMD, two pairs per round
-                LAUNCH_T(h, (k_frozen_sweep<256, 4, 2>), dim3((unsigned)n_prop), dim3(256), 0, k);
-            else if (wg_f == 2541)  // ... one pair per round
-                LAUNCH_T(h, (k_frozen_sweep<256, 4, 1>), dim3((unsigned)n_prop), dim3(256), 0, k);
-            else if (wg_f == 2531)  // three waves per SIMD, one pair per round
-                LAUNCH_T(h, (k_frozen_sweep<256, 3, 1>), dim3((unsigned)n_prop), dim3(256), 0, k);
-            else if (wg_f == 2551)  // five waves per SIMD (96 registers), one pair per round
-                LAUNCH_T(h, (k_frozen_sweep<256, 5, 1>), dim3((unsigned)n_prop), dim3(256), 0, k);
+            if (big)
+                LAUNCH_T(h, (k_frozen_sweep<256, 3, 2, true>), dim3((unsigned)n_prop), dim3(256), 0, k);
             else
-#endif
                 LAUNCH_T(h, k_frozen_sweep<256>, dim3((unsigned)n_prop), dim3(256), 0, k);
             tick(h, 0, false);
             return DEMC_OK;
@@ -893,58 +796,32 @@ int launch_phase(demc_handle* h, KParams k) {
     if (snapshot)
         if (int rc = take_snapshot(false)) return rc;
     if (lr_shape && k.fuse_obs && k.fuse_accept) {
-        {
-            if (const char* e = experiment("DEMC_LR_EXIT")) k.n_split = -std::atoi(e);  // A/B experiments
-            if (const char* e = experiment("DEMC_LR_DEFER"))
-                if (e[0] == '0' && k.n_split >= 0) k.n_split = -100;
-            // Enough moving particles for two workgroups per CU (counted on the geometry's groups, so that a shard takes the
-            // same form as the whole run): 256 threads each -- one wave per SIMD per workgroup, two particles per CU out of
-            // step, one's prologue and row moves under the other's pass -- when two rows fit in the CU's LDS.
-            if (h->lr_two_lds != lr_lds) {  // (asked once per row size)
-                int nb = 0;
-                HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)k_longrow<256>, 256, lr_lds));
-                h->lr_two_lds = lr_lds;
-                h->lr_two_fit = nb >= 2;
-            }
-            const bool two_per_cu = (long long)h->geo_groups * k.n_act >= 2LL * h->n_cus && h->lr_two_fit;
-            int wg_lr = two_per_cu ? 256 : 512;
-            if (const char* e = experiment("DEMC_LR_WG")) wg_lr = std::atoi(e);  // A/B experiments
-#ifdef DEMC_EXPERIMENTS
-            {
-                static bool said = false;
-                if (!said) {
-                    said = true;
-                    int n256 = 0, n384 = 0, n512 = 0;
-                    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&n256, (const void*)k_longrow<256>, 256, lr_lds);
-                    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&n384, (const void*)k_longrow<384, 2>, 384, lr_lds);
-                    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&n512, (const void*)k_longrow<512, 2>, 512, lr_lds);
-                    std::fprintf(stderr, "experiment: k_longrow workgroups per CU at %zu B of dynamic LDS: <256> %d, <384,2> %d, <512,2> %d\n", lr_lds, n256, n384, n512);
-                }
-            }
-#endif
-            h->last = demc_handle::LastPlan();
-            h->last.k1 = 1; h->last.wg = wg_lr;
-            tick(h, 0, true);
-            // persistent: as many workgroups as are resident at once, each takes particles blockIdx.x, + gridDim.x, ... (the
-            // row moves of one particle then run inside the span loops of the next: demc_longrow.hpp).  A multiple of 8 keeps
-            // a workgroup's particles on its own XCD (the kernel's blockIdx -> group mapping).
-            long long grid_lr = (long long)(wg_lr == 512 ? 1 : 2) * h->n_cus;
-            if (const char* e = experiment("DEMC_LR_GRID")) grid_lr = std::atoll(e);  // A/B experiments
-            if (grid_lr > n_prop || grid_lr < 1) grid_lr = n_prop;
-            if ((k.n_groups & 7) == 0 && grid_lr >= 8) grid_lr &= ~7LL;
-            if (wg_lr == 256)
-                LAUNCH_T(h, k_longrow<256>, dim3((unsigned)grid_lr), dim3(256), lr_lds, k);
-#ifdef DEMC_EXPERIMENTS
-            else if (wg_lr == 384)
-                LAUNCH_T(h, (k_longrow<384, 2>), dim3((unsigned)grid_lr), dim3(384), lr_lds, k);
-            else if (wg_lr == 1024)  // (512 threads, two workgroups per CU)
-                LAUNCH_T(h, (k_longrow<512, 2>), dim3((unsigned)grid_lr), dim3(512), lr_lds, k);
-#endif
-            else
-                LAUNCH_T(h, k_longrow<512>, dim3((unsigned)grid_lr), dim3(512), lr_lds, k);
-            tick(h, 0, false);
-            return DEMC_OK;
+        // Enough moving particles for two workgroups per CU (counted on the geometry's groups, so that a shard takes the
+        // same form as the whole run): 256 threads each -- one wave per SIMD per workgroup, two particles per CU out of
+        // step, one's prologue and row moves under the other's pass -- when two rows fit in the CU's LDS.
+        if (h->lr_two_lds != lr_lds) {  // (asked once per row size)
+            int nb = 0;
+            HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)k_longrow<256>, 256, lr_lds));
+            h->lr_two_lds = lr_lds;
+            h->lr_two_fit = nb >= 2;
         }
+        const bool two_per_cu = (long long)h->geo_groups * k.n_act >= 2LL * h->n_cus && h->lr_two_fit;
+        const int wg_lr = two_per_cu ? 256 : 512;
+        h->last = demc_handle::LastPlan();
+        h->last.k1 = 1; h->last.wg = wg_lr;
+        tick(h, 0, true);
+        // persistent: as many workgroups as are resident at once, each takes particles blockIdx.x, + gridDim.x, ... (the
+        // row moves of one particle then run inside the span loops of the next: demc_longrow.hpp).  A multiple of 8 keeps
+        // a workgroup's particles on its own XCD (the kernel's blockIdx -> group mapping).
+        long long grid_lr = (long long)(wg_lr == 512 ? 1 : 2) * h->n_cus;
+        if (grid_lr > n_prop || grid_lr < 1) grid_lr = n_prop;
+        if ((k.n_groups & 7) == 0 && grid_lr >= 8) grid_lr &= ~7LL;
+        if (wg_lr == 256)
+            LAUNCH_T(h, k_longrow<256>, dim3((unsigned)grid_lr), dim3(256), lr_lds, k);
+        else
+            LAUNCH_T(h, k_longrow<512>, dim3((unsigned)grid_lr), dim3(512), lr_lds, k);
+        tick(h, 0, false);
+        return DEMC_OK;
     }
     tick(h, 0, true);
     const int tail = tail_of(k);
@@ -981,8 +858,6 @@ void plan_resident(demc_handle* h) {
     const demc_config& c = h->c;
     h->res_ok = false;
     if (c.fuse != 0 || c.schedule != DEMC_SCHED_TWO_COLOUR || c.partner_kind != DEMC_PARTNER_CURRENT || c.Np < 4) return;
-    if (const char* e = experiment("DEMC_RESIDENT"))  // A/B experiments
-        if (e[0] == '0') return;
     int lpp_max = pow2_ceil((c.D + 1) / 2);
     if (lpp_max > 64) return;
     const int n_act = c.Np - c.Np / 2;
@@ -1026,7 +901,6 @@ int launch_resident(demc_handle* h, long long iter0, int n_iters) {
     k.n_split = 1; k.exclude_self = 0; k.own_in_pool = 1; k.tile_rows = c.Np; k.tile_in_lds = 1;
     k.scr_doubles = h->res_scr_doubles;
     k.plan = (k.lpp >= 4) ? 1 : 0;
-    if (const char* e = experiment("DEMC_K1_PLAN")) k.plan = k.plan && e[0] == '1';  // A/B experiments
     h->last = demc_handle::LastPlan();
     h->last.k1 = 2; h->last.wg = h->res_wg; h->last.tile = 1; h->last.tail = tail_of(k); h->last.plain = lean_level(h, k);
     tick(h, 0, true);
@@ -1052,9 +926,7 @@ void plan_lean(demc_handle* h) {
         for (const DimTab& t : h->h_tab) ref = ref || t.kind == PR_NORMAL_REF;
         const size_t doubles = (size_t)c.Np * c.D + (size_t)c.Np + (size_t)(c.Np - c.Np / 2) + (size_t)(256 / 16) * c.D +
                                (h->family == FAM_LNR ? (size_t)kLogPhiRows * kLogPhiRow : 0);
-        bool on = !ref && doubles * sizeof(double) <= kMaxDynLds;
-        if (const char* e = experiment("DEMC_LEAN_OBS")) on = on && e[0] == '1';  // A/B experiments
-        if (on) { h->lean_obs_ok = true; h->lean_obs_lds = doubles * sizeof(double); }
+        if (!ref && doubles * sizeof(double) <= kMaxDynLds) { h->lean_obs_ok = true; h->lean_obs_lds = doubles * sizeof(double); }
     }
     // DE-MC_Z (history partners, the synchronous schedule) on the same family in SUFFSTAT mode: the lean body with partner rows
     // from the history, one launch per iteration (step_body) -- all it needs in LDS are select_base's cumulative weights and the
@@ -1066,9 +938,7 @@ void plan_lean(demc_handle* h) {
         (c.Np - c.Np / 2) * 4 <= 512 && h->hist) {
         bool ref = false;
         for (const DimTab& t : h->h_tab) ref = ref || t.kind == PR_NORMAL_REF;
-        bool on = !ref;
-        if (const char* e = experiment("DEMC_LEAN_HIST")) on = on && e[0] == '1';  // A/B experiments
-        if (on) {
+        if (!ref) {
             const int wgh = (c.Np - c.Np / 2) * 4 > 256 ? 512 : 256;
             h->lean_hist_ok = true; h->lean_wg = wgh;
             // cdf | chunk offsets | centred rows | A^-1 fragments [2][8][64]
@@ -1081,8 +951,6 @@ void plan_lean(demc_handle* h) {
     if (h->family != FAM_MVN_FULL || c.D != h->d || h->d > 32 || c.fuse != 0 || c.schedule != DEMC_SCHED_TWO_COLOUR ||
         c.partner_kind != DEMC_PARTNER_CURRENT || c.Np < 4)
         return;
-    if (const char* e = experiment("DEMC_LEAN"))  // A/B experiments
-        if (e[0] == '0') return;
     if (h->n_seg < 1) return;  // (the prior table must fit its run-length form)
     for (const DimTab& t : h->h_tab)
         if (t.kind == PR_NORMAL_REF) return;  // (hierarchical scale priors: the general kernel)
@@ -1114,31 +982,6 @@ void plan_lean(demc_handle* h) {
         bytes += xbytes;
     }
     h->lean_stream_ok = !dir; h->lean_direct_ok = dir; h->lean_wg = wg; h->lean_stream_lds = bytes;
-    h->lean_st_C = h->st_C; h->lean_st_chunk_tiles = h->st_chunk_tiles; h->lean_st_x_lds = h->st_x_lds; h->lean_st_occ = 1;
-    if (dir) return;
-#ifdef DEMC_EXPERIMENTS
-    // A/B builds only (DEMC_LEAN_OCC2=1) -- TWO workgroups per CU (D = 8, the instance compiled for it): twice the chunks, so that
-    // the grid is twice the CU count and a CU holds workgroups of two different groups ("two latency chains on a
-    // CU") -- taken when BOTH are resident at once by the runtime's own occupancy figure (every workgroup of the grid must be: the
-    // chunks of a group spin on each other's hand-over).  Measured in round 5 at BASELINE cfg2 (profiles/r05/NOTES.md): 0.1664 ms
-    // per launch against 0.1407 with one workgroup per CU (0.257 / 0.304 of the matrix peak; past burn-in 0.291 / 0.343): the
-    // two workgroups of a CU run in step, their matrix stages collide, and sixteen chunks make the hand-over longer.  Not shipped.
-    {
-        const int gg = h->geo_groups > c.n_groups ? h->geo_groups : c.n_groups;
-        const int C2 = 2 * h->st_C;
-        bool want = h->n_seg == 1 && c.D == 8 && h->st_x_lds && C2 <= 16 && (long long)C2 * gg <= 2LL * h->n_cus && h->n_tiles / C2 >= 8;
-        const char* e = experiment("DEMC_LEAN_OCC2");
-        want = want && e && e[0] == '1';
-        if (want) {
-            const int chunk2 = (h->n_tiles + C2 - 1) / C2;
-            const size_t bytes2 = bytes - xbytes + (size_t)(chunk2 + 1) * (h->dpad / 4) * 64 * sizeof(double);
-            int nb = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)k_res_mvn<256, true, 8, 0, 2>, 256, bytes2) == hipSuccess && nb >= 2) {
-                h->lean_st_C = C2; h->lean_st_chunk_tiles = chunk2; h->lean_st_occ = 2; h->lean_stream_lds = bytes2;
-            }
-        }
-    }
-#endif
 }
 
 int launch_lean(demc_handle* h, long long iter0, int n_iters, bool stream) {
@@ -1148,15 +991,14 @@ int launch_lean(demc_handle* h, long long iter0, int n_iters, bool stream) {
     k.sx = stream ? nullptr : h->sx;
     k.Ainv = h->Ainv;
     if (stream) {
-        k.st_C = h->lean_st_C; k.st_nact_max = h->st_nact_max; k.st_x_lds = h->lean_st_x_lds; k.st_chunk_tiles = h->lean_st_chunk_tiles;
+        k.st_C = h->st_C; k.st_nact_max = h->st_nact_max; k.st_x_lds = h->st_x_lds; k.st_chunk_tiles = h->st_chunk_tiles;
         k.n_tiles = h->n_tiles; k.Xf = h->Xf; k.st_gran = h->st_gran; k.st_err = h->st_err;
         k.st_rows = 0;
-        if (const char* e = experiment("DEMC_OCC2_DELAY")) k.st_rows = std::atoi(e);  // A/B experiments (k_res_mvn<...,OCC 2>: start offset in cycles)
-        if (k.n_groups * h->lean_st_C > h->n_cus * h->lean_st_occ) return fail(h, DEMC_EINVAL, "streaming-resident grid exceeds what is resident at once");
-        HIPCHK(hipMemsetAsync(h->st_gran, 0, 2 * (size_t)c.n_groups * h->lean_st_C * h->st_nact_max * 2 * sizeof(unsigned long long), h->stream));
+        if (k.n_groups * h->st_C > h->n_cus) return fail(h, DEMC_EINVAL, "streaming-resident grid exceeds what is resident at once");
+        HIPCHK(hipMemsetAsync(h->st_gran, 0, 2 * (size_t)c.n_groups * h->st_C * h->st_nact_max * 2 * sizeof(unsigned long long), h->stream));
     }
     tick(h, 0, true);
-    const unsigned grid = (unsigned)(k.n_groups * (stream ? h->lean_st_C : 1));
+    const unsigned grid = (unsigned)(k.n_groups * (stream ? h->st_C : 1));
     const size_t lds = stream ? h->lean_stream_lds : h->lean_lds;
     // instances with the row length folded in (cfg3: 32, cfg2: 8) when the prior table is one segment
     const int dt = (h->n_seg == 1 && (c.D == 32 || c.D == 8)) ? c.D : 0;
@@ -1164,10 +1006,6 @@ int launch_lean(demc_handle* h, long long iter0, int n_iters, bool stream) {
     h->last.k1 = 4; h->last.wg = h->lean_wg; h->last.stream = stream; h->last.dt = dt;
     h->last.big = stream && h->lean_direct_ok;  // (the DIRECT instance: named below)
     void (*fn)(KParams) = nullptr;
-#ifdef DEMC_EXPERIMENTS
-    if (stream && h->lean_st_occ == 2) fn = k_res_mvn<256, true, 8, 0, 2>;  // (plan_lean: D = 8 only)
-    else
-#endif
     if (stream && h->lean_direct_ok) fn = dt == 8 ? k_res_mvn<512, true, 8, 0, 1, false, true> : k_res_mvn<256, true, 32, 0, 1, false, true>;
     else if (stream) fn = dt == 8 ? k_res_mvn<256, true, 8> : dt == 32 ? k_res_mvn<256, true, 32> : k_res_mvn<256, true, 0>;
     else if (h->lean_wg == 512) fn = dt == 8 ? k_res_mvn<512, false, 8> : dt == 32 ? k_res_mvn<512, false, 32> : k_res_mvn<512, false, 0>;
@@ -1269,8 +1107,6 @@ void plan_stream(demc_handle* h) {
     // the WHOLE population (geometry_groups), not from this shard's: C fixes the summation order of the cross terms, and a
     // shard must make the choices of the unsharded run to reproduce it bit for bit (demc_create_multi, demc.h).
     const int gg = h->geo_groups > c.n_groups ? h->geo_groups : c.n_groups;
-    if (const char* e = experiment("DEMC_STREAM_RES"))  // A/B experiments
-        if (e[0] == '0') return;
     const int nact_max = c.Np - c.Np / 2;
     if (nact_max > 512) return;
     const double phase_flop = 2.0 * (double)nact_max * gg * (double)h->N * h->dpad;
@@ -1297,8 +1133,7 @@ void plan_stream(demc_handle* h) {
     if (x_lds) bytes += xbytes;
     // hand-over granules [2][n_groups][C][nact_max][2] and the time-out word
     if (h->st_gran) { hipFree(h->st_gran); h->st_gran = nullptr; }
-    // (room for 2 C chunks: the lean kernel may cut the tiles twice as fine, plan_lean)
-    if (hipMalloc((void**)&h->st_gran, 2 * (size_t)c.n_groups * 2 * C * nact_max * 2 * sizeof(unsigned long long)) != hipSuccess) return;
+    if (hipMalloc((void**)&h->st_gran, 2 * (size_t)c.n_groups * C * nact_max * 2 * sizeof(unsigned long long)) != hipSuccess) return;
     if (!h->st_err) {
         if (hipHostMalloc((void**)&h->st_err, sizeof(unsigned), hipHostMallocMapped) != hipSuccess) return;
         *h->st_err = 0u;
@@ -1446,7 +1281,6 @@ int size_k1_lds(demc_handle* h) {
     const size_t scr = scr_fam ? scr_rows : 0;
     const size_t tile = (size_t)c.Np * D * sizeof(double);
     h->tile_in_lds = (tile + cdf + ainv + xb + scr <= 96 * 1024) ? 1 : 0;
-    if (const char* e = experiment("DEMC_K1_TILE")) h->tile_in_lds = (e[0] == '1') && h->tile_in_lds;  // A/B experiments
     h->k1_tile_bytes = h->tile_in_lds ? tile : 0;
     h->k1_scr_bytes = scr;
     h->k1_lds = h->k1_tile_bytes + cdf + ainv + xb + scr;
@@ -1468,24 +1302,13 @@ int size_k1_lds(demc_handle* h) {
             for (int lean = 0; lean < 3; ++lean)
                 HIPCHK(hipFuncSetAttribute((const void*)k1_stream_instance(wgs, tail, lean),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynLds));
-#ifdef DEMC_EXPERIMENTS
-    h->lba_wide_ok = kLbaTableBytes <= kMaxDynLds &&
-                     hipFuncSetAttribute((const void*)k_lba_loglike<512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLbaTableBytes) == hipSuccess;
-#endif
     HIPCHK(hipFuncSetAttribute((const void*)k_longrow<512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynLds));
     HIPCHK(hipFuncSetAttribute((const void*)k_longrow<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynLds));
-#ifdef DEMC_EXPERIMENTS
-    HIPCHK(hipFuncSetAttribute((const void*)k_longrow<384, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynLds));
-    HIPCHK(hipFuncSetAttribute((const void*)k_longrow<512, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynLds));
-#endif
     {
         void (*lean[])(KParams) = {k_res_mvn<256, false, 0>, k_res_mvn<256, false, 8>, k_res_mvn<256, false, 32>,
                                    k_res_mvn<512, false, 0>, k_res_mvn<512, false, 8>, k_res_mvn<512, false, 32>,
                                    k_res_mvn<256, true, 0>,  k_res_mvn<256, true, 8>,  k_res_mvn<256, true, 32>,
                                    k_res_mvn<512, true, 8, 0, 1, false, true>, k_res_mvn<256, true, 32, 0, 1, false, true>,
-#ifdef DEMC_EXPERIMENTS
-                                   k_res_mvn<256, true, 8, 0, 2>,
-#endif
                                    k_res_mvn<256, false, 0, 1>, k_res_mvn<256, false, 8, 1>, k_res_mvn<256, false, 32, 1>,
                                    k_res_mvn<512, false, 0, 1>, k_res_mvn<512, false, 8, 1>, k_res_mvn<512, false, 32, 1>,
                                    k_res_mvn<256, false, 0, 2>, k_res_mvn<256, false, 8, 2>, k_res_mvn<256, false, 32, 2>,
@@ -1652,10 +1475,6 @@ int32_t demc_create(const demc_config* cfg, demc_handle** out) {
                 break;
             }
         }
-    }
-    if (const char* e = experiment("DEMC_LPP")) {  // A/B experiments: fewer lanes per particle = less replicated scalar work
-        const int v = std::atoi(e);
-        if (v >= 1 && v <= 512 && v != 128 && (v & (v - 1)) == 0 && (v <= h->lpp || v == 256 || v == 512)) h->lpp = v;
     }
     int rc_lds = size_k1_lds(h);
     if (rc_lds != DEMC_OK) return rc_lds;
@@ -3083,7 +2902,6 @@ int32_t demc_last_kernels(demc_handle* h, char* out, int32_t nbytes) {
     else if (L.k2 == 4) s += " + k_user_loglike";
     else if (L.k2 == 5) s += " + k_direct_mvn<" + std::to_string(L.ks) + ">";
     else if (L.k2 == 6) s += " + k_user_row";
-    else if (L.k2 == 7) s += " + k_lba_loglike<512>";
     if (L.k3) s += " + k_accept_store";
     std::snprintf(out, (size_t)nbytes, "%s", s.c_str());
     return DEMC_OK;

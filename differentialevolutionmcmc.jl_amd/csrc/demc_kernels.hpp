@@ -280,7 +280,7 @@ __device__ inline double loglike_from_stats(const KParams& p, double s, double a
 // >= 1e-10 and of order one or below for any plausible proposal; a product that nevertheless leaves the double range is
 // redone with a log per trial; a -Inf trial contributes a factor 0 and log 0 = -Inf).
 constexpr int kLbaBatch = 8;
-template <int NA, int RS = kPhiRow>
+template <int NA>
 __device__ __forceinline__ double lba_range_sum(const KParams& p, const double* th, long long i0, long long i1, int stride, const double* tab) {
     const int na = NA > 0 ? NA : p.n_acc;
     double nu[8], nuS[8];
@@ -296,7 +296,7 @@ __device__ __forceinline__ double lba_range_sum(const KParams& p, const double* 
     for (int a = 0; a < (NA > 0 ? NA : 8); ++a)
         if (a < na) {
             double q, Ph;
-            phiS_Phi_table<RS>(tab, -nuS[a], q, Ph);
+            phiS_Phi_table(tab, -nuS[a], q, Ph);
             pneg *= Ph;
         }
     const double inv_norm = 1.0 / (1.0 - pneg);
@@ -312,14 +312,14 @@ __device__ __forceinline__ double lba_range_sum(const KParams& p, const double* 
         double prod = 1.0;
 #pragma unroll
         for (int j = 0; j < kLbaBatch; ++j)
-            prod *= lba_trial<NA, RS>(tab, na, nu, nuS, kS, bS, tau, inv_A, inv_SA, inv_norm, (int)cc[j], rr[j]);
+            prod *= lba_trial<NA>(tab, na, nu, nuS, kS, bS, tau, inv_A, inv_SA, inv_norm, (int)cc[j], rr[j]);
         if (__builtin_expect(!(prod < 1e300), 0)) {
             // The density scales like 1/b and b = A + k has no lower bound inside the bounds (0, Inf): eight huge factors could
             // leave the double range and log(+Inf) would be accepted for ever.  Cold path: the batch again, a log per trial.
             double s = 0.0;
 #pragma unroll 1
             for (int j = 0; j < kLbaBatch; ++j)
-                s += log(lba_trial<NA, RS>(tab, na, nu, nuS, kS, bS, tau, inv_A, inv_SA, inv_norm, (int)p.data[i + (long long)j * stride],
+                s += log(lba_trial<NA>(tab, na, nu, nuS, kS, bS, tau, inv_A, inv_SA, inv_norm, (int)p.data[i + (long long)j * stride],
                                        p.data2[i + (long long)j * stride]));
             acc += s;
         } else
@@ -327,7 +327,7 @@ __device__ __forceinline__ double lba_range_sum(const KParams& p, const double* 
     }
     double prod = 1.0;
     for (; i < i1; i += stride)
-        prod *= lba_trial<NA, RS>(tab, na, nu, nuS, kS, bS, tau, inv_A, inv_SA, inv_norm, (int)p.data[i], p.data2[i]);
+        prod *= lba_trial<NA>(tab, na, nu, nuS, kS, bS, tau, inv_A, inv_SA, inv_norm, (int)p.data[i], p.data2[i]);
     return acc + log(prod);
 }
 
@@ -2226,19 +2226,19 @@ __global__ __launch_bounds__(256, 2) void k_lba_wave(KParams p, int n_chunks, un
         // batches of a proposal -- with the scalar-branch form behind it measured 2 % SLOWER, profiles/r05/NOTES.md section 10)
 #pragma unroll
         for (int j = 0; j < kLbaBatch; ++j)
-            prod *= lba_trial<NA, kPhiRow, double>(s_tab, na, nu, nuS, kS, bS, tau, inv_A, inv_SA, inv_norm, cc[j], rr[j]);
+            prod *= lba_trial<NA, double>(s_tab, na, nu, nuS, kS, bS, tau, inv_A, inv_SA, inv_norm, cc[j], rr[j]);
         if (__builtin_expect(!(prod < 1e300), 0)) {  // (see lba_range_sum: the batch again, a log per trial)
             double s2 = 0.0;
 #pragma unroll 1
             for (int j = 0; j < kLbaBatch; ++j)
-                s2 += log(lba_trial<NA, kPhiRow, double>(s_tab, na, nu, nuS, kS, bS, tau, inv_A, inv_SA, inv_norm, cc[j], rr[j]));
+                s2 += log(lba_trial<NA, double>(s_tab, na, nu, nuS, kS, bS, tau, inv_A, inv_SA, inv_norm, cc[j], rr[j]));
             acc += s2;
         } else
             acc += log(prod);
     }
 #pragma unroll 1
     for (long long i = base + lane; i < i1; i += 64)  // the ragged end of the data (fewer than 512 trials): a log per trial
-        acc += log(lba_trial<NA, kPhiRow, double>(s_tab, na, nu, nuS, kS, bS, tau, inv_A, inv_SA, inv_norm, p.data[i], p.data2[i]));
+        acc += log(lba_trial<NA, double>(s_tab, na, nu, nuS, kS, bS, tau, inv_A, inv_SA, inv_norm, p.data[i], p.data2[i]));
     acc = subgroup_sum(acc, 64);
     if (lane == 0) p.partial[(size_t)chunk * p.P + slot] = acc;
     if (clk) {  // (demc_timing_clock: as k_direct_mvn -- end-of-life stamps only, behind every load of the kernel)
@@ -2253,46 +2253,6 @@ __global__ __launch_bounds__(256, 2) void k_lba_wave(KParams p, int n_chunks, un
     }
 }
 #endif
-
-#ifdef DEMC_EXPERIMENTS
-// ------------------------------------------------------------------------------------------------
-// K2 (LBA, Examples/Run_LBA.jl:33-37) with EIGHT shifted copies of the table -- an A/B EXPERIMENT (make EXPERIMENTS=1,
-// DEMC_LBA_WIDE=1), not the product path.  k_obs_loglike keeps one packed copy of the Phi polynomials in LDS (80-byte rows);
-// the lanes of a wave are proposals at the same trial, a population that has not converged reads a different row in almost
-// every lane, and the LDS pipe -- the kernel's limiting pipe, busy 0.80 -- spent 56 % of its active cycles on bank conflicts
-// (profiles/r03).  Here rows are padded to 128 bytes and copy j is shifted by 16 j bytes; lane l reads copy l & 7, the row
-// address is a shift.  Measured (cfg5, 20 steps, twice each): 1.584 ms per launch against 1.522 for the packed copy -- 4 %
-// SLOWER.  Why it cannot win: a ds_read_b128 is served in four groups of SIXTEEN lanes over 64 banks
-// (MI355X_MICROARCH.md, LDS), so a conflict-free gather needs sixteen independently shifted slots per group -- sixteen copies
-// of 256-byte-stride rows (560 KB) -- while eight copies of 128-byte rows leave two lanes per slot that collide whenever their
-// rows have the same parity, and the 140 KB cost a third of the occupancy (one workgroup of 512 per CU instead of three of
-// 256).  Same arithmetic per evaluation as k_obs_loglike (lba_range_sum), same partial sums per chunk: same bits.
-// ------------------------------------------------------------------------------------------------
-constexpr int kLbaCopyDoubles = kPhiIntervals * 16 + 2;  // 137 rows of 128 B + the 16-byte shift to the next copy
-constexpr size_t kLbaTableBytes = (size_t)8 * kLbaCopyDoubles * sizeof(double);
-template <int WG>
-__global__ __launch_bounds__(WG) void k_lba_loglike(KParams p, int n_chunks) {
-    extern __shared__ __attribute__((aligned(16))) double s_lba[];  // [8][137][16] (+ 2 doubles per copy); 16-byte reads
-    for (int i = threadIdx.x; i < 8 * kPhiIntervals * kPhiRow; i += WG) {
-        const int c = i / (kPhiIntervals * kPhiRow), e = i - c * (kPhiIntervals * kPhiRow);
-        const int r = e / kPhiRow, k = e - r * kPhiRow;
-        s_lba[c * kLbaCopyDoubles + r * 16 + k] = kPhiTable[e];
-    }
-    __syncthreads();
-    const int q = blockIdx.x * WG + threadIdx.x;
-    const int n_prop = p.n_groups * p.n_act;
-    const int chunk = blockIdx.y;
-    if (q >= n_prop) return;
-    const size_t slot = (size_t)slot_of(p, q);
-    const double* th = p.prop + slot * p.D;
-    const long long per = (p.N + n_chunks - 1) / n_chunks;
-    const long long i0 = chunk * per, i1 = (i0 + per < p.N) ? i0 + per : p.N;
-    const double* tab = s_lba + (threadIdx.x & 7) * kLbaCopyDoubles;  // the lane's own copy
-    const double acc = p.n_acc == 3 ? lba_range_sum<3, 16>(p, th, i0, i1, 1, tab)
-                       : p.n_acc == 2 ? lba_range_sum<2, 16>(p, th, i0, i1, 1, tab) : lba_range_sum<0, 16>(p, th, i0, i1, 1, tab);
-    p.partial[(size_t)chunk * p.P + slot] = acc;
-}
-#endif  // DEMC_EXPERIMENTS
 
 // ------------------------------------------------------------------------------------------------
 // K2 (hierarchical families): cost O(D) per proposal: one workgroup per proposal, lanes across subjects,

@@ -37,18 +37,6 @@ namespace demc {
 // value held by lane `src` of the wave, as a wave-uniform scalar
 __device__ inline uint32_t wave_get(uint32_t v, int src) { return (uint32_t)__builtin_amdgcn_readlane((int)v, src); }
 
-// (A/B build only, make EXPERIMENTS=1: leave the kernel at a given point, to time what lies before it --
-// tools/lr_exit_experiment.py; the product build compiles these away)
-#ifdef DEMC_EXPERIMENTS
-#define DEMC_LR_EXIT(n) \
-    if (p.n_split == -(n)) return
-#define DEMC_LR_NEXT(n) \
-    if (p.n_split == -(n)) continue  /* inside the persistent loop: on to the workgroup's next particle */
-#else
-#define DEMC_LR_EXIT(n)
-#define DEMC_LR_NEXT(n)
-#endif
-
 #ifndef DEMC_LR_PREFETCH
 #define DEMC_LR_PREFETCH 1  // blocks requested ahead of the one being worked on in the span loops
 #endif
@@ -58,7 +46,7 @@ __device__ inline uint32_t wave_get(uint32_t v, int src) { return (uint32_t)__bu
 // 0.219.  More workgroups in flight make the launch SLOWER: the phase is not waiting for latency that more waves could hide.)
 // PER_CU workgroups of WG threads share a CU (each parks an 80 KB row in LDS: at most two): WG / 64 * PER_CU / 4 waves per SIMD,
 // which is what the register budget follows from -- (256, 2) and (512, 1), the forms that ship: two waves per SIMD, 256 registers.
-// Round 5 measured the forms with MORE waves per CU (A/B builds only; profiles/r05/NOTES.md): (384, 2) -- three waves per SIMD,
+// Round 5 measured the forms with MORE waves per CU (profiles/r05/NOTES.md): (384, 2) -- three waves per SIMD,
 // 168 registers, no spill, seven rounds per particle instead of ten, two workgroups per CU confirmed by the occupancy query --
 // 0.216 ms per launch of the whole cfg4 against 0.167; (512, 2) does not fit twice (LDS) and spills at 128 registers: 0.239.
 // With round 3's global-scratch forms and round 4's LITE instance that makes four measurements that say the same: this kernel
@@ -89,7 +77,6 @@ __global__ __launch_bounds__(WG, (WG / 64 * PER_CU + 3) / 4) void k_longrow(KPar
 #ifdef DEMC_STAMPS
     const unsigned long long t_real0__ = __builtin_amdgcn_s_memrealtime();  // (100 MHz: the shader clock of the run = stamp 10 / stamp 18 x 100 MHz)
 #endif
-    DEMC_LR_EXIT(1);
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // (wave: an SGPR)
     const int D = p.D, Np = p.Np;
     // the prior-table segments go to LDS: loaded now, stored just before the first barrier (no wait on a cold line here)
@@ -600,7 +587,6 @@ __global__ __launch_bounds__(WG, (WG / 64 * PER_CU + 3) / 4) void k_longrow(KPar
         isg_obs = 1.0 / sg_obs;
     }
     const double n_bin = p.c0;
-    DEMC_LR_NEXT(2);
     int oob = 0;
     double prior = 0.0, like = 0.0, s1 = 0.0, s2 = 0.0;
     unsigned long long wbits = 0;  // which of this lane's pairs lie (partly) inside the block of the sweep
@@ -936,7 +922,6 @@ __global__ __launch_bounds__(WG, (WG / 64 * PER_CU + 3) / 4) void k_longrow(KPar
             }
         }
     }
-    DEMC_LR_NEXT(3);
     DEMC_STAMP_AT(15, 64, DEMC_STAMP_NOW());      // spans done
     DEMC_STAMP_AT(13, 0, DEMC_STAMP_NOW());       // ... by wave 0
     DEMC_STAMP_AT(14, WG - 64, DEMC_STAMP_NOW());  // ... by the last wave
@@ -1015,7 +1000,6 @@ __global__ __launch_bounds__(WG, (WG / 64 * PER_CU + 3) / 4) void k_longrow(KPar
     DEMC_STAMP_AT(5, 64, DEMC_STAMP_NOW());  // the pass over the row done
     DEMC_STAMP_AT(2, 64, n_fast_blocks__);
     DEMC_STAMP_AT(3, 64, n_done);
-    DEMC_LR_NEXT(4);
     // ---- one reduction for everything: waves on the DPP network, then the fixed tree over the waves through LDS ----
     prior = subgroup_sum(prior, 64); like = subgroup_sum(like, 64); oob = subgroup_sum(oob, 64);
     if (kind == 1) { s1 = subgroup_sum(s1, 64); s2 = subgroup_sum(s2, 64); }
@@ -1063,7 +1047,6 @@ __global__ __launch_bounds__(WG, (WG / 64 * PER_CU + 3) / 4) void k_longrow(KPar
             p.id_hist[hrow] = (int)p.id[slot];
         }
     }
-    DEMC_LR_NEXT(5);
     double* trow = p.theta + slot * D;
     double* hrow = (p.store_row >= 0) ? p.hist + ((size_t)p.store_row * p.P + slot) * p.hist_ld : nullptr;
     // in a block sweep an accepted crossover proposal differs from the row only inside the block: write only those
@@ -1071,12 +1054,7 @@ __global__ __launch_bounds__(WG, (WG / 64 * PER_CU + 3) / 4) void k_longrow(KPar
     // A whole row to move and another particle to follow in this workgroup: its span loops do it (see `pend` at the top).
     // (The LDS copy is complete for an accepted particle -- frozen scalars are parked as they are; a rejected one's row is
     // its row in HBM, which nothing writes in this launch.)
-#ifdef DEMC_EXPERIMENTS
-    const bool defer_allowed = p.n_split != -100;  // (A/B build: DEMC_LR_DEFER=0 keeps every row move at its particle's end)
-#else
-    constexpr bool defer_allowed = true;
-#endif
-    if (defer_allowed && fast_ok && (hrow || (acc && !masked)) && vb + (int)gridDim.x < n_prop && n_blocks <= 32 * WG && !p.write_prop) {
+    if (fast_ok && (hrow || (acc && !masked)) && vb + (int)gridDim.x < n_prop && n_blocks <= 32 * WG && !p.write_prop) {
         pend = true; pend_acc = acc != 0; pend_masked = masked; pend_trow = trow; pend_hrow = hrow;
         pend_wbits = wbits;
         if (!acc) {  // rejected: the history row is the current row -- back into the LDS copy, four blocks' loads in flight
@@ -1171,10 +1149,6 @@ __global__ __launch_bounds__(WG, (WG / 64 * PER_CU + 3) / 4) void k_longrow(KPar
 #ifdef DEMC_LONGROW_EXTERN  // the instances live in demc_longrow.cpp (its own translation unit, its own compiler flags)
 extern template __global__ void k_longrow<256>(KParams);
 extern template __global__ void k_longrow<512>(KParams);
-#ifdef DEMC_EXPERIMENTS
-extern template __global__ void k_longrow<384, 2>(KParams);
-extern template __global__ void k_longrow<512, 2>(KParams);
-#endif
 #endif
 
 }  // namespace demc

@@ -44,10 +44,11 @@ namespace demc {
 // (crossover.jl:241), the third one in the slot the base row has in instance 2 (a snooker update reads no base particle), projects
 // two of them onto Pt - Pz (utilities.jl:239-246: three dot products, summed over the quad) and carries adjust_loglike's norms
 // (crossover.jl:268-273) into the decision; the other particles of the wave take the crossover as in instance 2, in or past burn-in.
-// OCC = 2 (STREAM, 256 threads; A/B builds only): the instance compiled for TWO workgroups per CU -- 256 registers per lane, the
-// observation stage's accumulators in AGPRs inside that budget -- so that a small population (BASELINE cfg2: 32 groups on 256 CUs)
-// is cut into twice as many observation chunks and a CU holds workgroups of two DIFFERENT groups, one group's dependent chain
-// (draws, proposal, hand-over round trip, decision) under the other's matrix stage.  Measured slower (plan_lean).
+// OCC = 2 (STREAM, 256 threads): the register budget of TWO workgroups per CU -- 256 registers per lane, the observation stage's
+// accumulators in AGPRs inside that budget -- so that a small population (BASELINE cfg2: 32 groups on 256 CUs) is cut into twice as
+// many observation chunks and a CU holds workgroups of two DIFFERENT groups, one group's dependent chain (draws, proposal, hand-over
+// round trip, decision) under the other's matrix stage.  Measured slower in round 5 (profiles/r05/NOTES.md); no
+// instance is built with it any more.
 // ISO = MvNormal(mu, sigma^2 I) with sigma a PARAMETER (theta = (mu[d], sigma), D = d + 1 <= 32; test/multivariate_normal_tests.jl:
 // 16-33, which the reference runs as DE-MC_Z with snooker, :50-59): the same body with the quadratic form on the vector pipe inside
 // the quad -- aux = |mu - xbar|^2 and S = (mu - xbar) . sum_i x~_i are eight products per lane and one quad sum each, sigma comes
@@ -339,16 +340,6 @@ __global__ __launch_bounds__(WG, (WG == 256 && (!STREAM || OCC == 2)) ? 2 : 1) v
     // the three-round cumulative weights or the two-level base pick move the phase: it is a chain of dependent latencies at two
     // waves per SIMD with the vector pipe 0.39 busy, not a count of instructions.)
     if (STREAM) draw_phase(0, pre_mine, pre_nzA, pre_nzB);
-#ifdef DEMC_EXPERIMENTS
-    if constexpr (STREAM && OCC == 2) {
-        // A/B only: the second workgroup of every CU (the upper half of the grid: other groups) starts p.st_rows shader cycles late,
-        // so that the two workgroups of a CU run OUT of step -- one's matrix stage under the other's proposal / hand-over stages
-        if (p.st_rows > 0 && blockIdx.x >= gridDim.x / 2) {
-            const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-            while (__builtin_amdgcn_s_memtime() - t0 < (unsigned long long)p.st_rows) __builtin_amdgcn_s_sleep(8);
-        }
-    }
-#endif
     for (long long step = 0; step < n_steps; ++step) {
         DEMC_STAMP_RESET();
         const int ph = (int)(step & 1);
@@ -1029,16 +1020,10 @@ __global__ __launch_bounds__(WG, (WG == 256 && (!STREAM || OCC == 2)) ? 2 : 1) v
     X(256, true, 8, 0, 1, false) \
     X(256, true, 32, 0, 1, false)
 #define DEMC_RESMVN_INSTANCES_DIR(X) X(512, true, 8, 0, 1, false, true) X(256, true, 32, 0, 1, false, true)  // the DIRECT streaming-resident form
-#ifdef DEMC_EXPERIMENTS
-#define DEMC_RESMVN_INSTANCES_EXP(X) X(256, true, 8, 0, 2, false)  // A/B only: two streaming workgroups per CU
-#else
-#define DEMC_RESMVN_INSTANCES_EXP(X)
-#endif
 #ifdef DEMC_RESMVN_EXTERN
 #define DEMC_X_(...) extern template __global__ void k_res_mvn<__VA_ARGS__>(KParams);
 DEMC_RESMVN_INSTANCES(DEMC_X_)
 DEMC_RESMVN_INSTANCES_DIR(DEMC_X_)
-DEMC_RESMVN_INSTANCES_EXP(DEMC_X_)
 #undef DEMC_X_
 #endif
 

@@ -61,7 +61,7 @@ else:
         eng.set_history_rows(0, np.stack([prob["init"](a.n_groups * a.Np, rng0) for _ in range(16)]))
     eng.set_state(prob["init"](a.n_groups * a.Np, rng0))
     eng.step(17 if hist else 1, 30)
-    n_wg = min(512, (a.n_groups * a.Np) // 16) if (os.environ.get('DEMC_RESIDENT') == '0' or hist) else a.n_groups  # resident: one per group
+    n_wg = min(512, (a.n_groups * a.Np) // 16) if hist else a.n_groups  # resident: one per group
 if os.environ.get("STAMP_NWG"):  # (e.g. 256: k_res_mvn<..., HIST> is one workgroup per group; slots beyond hold an earlier kernel's stamps)
     n_wg = int(os.environ["STAMP_NWG"])
 w_prop = eng.get_trace()["w_prop"]
