@@ -25,6 +25,7 @@ EXPORTS = [
     "demc_comm_unique_id", "demc_comm_init", "demc_comm_destroy", "demc_comm_set_overlap", "demc_migration_exchange",
     "demc_migration_exchange_async", "demc_comm_allreduce", "demc_comm_stats",
     "demc_create_multi", "demc_destroy_multi", "demc_multi_last_error", "demc_multi_size", "demc_multi_shard", "demc_multi_step",
+    "demc_set_model_sim",
 ]
 COMM_ID_BYTES = 128
 _NOT_STATUS = {"demc_last_error": C.c_char_p, "demc_multi_last_error": C.c_char_p, "demc_multi_shard": C.c_void_p}
@@ -131,6 +132,7 @@ def load():
     L.demc_set_model.argtypes = [H, C.c_int32, _dp, _lp, C.c_int32, _dp, C.c_int32]
     L.demc_set_model_source.argtypes = [H, C.c_char_p, _dp, _lp, C.c_int32, _dp, C.c_int32]
     L.demc_set_model_source_row.argtypes = [H, C.c_char_p, _dp, _lp, C.c_int32, _dp, C.c_int32, C.c_int32]
+    L.demc_set_model_sim.argtypes = [H, C.c_int32, C.c_int32, C.c_int64, C.c_char_p, _dp, C.c_int64, _dp, C.c_int32]
     L.demc_set_priors.argtypes = [H, _ip, _dp, _dp, _ip]
     L.demc_set_bounds.argtypes = [H, _dp, _dp]
     L.demc_set_blocks.argtypes = [H, _bp, C.c_int32]
@@ -264,6 +266,15 @@ class HipEngine:
         hyper = None if hyper is None else np.ascontiguousarray(np.asarray(hyper, dtype=np.float64).ravel())
         self._ck(self.L.demc_set_model_source_row(self.h, source.encode(), _d(data), dims.ctypes.data_as(_lp), dims.size,
                                                   _d(hyper), 0 if hyper is None else hyper.size, 1 if has_prior else 0))
+
+    def set_model_sim(self, simulator, estimator, n_sim, data, hyper=None, source=None):
+        """simulation-based likelihood (demc_set_model_sim, include/demc.h): `simulator` / `estimator` are the DEMC_SIM_* /
+        DEMC_SIMEST_* codes, data the scalar observations, hyper = [bandwidth, the simulator's own ...], source the HIP text of
+        demc_user_sim for DEMC_SIM_USER"""
+        data = np.ascontiguousarray(np.asarray(data, dtype=np.float64).ravel())
+        hyper = None if hyper is None else np.ascontiguousarray(np.asarray(hyper, dtype=np.float64).ravel())
+        self._ck(self.L.demc_set_model_sim(self.h, simulator, estimator, n_sim, None if source is None else source.encode(),
+                                           _d(data), data.size, _d(hyper), 0 if hyper is None else hyper.size))
 
     def set_priors(self, kind, a, b, ref=None):
         kind = np.ascontiguousarray(kind, dtype=np.int32)

@@ -35,6 +35,8 @@
 #include "demc_resmvn.hpp"
 #define DEMC_RESOBS_EXTERN
 #include "demc_resobs.hpp"
+#define DEMC_SIMLIKE_EXTERN  // k_sim_loglike in demc_simlike.cpp
+#include "demc_simlike.hpp"
 
 using namespace demc;
 
@@ -94,6 +96,11 @@ struct demc_handle {
     bool user_has_prior = false;  // ... whose source also defines demc_user_prior_row
     long long* user_dims = nullptr;
     int user_ndims = 0;
+    // simulation-based likelihood (demc_set_model_sim, demc_simlike.hpp); a user simulator's module lives in user_module / user_kernel
+    int sim_kind = -1, sim_est = 0, sim_n = 0;
+    double sim_bw = 0.0;
+    double* sim_logtab = nullptr;   // [n_sim + 1] log(c / n_sim): the frequency estimator's terms
+    unsigned sim_entity_base = 0;   // demc_logpost: row r of a call is evaluated at entity r
     double c0 = 0, c1 = 0, c2 = 0;
     int partial_cap = 64;
     int lpp = 1;
@@ -458,6 +465,43 @@ int clock_buffer(demc_handle* h, size_t wgs, unsigned long long** out) {
     return DEMC_OK;
 }
 
+// The text of demc_simlike.hpp, embedded by the build (csrc/Makefile): what hiprtc compiles around a user simulator.
+const char* kSimKernelSource =
+#include "demc_simlike_src.inc"
+    ;
+const char* sim_name(int sim) { return sim == SIM_NORMAL ? "normal" : sim == SIM_BINOMIAL ? "binomial" : "user"; }
+
+// K2 of a simulation-based model: one workgroup per proposal, the simulated sample in LDS (demc_simlike.hpp)
+int launch_sim_loglike(demc_handle* h, KParams& k, long long n_prop) {
+    SimKParams s;
+    std::memset(&s, 0, sizeof s);
+    s.n_groups = k.n_groups; s.Np = k.Np; s.D = k.D; s.a_lo = k.a_lo; s.n_act = k.n_act; s.group_offset = k.group_offset;
+    s.n_sim = h->sim_n; s.nhyper = h->user_nhyper > 0 ? h->user_nhyper - 1 : 0;
+    s.n_obs = h->N; s.iter = k.iter; s.seed = k.seed; s.sweep = k.sweep; s.entity_base = h->sim_entity_base;
+    s.bandwidth = h->sim_bw; s.n_pow = std::pow((double)h->sim_n, -0.2);
+    s.prop = k.prop; s.partial = k.partial; s.obs = h->data; s.hyper = h->user_hyper ? h->user_hyper + 1 : nullptr;
+    s.logtab = h->sim_logtab; s.glist = k.glist;
+    const size_t lds = (size_t)h->sim_n * sizeof(double);
+    h->last.k2 = 9;
+    if (h->sim_kind == SIM_USER) {
+        size_t sz = sizeof s;
+        void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &s, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
+        tick(h, 2, true, true);
+        const hipError_t e = hipModuleLaunchKernel(h->user_kernel, (unsigned)n_prop, 1, 1, 256, 1, 1, 0, h->stream, nullptr, cfg);
+        tick(h, 2, false, true);
+        if (e != hipSuccess) return fail(h, DEMC_EHIP, std::string("hipModuleLaunchKernel: ") + hipGetErrorString(e));
+        return DEMC_OK;
+    }
+    tick(h, 2, true);
+    const dim3 grid((unsigned)n_prop);
+    if (h->sim_kind == SIM_NORMAL && h->sim_est == EST_KDE) LAUNCH_T(h, (k_sim_loglike<SIM_NORMAL, EST_KDE>), grid, dim3(256), lds, s);
+    else if (h->sim_kind == SIM_NORMAL) LAUNCH_T(h, (k_sim_loglike<SIM_NORMAL, EST_FREQ>), grid, dim3(256), lds, s);
+    else if (h->sim_est == EST_KDE) LAUNCH_T(h, (k_sim_loglike<SIM_BINOMIAL, EST_KDE>), grid, dim3(256), lds, s);
+    else LAUNCH_T(h, (k_sim_loglike<SIM_BINOMIAL, EST_FREQ>), grid, dim3(256), lds, s);
+    tick(h, 2, false);
+    return DEMC_OK;
+}
+
 // K2 dispatch for the active set described by k.  Sets k.n_partials.
 int launch_loglike(demc_handle* h, KParams& k) {
     const long long n_prop = (long long)k.n_groups * k.n_act;
@@ -592,6 +636,10 @@ int launch_loglike(demc_handle* h, KParams& k) {
             tick(h, 2, false, true);
             if (e != hipSuccess) return fail(h, DEMC_EHIP, std::string("hipModuleLaunchKernel: ") + hipGetErrorString(e));
             k.n_partials = (int)want;
+        } break;
+        case FAM_SIM: {
+            if (int rc = launch_sim_loglike(h, k, n_prop)) return rc;
+            k.n_partials = 1;
         } break;
         case FAM_HIER_BINOMIAL:
         case FAM_HIER_GAUSSIAN: {
@@ -1321,6 +1369,9 @@ int size_k1_lds(demc_handle* h) {
                                    k_res_mvn<512, false, 31, 1, 1, true>, k_res_mvn<512, false, 31, 2, 1, true>, k_res_mvn<512, false, 31, 3, 1, true>};
         for (auto f : lean) HIPCHK(hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynLds));
         HIPCHK(hipFuncSetAttribute((const void*)k_res_obs<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynLds));
+#define DEMC_X_(...) HIPCHK(hipFuncSetAttribute((const void*)k_sim_loglike<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynLds));
+        DEMC_SIM_INSTANCES(DEMC_X_)
+#undef DEMC_X_
     }
     plan_resident(h);
     plan_stream(h);
@@ -1507,6 +1558,7 @@ int32_t demc_destroy(demc_handle* h) {
     if (h->user_module) hipModuleUnload(h->user_module);
     if (h->user_hyper) hipFree(h->user_hyper);
     if (h->user_dims) hipFree(h->user_dims);
+    if (h->sim_logtab) hipFree(h->sim_logtab);
     free_replay(h);
     for (int i = 0; i < demc_handle::kGlistRing; ++i) {
         if (h->glist_buf[i]) hipFree(h->glist_buf[i]);
@@ -1565,7 +1617,7 @@ int32_t demc_set_model(demc_handle* h, int32_t family, const double* data, const
     for (double** p : {&h->data, &h->Ainv, &h->Ypad, &h->Xf, &h->sx, &h->xbar})
         if (*p) { hipFree(*p); *p = nullptr; }
     h->family = -1; h->N = 0; h->d = 0; h->n_acc = 0; h->dpad = 0; h->n_tiles = 0; h->c0 = h->c1 = h->c2 = 0; h->data2_off = 0;
-    h->dp_direct = 0; h->direct_wgs_per_cu = 0;
+    h->dp_direct = 0; h->direct_wgs_per_cu = 0; h->sim_kind = -1;
     std::vector<double> dev;  // what goes to h->data
     switch (family) {
         case DEMC_FAM_GAUSSIAN:
@@ -1766,7 +1818,7 @@ static int32_t set_model_source_impl(demc_handle* h, const char* hip_source, con
     if (h->user_dims) { hipFree(h->user_dims); h->user_dims = nullptr; }
     if (h->user_module) { hipModuleUnload(h->user_module); h->user_module = nullptr; h->user_kernel = nullptr; }
     h->family = -1; h->d = 0; h->n_acc = 0; h->dpad = 0; h->n_tiles = 0; h->c0 = h->c1 = h->c2 = 0; h->data2_off = 0;
-    h->user_row = row; h->user_has_prior = row && has_prior; h->user_ndims = ndims;
+    h->user_row = row; h->user_has_prior = row && has_prior; h->user_ndims = ndims; h->sim_kind = -1;
     // compile: kernarg struct + declarations + user source + kernel, for gfx950
     const std::string src = std::string(row && has_prior ? "#define DEMC_USER_HAS_PRIOR 1\n" : "") + kUserStruct +
                             (row ? kUserRowPrologue : kUserPrologue) + hip_source + (row ? kUserRowKernel : kUserKernel);
@@ -1819,6 +1871,94 @@ int32_t demc_set_model_source_row(demc_handle* h, const char* hip_source, const 
                                   const double* hyper, int32_t nhyper, int32_t flags) {
     if (flags & ~DEMC_USER_HAS_PRIOR) return h ? fail(h, DEMC_EINVAL, "unknown flag") : DEMC_EINVAL;
     return set_model_source_impl(h, hip_source, data, dims, ndims, hyper, nhyper, true, (flags & DEMC_USER_HAS_PRIOR) != 0);
+}
+
+// Simulation-based likelihood (demc_simlike.hpp).  hyper[0] = the KDE bandwidth (<= 0 or absent: the rule of thumb), hyper[1..] the
+// simulator's own hyper-parameters.
+int32_t demc_set_model_sim(demc_handle* h, int32_t simulator, int32_t estimator, int64_t n_sim, const char* hip_source,
+                           const double* data, int64_t n_obs, const double* hyper, int32_t nhyper) {
+    return guarded(h, [&]() -> int32_t {
+    if (!h) return DEMC_EINVAL;
+    USE_DEVICE(h);
+    if (simulator != DEMC_SIM_NORMAL && simulator != DEMC_SIM_BINOMIAL && simulator != DEMC_SIM_USER)
+        return fail(h, DEMC_EINVAL, "demc_set_model_sim: unknown simulator");
+    if (estimator != DEMC_SIMEST_KDE_EPANECHNIKOV && estimator != DEMC_SIMEST_FREQUENCY)
+        return fail(h, DEMC_EINVAL, "demc_set_model_sim: unknown estimator");
+    if (n_sim < 2) return fail(h, DEMC_EINVAL, "demc_set_model_sim: n_sim < 2 (a density estimate needs at least two simulated values)");
+    if (n_sim > kSimMaxN)
+        return fail(h, DEMC_EINVAL, "demc_set_model_sim: n_sim = " + std::to_string(n_sim) + " is above the cap of " + std::to_string(kSimMaxN) +
+                                        " simulated values (the sample of a proposal is held in LDS)");
+    if (n_obs < 1 || !data) return fail(h, DEMC_EINVAL, "demc_set_model_sim: n_obs >= 1 observations required");
+    if (nhyper < 0 || (nhyper > 0 && !hyper)) return fail(h, DEMC_EINVAL, "demc_set_model_sim: nhyper > 0 without hyper");
+    if (simulator == DEMC_SIM_USER && (!hip_source || !hip_source[0]))
+        return fail(h, DEMC_EINVAL, "demc_set_model_sim: DEMC_SIM_USER needs hip_source (a definition of demc_user_sim)");
+    if (simulator != DEMC_SIM_USER && hip_source && hip_source[0])
+        return fail(h, DEMC_EINVAL, "demc_set_model_sim: hip_source given with a registered simulator");
+    if (simulator == DEMC_SIM_NORMAL && h->c.D != 2) return fail(h, DEMC_EINVAL, "SIM_NORMAL: theta=(mu,sigma)");
+    if (simulator == DEMC_SIM_BINOMIAL) {
+        if (h->c.D != 1) return fail(h, DEMC_EINVAL, "SIM_BINOMIAL: theta=p");
+        if (nhyper < 2 || !(hyper[1] >= 1.0 && hyper[1] <= 1024.0 && hyper[1] == std::floor(hyper[1])))
+            return fail(h, DEMC_EINVAL, "SIM_BINOMIAL: hyper=[bandwidth, n_trials], n_trials an integer in [1, 1024]");
+        if (n_sim * (((int64_t)hyper[1] + 3) / 4) > 0x7fffffffLL) return fail(h, DEMC_EINVAL, "SIM_BINOMIAL: too many Philox blocks per proposal");
+    }
+    if (estimator == DEMC_SIMEST_FREQUENCY)
+        for (int64_t j = 0; j < n_obs; ++j)
+            if (!(data[j] == std::floor(data[j])))
+                return fail(h, DEMC_EINVAL, "demc_set_model_sim: the FREQUENCY estimator needs integer-valued data (observation " + std::to_string(j) + " is not)");
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (double** p : {&h->data, &h->Ainv, &h->Ypad, &h->Xf, &h->sx, &h->xbar, &h->user_hyper, &h->sim_logtab})
+        if (*p) { hipFree(*p); *p = nullptr; }
+    if (h->user_dims) { hipFree(h->user_dims); h->user_dims = nullptr; }
+    if (h->user_module) { hipModuleUnload(h->user_module); h->user_module = nullptr; h->user_kernel = nullptr; }
+    h->family = -1; h->N = 0; h->d = 0; h->n_acc = 0; h->dpad = 0; h->n_tiles = 0; h->c0 = h->c1 = h->c2 = 0; h->data2_off = 0;
+    h->user_row = false; h->user_has_prior = false; h->user_ndims = 0; h->user_nhyper = 0; h->sim_kind = -1;
+    if (simulator == DEMC_SIM_USER) {
+        // the one kernel text (demc_simlike.hpp) with n_sim and the estimator compiled in, the user's function behind it
+        const std::string src = "#define DEMC_SIM_JIT 1\n#define DEMC_SIM_JIT_N " + std::to_string(n_sim) + "\n#define DEMC_SIM_JIT_EST " +
+                                std::to_string(estimator) + "\n" + kSimKernelSource + "\n" + hip_source + "\n";
+        hiprtcProgram prog;
+        if (hiprtcCreateProgram(&prog, src.c_str(), "demc_user_sim.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS)
+            return fail(h, DEMC_EHIP, "hiprtcCreateProgram failed");
+        const char* opts[] = {"--offload-arch=" DEMC_ARCH_STR, "-O3", "-std=c++17", "-ffp-contract=off"};
+        const hiprtcResult cr = hiprtcCompileProgram(prog, 4, opts);
+        if (cr != HIPRTC_SUCCESS) {
+            size_t ls = 0;
+            hiprtcGetProgramLogSize(prog, &ls);
+            std::string log(ls, '\0');
+            if (ls) hiprtcGetProgramLog(prog, &log[0]);
+            hiprtcDestroyProgram(&prog);
+            return fail(h, DEMC_EINVAL, std::string("user simulator does not compile: ") + hiprtcGetErrorString(cr) + "\n" + log);
+        }
+        size_t cs = 0;
+        hiprtcGetCodeSize(prog, &cs);
+        std::vector<char> code(cs);
+        hiprtcGetCode(prog, code.data());
+        hiprtcDestroyProgram(&prog);
+        HIPCHK(hipModuleLoadData(&h->user_module, code.data()));
+        HIPCHK(hipModuleGetFunction(&h->user_kernel, h->user_module, "k_sim_loglike_user"));
+    }
+    h->N = n_obs;
+    ALLOC(h->data, (size_t)n_obs);
+    HIPCHK(hipMemcpy(h->data, data, sizeof(double) * (size_t)n_obs, hipMemcpyHostToDevice));
+    // hyper as the kernels see it: [bandwidth, the simulator's own ...]
+    h->user_nhyper = nhyper > 0 ? nhyper : 1;
+    {
+        std::vector<double> hy((size_t)h->user_nhyper, 0.0);
+        for (int i = 0; i < nhyper; ++i) hy[(size_t)i] = hyper[i];
+        ALLOC(h->user_hyper, hy.size());
+        HIPCHK(hipMemcpy(h->user_hyper, hy.data(), sizeof(double) * hy.size(), hipMemcpyHostToDevice));
+        h->sim_bw = hy[0] > 0.0 ? hy[0] : 0.0;
+    }
+    if (estimator == DEMC_SIMEST_FREQUENCY) {
+        std::vector<double> lt((size_t)n_sim + 1);
+        for (int64_t c = 0; c <= n_sim; ++c) lt[(size_t)c] = std::log((double)c / (double)n_sim);  // (log 0 = -Inf: a count of zero)
+        ALLOC(h->sim_logtab, lt.size());
+        HIPCHK(hipMemcpy(h->sim_logtab, lt.data(), sizeof(double) * lt.size(), hipMemcpyHostToDevice));
+    }
+    h->sim_kind = simulator; h->sim_est = estimator; h->sim_n = (int)n_sim;
+    h->family = FAM_SIM;
+    return size_k1_lds(h);
+    });
 }
 
 static int upload_dimtab(demc_handle* h) {
@@ -2784,7 +2924,9 @@ int32_t demc_logpost(demc_handle* h, const double* theta, int64_t n, double* out
         HIPCHK(hipStreamSynchronize(h->stream));
         HIPCHK(hipMemset(h->scratch_theta, 0, P * D * sizeof(double)));
         HIPCHK(hipMemcpy(h->scratch_theta, theta + (size_t)off * D, m * D * sizeof(double), hipMemcpyHostToDevice));
+        h->sim_entity_base = (unsigned)off;  // (a simulated likelihood evaluates row r of the call at entity r)
         int rc = evaluate_rows(h, h->scratch_theta, h->scratch_w);
+        h->sim_entity_base = 0;
         if (rc != DEMC_OK) return rc;
         HIPCHK(hipStreamSynchronize(h->stream));
         HIPCHK(hipGetLastError());
@@ -2902,6 +3044,7 @@ int32_t demc_last_kernels(demc_handle* h, char* out, int32_t nbytes) {
     else if (L.k2 == 4) s += " + k_user_loglike";
     else if (L.k2 == 5) s += " + k_direct_mvn<" + std::to_string(L.ks) + ">";
     else if (L.k2 == 6) s += " + k_user_row";
+    else if (L.k2 == 9) s += std::string(" + k_sim_loglike<") + (h->sim_est == EST_KDE ? "kde" : "frequency") + "," + sim_name(h->sim_kind) + ">";
     if (L.k3) s += " + k_accept_store";
     std::snprintf(out, (size_t)nbytes, "%s", s.c_str());
     return DEMC_OK;

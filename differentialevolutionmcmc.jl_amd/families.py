@@ -11,6 +11,10 @@ import numpy as np
 FAM_GAUSSIAN, FAM_MVN_ISO, FAM_MVN_FULL, FAM_BINOMIAL, FAM_HIER_BINOMIAL, FAM_HIER_GAUSSIAN, FAM_LBA, FAM_LNR, \
     FAM_RASTRIGIN = range(9)
 FAM_USER = 100
+# simulation-based likelihoods (demc_set_model_sim): simulator and estimator codes (include/demc.h)
+SIM_NORMAL, SIM_BINOMIAL, SIM_USER = 0, 1, 100
+SIMEST_KDE_EPANECHNIKOV, SIMEST_FREQUENCY = 0, 1
+SIM_MAX_N = 16384
 PRIOR_FLAT, PRIOR_NORMAL, PRIOR_HALFCAUCHY, PRIOR_UNIFORM, PRIOR_BETA, PRIOR_NORMAL_REF, PRIOR_GAMMA, \
     PRIOR_EXPONENTIAL, PRIOR_LOGNORMAL, PRIOR_CAUCHY = range(10)
 
@@ -223,3 +227,89 @@ class SourceLikelihood(Likelihood):
     def pack(self, data, shapes):
         x = np.ascontiguousarray(np.asarray(data, dtype=np.float64))
         return x, list(x.shape), self.hyper
+
+
+# ---- simulation-based likelihoods: the model is a simulator (Examples/KDE_Example.jl, Examples/Binomial_ABC.jl) ----
+class Simulator:
+    code = None
+    source = None
+    n_params = None  # scalars of theta the simulator reads (None: any)
+
+    def hyper(self):
+        return []
+
+
+class SimNormal(Simulator):
+    """rand(Normal(mu, sigma), n_sim) (Examples/KDE_Example.jl:12); theta = (mu, sigma)."""
+    code = SIM_NORMAL
+    n_params = 2
+
+
+class SimBinomial(Simulator):
+    """rand(Binomial(n, theta)) n_sim times (Examples/Binomial_ABC.jl:19); theta = p."""
+    code = SIM_BINOMIAL
+    n_params = 1
+
+    def __init__(self, n):
+        if int(n) != n or not 1 <= int(n) <= 1024:
+            raise ValueError("SimBinomial(n): n must be an integer in [1, 1024]")
+        self.n = int(n)
+
+    def hyper(self):
+        return [float(self.n)]
+
+
+class SimSource(Simulator):
+    """A simulator written as a HIP device function, one call per simulated value:
+
+        __device__ double demc_user_sim(const double* theta, int D, const double* hyper, int nhyper, demc_sim_rng* rng);
+
+    which draws with demc_sim_uniform(rng) / demc_sim_normal(rng) / demc_sim_u32(rng) (include/demc.h)."""
+    code = SIM_USER
+
+    def __init__(self, source, hyper=None):
+        if not isinstance(source, str) or not source.strip():
+            raise ValueError("SimSource(source): HIP source defining demc_user_sim")
+        self.source = source
+        self._hyper = [] if hyper is None else [float(x) for x in np.asarray(hyper, dtype=np.float64).ravel()]
+
+    def hyper(self):
+        return self._hyper
+
+
+class SimulatedLikelihood(Likelihood):
+    """A likelihood without a closed form, estimated per proposal from n_sim simulated values (demc_set_model_sim):
+    estimator "kde" = sum(log(max(1e-10, pdf(kde, x)))) with an Epanechnikov kernel (Examples/KDE_Example.jl:10-18; bandwidth
+    0.0 = the rule of thumb 0.9 sd n^(-1/5)), "frequency" = log(#{sim == x} / n_sim) summed over the observations
+    (Examples/Binomial_ABC.jl:15-22).  Data: scalar observations (or the reference's (N=..., k=...) with a SimBinomial)."""
+    family = None  # not a DEMC_FAM_* family: sampler.configure_engine routes it to set_model_sim
+    ESTIMATORS = {"kde": SIMEST_KDE_EPANECHNIKOV, "frequency": SIMEST_FREQUENCY}
+
+    def __init__(self, simulator, estimator="kde", n_sim=10_000, bandwidth=0.0):
+        if not isinstance(simulator, Simulator) or simulator.code is None:
+            raise TypeError("SimulatedLikelihood(simulator): SimNormal(), SimBinomial(n) or SimSource(source)")
+        if estimator not in self.ESTIMATORS:
+            raise ValueError(f"estimator must be one of {sorted(self.ESTIMATORS)}")
+        if int(n_sim) != n_sim or not 2 <= int(n_sim) <= SIM_MAX_N:
+            raise ValueError(f"n_sim must be an integer in [2, {SIM_MAX_N}] (the sample of a proposal is held in LDS)")
+        if not np.isfinite(bandwidth) or bandwidth < 0:
+            raise ValueError("bandwidth must be finite and >= 0 (0: the rule of thumb)")
+        self.simulator, self.estimator, self.n_sim, self.bandwidth = simulator, estimator, int(n_sim), float(bandwidth)
+
+    def pack(self, data, shapes):
+        """-> (observations, [N], hyper = [bandwidth, the simulator's own ...])"""
+        if isinstance(data, dict) or hasattr(data, "k"):  # the reference's NamedTuple (N = ..., k = ...)
+            data = data["k"] if isinstance(data, dict) else data.k
+        x = np.atleast_1d(np.asarray(data, dtype=np.float64)).ravel()
+        if x.size < 1:
+            raise ValueError("SimulatedLikelihood: no observations")
+        if self.estimator == "frequency" and not np.all(x == np.floor(x)):
+            raise ValueError("the frequency estimator needs integer-valued data")
+        D = int(sum(int(np.prod(s)) if len(s) else 1 for s in shapes))
+        if self.simulator.n_params is not None and D != self.simulator.n_params:
+            raise ValueError(f"{type(self.simulator).__name__} reads {self.simulator.n_params} parameters, the model has {D}")
+        return x, [x.size], [self.bandwidth] + list(self.simulator.hyper())
+
+    def configure(self, eng, data, shapes):
+        x, _, hyper = self.pack(data, shapes)
+        eng.set_model_sim(self.simulator.code, self.ESTIMATORS[self.estimator], self.n_sim, x, hyper, self.simulator.source)

@@ -4,7 +4,7 @@ import numpy as np
 
 from . import _ffi
 from .chains import Chains
-from .families import PRIOR_NORMAL_REF, Priors, SourceLikelihood
+from .families import PRIOR_NORMAL_REF, Priors, SimulatedLikelihood, SourceLikelihood
 from .structs import (DE, HIPBackend, LOGLIKE_MODES, MCMCThreads, SCHEDULES, DEModel, Particle, maximize)
 
 
@@ -114,6 +114,11 @@ def engine_config(de, lay, n_iter, backend, n_groups_local=None, group_offset=0,
 
 
 def configure_engine(eng, model, lay):
+    if isinstance(model.loglike, SimulatedLikelihood):  # a simulator, not a density: demc_set_model_sim
+        model.loglike.configure(eng, model.data, lay["shapes"])
+        eng.set_priors(lay["kind"], lay["a"], lay["b"], lay["ref"])
+        eng.set_bounds(lay["lo"], lay["hi"])
+        return
     data, dims, hyper = model.loglike.pack(model.data, lay["shapes"])
     if isinstance(model.loglike, SourceLikelihood) and model.loglike.row:
         eng.set_model_source_row(model.loglike.source, data, dims, hyper, has_prior=model.loglike.has_prior)

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define DEMC_VERSION 120 /* 0.1.2 */
+#define DEMC_VERSION 130 /* 0.1.3 */
 
 enum {
     DEMC_OK = 0,
@@ -187,6 +187,43 @@ int32_t demc_set_model_source(demc_handle* h, const char* hip_source, const doub
 #define DEMC_USER_HAS_PRIOR 1
 int32_t demc_set_model_source_row(demc_handle* h, const char* hip_source, const double* host_data, const int64_t* dims,
                                   int32_t ndims, const double* host_hyper, int32_t nhyper, int32_t flags);
+/* Simulation-based likelihood: the model is a SIMULATOR, its likelihood has no closed form and is estimated per proposal from
+ * n_sim simulated values -- probability density approximation (Examples/KDE_Example.jl, with Examples/KDE.jl: 10 000 draws of
+ * Normal(mu, sigma), an Epanechnikov kernel density estimate, sum_i log max(1e-10, pdf(kde, x_i))) and approximate Bayesian
+ * computation by matching counts (Examples/Binomial_ABC.jl:15-22: 10 000 Binomial(N, theta) counts, log(#{sim == k} / n_sim)).
+ * host_data = n_obs scalar observations.  For a proposal row theta evaluated at (iter, sweep, entity):
+ *   simulated sample s_0 .. s_{n_sim-1} from the addressed Philox stream 7 (DESIGN.md "Randomness"); entity = the GLOBAL slot
+ *   (group_offset + g) Np + p in a step -- shards draw what the single handle draws -- ; demc_set_state (weight == NULL) uses
+ *   iter = sweep = 0 and the global slot, demc_logpost iter = sweep = 0 and group_offset Np + the row's index in the call, so
+ *   demc_logpost(theta)[r] is the weight demc_set_state gives slot r.
+ *     DEMC_SIM_NORMAL    theta = (mu, sigma): s_i = mu + sigma z_i, four Box-Muller normals per Philox block
+ *     DEMC_SIM_BINOMIAL  theta = p, host_hyper = [bandwidth, n_trials], n_trials <= 1024: count i = successes among the words of
+ *                        its ceil(n_trials / 4) blocks, a trial succeeds when its 32-bit uniform is below p
+ *     DEMC_SIM_USER      hip_source defines
+ *         __device__ double demc_user_sim(const double* theta, int D, const double* hyper, int nhyper, demc_sim_rng* rng);
+ *                        (hyper = host_hyper + 1, nhyper - 1 entries), called once per simulated value; it draws with
+ *                        demc_sim_u32(rng) / demc_sim_uniform(rng) (one word, in (0,1)) / demc_sim_normal(rng) (two words), which
+ *                        consume the words of the Philox blocks (i << 8) | k, k = 0, 1, ... (mod 256) of value i in order.
+ *                        Compiled for gfx950 at this call (hiprtc) into the same kernel text as the registered simulators;
+ *                        compile errors come back through demc_last_error.  NULL for a registered simulator.
+ *   estimator
+ *     DEMC_SIMEST_KDE_EPANECHNIKOV  f(x) = 1/(n h) sum_i 3/4 max(0, 1 - ((x - s_i)/h)^2), loglike = sum_j log max(1e-10, f(x_j)),
+ *                        h = host_hyper[0] when nhyper >= 1 and it is > 0, else 0.9 sd n^(-1/5), sd the sample standard deviation
+ *                        (n - 1 in the denominator; sd == 0 makes the log-likelihood -Inf).  Two deviations from KernelDensity.jl as
+ *                        recalled (not pinned to a version): the density is summed exactly instead of binned on a 2048-point
+ *                        grid and interpolated, and the bandwidth rule leaves out min(sd, IQR / 1.34).
+ *     DEMC_SIMEST_FREQUENCY  loglike = sum_j log(#{s_i == x_j} / n); a count of zero gives -Inf (Binomial_ABC.jl:21); the data
+ *                        must be integer valued.
+ *   A non-finite simulated value makes the log-likelihood -Inf.  n_sim in [2, 16384] (the sample of a proposal is held in LDS;
+ *   above it: DEMC_EINVAL, nothing is truncated).  Pseudo-marginal semantics as in the reference: a particle keeps the noisy weight
+ *   it was accepted with, nothing is simulated again for a resting particle.  All sums run in a fixed order: same seed, same bits,
+ *   whatever the sharding.  Priors and bounds: demc_set_priors / demc_set_bounds, as for every family.  The update always runs
+ *   as proposal kernel -> k_sim_loglike<estimator,simulator> -> k_accept_store; demc_last_kernels names the middle one
+ *   "k_sim_loglike<kde|frequency,normal|binomial|user>". */
+enum { DEMC_SIM_NORMAL = 0, DEMC_SIM_BINOMIAL = 1, DEMC_SIM_USER = 100 };
+enum { DEMC_SIMEST_KDE_EPANECHNIKOV = 0, DEMC_SIMEST_FREQUENCY = 1 };
+int32_t demc_set_model_sim(demc_handle* h, int32_t simulator, int32_t estimator, int64_t n_sim, const char* hip_source,
+                           const double* host_data, int64_t n_obs, const double* host_hyper, int32_t nhyper);
 int32_t demc_set_priors(demc_handle* h, const int32_t* kind, const double* a, const double* b, const int32_t* ref);
 /* de.bounds flattened to one (lo,hi) per scalar; +-Inf allowed (utilities.jl:70-78) */
 int32_t demc_set_bounds(demc_handle* h, const double* lo, const double* hi);

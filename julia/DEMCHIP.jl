@@ -48,6 +48,32 @@ struct ModelSpec
     prior_ref::Vector{Int32}
 end
 
+"""
+Simulation-based model (include/demc.h, demc_set_model_sim): a simulator instead of a density -- the device form of
+Examples/KDE_Example.jl (`simulator = :normal`, `estimator = :kde`) and Examples/Binomial_ABC.jl (`simulator = :binomial`,
+`estimator = :frequency`, `sim_hyper = [N]`); `simulator = :user` with `source` = HIP text defining `demc_user_sim`.
+`data` are the scalar observations, `bandwidth = 0.0` the rule-of-thumb bandwidth, priors as in `ModelSpec`.
+"""
+struct SimModelSpec
+    simulator::Int32
+    estimator::Int32
+    n_sim::Int64
+    source::String
+    data::Vector{Float64}
+    hyper::Vector{Float64}     # [bandwidth, the simulator's own ...]
+    prior_kind::Vector{Int32}
+    prior_a::Vector{Float64}
+    prior_b::Vector{Float64}
+    prior_ref::Vector{Int32}
+end
+const SIMULATORS = Dict(:normal => Int32(0), :binomial => Int32(1), :user => Int32(100))
+const SIM_ESTIMATORS = Dict(:kde => Int32(0), :frequency => Int32(1))
+SimModelSpec(; simulator = :normal, estimator = :kde, n_sim = 10_000, source = "", data, bandwidth = 0.0,
+    sim_hyper = Float64[], prior_kind, prior_a, prior_b, prior_ref = zeros(Int32, length(prior_kind))) =
+    SimModelSpec(SIMULATORS[simulator], SIM_ESTIMATORS[estimator], n_sim, source, collect(Float64, data),
+        vcat(Float64(bandwidth), collect(Float64, sim_hyper)), prior_kind, prior_a, prior_b, prior_ref)
+const AnyModelSpec = Union{ModelSpec,SimModelSpec}
+
 struct HIPBackend
     schedule::Symbol      # :two_colour (default), :synchronous, or :sequential (the reference's own sweep; slow, for replay runs)
     loglike_mode::Symbol  # :streaming, :suffstat or :direct (include/demc.h DEMC_LOGLIKE_*)
@@ -139,10 +165,17 @@ function make_config(de::DE, D::Int, n_iter::Int, b; n_groups = de.n_groups, gro
 end
 
 "model, priors, bounds, the prior-draw history rows and the particles `ps` (one shard's, in slot order) onto handle `h`"
-function load_handle!(h, m::ModelSpec, de::DE, ps)
+set_model!(h, m::ModelSpec) =
+    check(h, @ccall LIB.demc_set_model(h::Ptr{Cvoid}, m.family::Int32, m.data::Ptr{Float64}, m.dims::Ptr{Int64},
+        Int32(length(m.dims))::Int32, m.hyper::Ptr{Float64}, Int32(length(m.hyper))::Int32)::Int32)
+set_model!(h, m::SimModelSpec) =
+    check(h, @ccall LIB.demc_set_model_sim(h::Ptr{Cvoid}, m.simulator::Int32, m.estimator::Int32, m.n_sim::Int64,
+        (isempty(m.source) ? C_NULL : m.source)::Cstring, m.data::Ptr{Float64}, Int64(length(m.data))::Int64,
+        m.hyper::Ptr{Float64}, Int32(length(m.hyper))::Int32)::Int32)
+
+function load_handle!(h, m::AnyModelSpec, de::DE, ps)
     GC.@preserve m begin
-        check(h, @ccall LIB.demc_set_model(h::Ptr{Cvoid}, m.family::Int32, m.data::Ptr{Float64}, m.dims::Ptr{Int64},
-            Int32(length(m.dims))::Int32, m.hyper::Ptr{Float64}, Int32(length(m.hyper))::Int32)::Int32)
+        set_model!(h, m)
         check(h, @ccall LIB.demc_set_priors(h::Ptr{Cvoid}, m.prior_kind::Ptr{Int32}, m.prior_a::Ptr{Float64},
             m.prior_b::Ptr{Float64}, m.prior_ref::Ptr{Int32})::Int32)
     end
@@ -188,7 +221,7 @@ end
 Same contract as `sample(model, de, MCMCThreads(), n_iter)` (src/main.jl:62-71): `sample_init` and
 `bundle_samples` run unchanged on the host; the iteration loop (src/main.jl:33-38) becomes `demc_step`.
 """
-function sample(model::DEModel, de::DE, b::HIPBackend, n_iter::Int; model_spec::ModelSpec, progress = false, kwargs...)
+function sample(model::DEModel, de::DE, b::HIPBackend, n_iter::Int; model_spec::AnyModelSpec, progress = false, kwargs...)
     groups = sample_init(model, de, n_iter)                      # src/main.jl:263-271 (allocates de.samples)
     particles = vcat(groups...)
     P = length(particles); D = length(flatten(particles[1].Θ))
@@ -268,7 +301,7 @@ The threaded method's contract (src/main.jl:62-71) on several GPUs from ONE proc
 `r*G+1:(r+1)*G` with their particles and history; `demc_multi_step` enqueues every shard's iterations and the one
 all-gather per migration (grouped ncclAllGather over xGMI) before it waits for any of them.
 """
-function sample(model::DEModel, de::DE, b::HIPMultiBackend, n_iter::Int; model_spec::ModelSpec, progress = false, kwargs...)
+function sample(model::DEModel, de::DE, b::HIPMultiBackend, n_iter::Int; model_spec::AnyModelSpec, progress = false, kwargs...)
     groups = sample_init(model, de, n_iter)
     particles = vcat(groups...)
     P = length(particles); D = length(flatten(particles[1].Θ))
