@@ -37,6 +37,7 @@
 #include "demc_resobs.hpp"
 #define DEMC_SIMLIKE_EXTERN  // k_sim_loglike in demc_simlike.cpp
 #include "demc_simlike.hpp"
+#include "demc_instances.hpp"  // one table per templated kernel, built from the lists above: every choice of an instance goes through them
 
 using namespace demc;
 
@@ -82,7 +83,7 @@ struct demc_handle {
     int n_tiles = 0;
     int ks_t = 0, n_kpass = 0;  // MFMA k-steps per pass (template) and passes over the dimensions
     int dp_direct = 0;          // DIRECT mode: padded length of a whitened observation row (8 / 16 / 32 / 64)
-    int direct_wgs_per_cu = 0;  // ... resident workgroups of its kernel per CU (asked once)
+    int direct_wgs_per_cu = 0;  // ... resident workgroups of its kernel per CU (wgs_per_cu: asked once)
     int obs_wgs_per_cu = 0;     // the same for k_obs_loglike
     int lba_wave_wgs_per_cu = 0;  // ... and k_lba_wave
     double *data = nullptr, *Ainv = nullptr, *Ypad = nullptr, *Xf = nullptr, *sx = nullptr, *xbar = nullptr;
@@ -110,6 +111,9 @@ struct demc_handle {
     bool res_ok = false;  // resident K1 (plan_resident)
     int res_lpp = 0, res_wg = 0, res_scr_doubles = 0;
     size_t res_lds = 0;
+    // the instances whose template arguments are fixed by the model, resolved when it is planned (a missing one fails there, not at
+    // step 1); the general resident forms per LEAN level (which a trace or a replay lowers to 0 at run time: lean_level)
+    const K1Inst *res_k1[3] = {}, *st_k1[3] = {}, *lean_k1 = nullptr, *lean_obs_k1 = nullptr;
     // streaming-resident form (plan_stream): the MvNormal observation stream inside the resident kernel
     bool st_ok = false;
     bool tf_cheap_obs = false;  // set_tail_flags' "the likelihood is cheap enough for K1" of the last call (launch_phase reads it)
@@ -180,11 +184,12 @@ struct demc_handle {
     struct demc_multi* multi = nullptr;
     bool multi_sealed = false;  // the set is built: demc_set_stream is refused from here on
     // which kernel instances the last update launched (demc_last_kernels: lets a test name the instance it compared)
+    enum K2Kind { K2_NONE, K2_CROSS_MFMA, K2_DIRECT_MVN, K2_OBS, K2_LBA_WAVE, K2_HIER, K2_USER, K2_USER_ROW, K2_SIM };
     struct LastPlan {
-        int k1 = -1;  // 0 k_propose per phase, 1 k_longrow, 2 k_propose resident, 3 k_propose streaming-resident, 4 k_res_mvn, 5 k_frozen_sweep, 6 k_res_obs
-        int wg = 0, tile = 0, tail = 0, plain = 0, dt = 0, stream = 0, hist = 0, iso = 0, big = 0;
-        int k2 = 0;   // 0 none (fused into K1), 1 k_cross_mfma, 2 k_obs_loglike, 3 k_hier_loglike, 4 user plug-in
-        int ks = 0, k3 = 0;
+        const K1Inst* k1 = nullptr;  // the entry that was launched (its key names it)
+        K2Kind k2 = K2_NONE;         // the likelihood kernel behind it (none: fused into K1) ...
+        InstKey k2_key = {};         // ... and the key of its instance (k_cross_mfma, k_direct_mvn; k_sim_loglike: <SIM, EST>, SIM_USER for the JIT one)
+        bool k3 = false;             // k_accept_store followed
     } last;
     // timing
     bool timing = false;
@@ -307,6 +312,25 @@ void drain_events(demc_handle* h) {
     h->events.clear();
 }
 
+// The instance of `kernel` with the template arguments `key`: the table's entry, or DEMC_EUNSUPPORTED (never a null launch).
+template <typename I, size_t N>
+int pick(demc_handle* h, const char* kernel, const I (&tab)[N], const InstKey& key, const I** out) {
+    if ((*out = find_inst(tab, key))) return DEMC_OK;
+    return fail(h, DEMC_EUNSUPPORTED, std::string("no instance ") + kernel + "<" + int_list(key, kMaxKey) + "> in this library");
+}
+#define PICK(out, kernel, tab, ...) \
+    do { if (int rc_ = pick(h, kernel, tab, InstKey{{__VA_ARGS__}}, &(out))) return rc_; } while (0)
+
+// resident 256-thread workgroups of `fn` per CU: asked once, kept in *cached (0: not asked yet)
+int wgs_per_cu(demc_handle* h, const void* fn, int* cached) {
+    if (*cached == 0) {
+        int nb = 0;
+        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 256, 0));
+        *cached = nb > 0 ? nb : 1;
+    }
+    return DEMC_OK;
+}
+
 bool is_mvn(int fam);
 
 int pow2_ceil(int x) {
@@ -350,23 +374,22 @@ KParams base_params(demc_handle* h) {
     return k;
 }
 
-template <int KS>
-void launch_cross(demc_handle* h, const KParams& k, int grid, int k0, int n_chunks, int part0) {
-    LAUNCH_T(h, (k_cross_mfma<KS, 4>), dim3(grid), dim3(256), 0, k, h->Ypad, h->dpad, k0, h->Xf, h->n_tiles, n_chunks, part0);
-}
-
-// Kernarg of the JIT-compiled user-likelihood kernel; the same text is prepended to the user's source.
-struct UserKParams {
-    int n_groups, Np, D, a_lo, n_act, n_chunks, nhyper, with_prior;
-    long long N, P;
-    const double* prop;
-    double* partial;
-    const double* data;
-    const double* hyper;
-    const long long* dims;
-    const int* glist;
-    int ndims, pad;
-};
+// Kernarg of the JIT-compiled user-likelihood kernel: ONE definition, compiled here and -- as text -- prepended to the user's source.
+#define DEMC_USER_KPARAMS                                                   \
+    struct UserKParams {                                                    \
+        int n_groups, Np, D, a_lo, n_act, n_chunks, nhyper, with_prior;     \
+        long long N, P;                                                     \
+        const double* prop;                                                 \
+        double* partial;                                                    \
+        const double* data;                                                 \
+        const double* hyper;                                                \
+        const long long* dims;                                              \
+        const int* glist;                                                   \
+        int ndims, pad;                                                     \
+    };
+DEMC_USER_KPARAMS
+#define DEMC_STR_(...) #__VA_ARGS__
+#define DEMC_STR(...) DEMC_STR_(__VA_ARGS__)
 const char* kUserStruct = R"SRC(
 #ifndef INFINITY
 #define INFINITY __builtin_huge_val()
@@ -374,18 +397,7 @@ const char* kUserStruct = R"SRC(
 #ifndef NAN
 #define NAN __builtin_nan("")
 #endif
-struct UserKParams {
-    int n_groups, Np, D, a_lo, n_act, n_chunks, nhyper, with_prior;
-    long long N, P;
-    const double* prop;
-    double* partial;
-    const double* data;
-    const double* hyper;
-    const long long* dims;
-    const int* glist;
-    int ndims, pad;
-};
-)SRC";
+)SRC" DEMC_STR(DEMC_USER_KPARAMS) "\n";
 const char* kUserPrologue = R"SRC(
 __device__ double demc_user_obs(const double* theta, int D, const double* data, long long N, long long i,
                                 const double* hyper, int nhyper);
@@ -469,7 +481,6 @@ int clock_buffer(demc_handle* h, size_t wgs, unsigned long long** out) {
 const char* kSimKernelSource =
 #include "demc_simlike_src.inc"
     ;
-const char* sim_name(int sim) { return sim == SIM_NORMAL ? "normal" : sim == SIM_BINOMIAL ? "binomial" : "user"; }
 
 // K2 of a simulation-based model: one workgroup per proposal, the simulated sample in LDS (demc_simlike.hpp)
 int launch_sim_loglike(demc_handle* h, KParams& k, long long n_prop) {
@@ -482,7 +493,7 @@ int launch_sim_loglike(demc_handle* h, KParams& k, long long n_prop) {
     s.prop = k.prop; s.partial = k.partial; s.obs = h->data; s.hyper = h->user_hyper ? h->user_hyper + 1 : nullptr;
     s.logtab = h->sim_logtab; s.glist = k.glist;
     const size_t lds = (size_t)h->sim_n * sizeof(double);
-    h->last.k2 = 9;
+    h->last.k2 = demc_handle::K2_SIM; h->last.k2_key = InstKey{{h->sim_kind, h->sim_est}};
     if (h->sim_kind == SIM_USER) {
         size_t sz = sizeof s;
         void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &s, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
@@ -492,12 +503,10 @@ int launch_sim_loglike(demc_handle* h, KParams& k, long long n_prop) {
         if (e != hipSuccess) return fail(h, DEMC_EHIP, std::string("hipModuleLaunchKernel: ") + hipGetErrorString(e));
         return DEMC_OK;
     }
+    const Inst<SimFn>* e = nullptr;
+    PICK(e, "k_sim_loglike", kSim, h->sim_kind, h->sim_est);
     tick(h, 2, true);
-    const dim3 grid((unsigned)n_prop);
-    if (h->sim_kind == SIM_NORMAL && h->sim_est == EST_KDE) LAUNCH_T(h, (k_sim_loglike<SIM_NORMAL, EST_KDE>), grid, dim3(256), lds, s);
-    else if (h->sim_kind == SIM_NORMAL) LAUNCH_T(h, (k_sim_loglike<SIM_NORMAL, EST_FREQ>), grid, dim3(256), lds, s);
-    else if (h->sim_est == EST_KDE) LAUNCH_T(h, (k_sim_loglike<SIM_BINOMIAL, EST_KDE>), grid, dim3(256), lds, s);
-    else LAUNCH_T(h, (k_sim_loglike<SIM_BINOMIAL, EST_FREQ>), grid, dim3(256), lds, s);
+    LAUNCH_T(h, e->fn, dim3((unsigned)n_prop), dim3(256), lds, s);
     tick(h, 2, false);
     return DEMC_OK;
 }
@@ -521,30 +530,22 @@ int launch_loglike(demc_handle* h, KParams& k) {
                 // The kernel is one long uniform loop per workgroup: the launch takes ceil(workgroups / resident workgroups)
                 // rounds of equal length, so the chunk count is chosen to fill the last round (cfg3: 128 blocks x 48 chunks =
                 // 4 full rounds of 1536 resident workgroups; 32 chunks would leave a third of the chip idle in round 3).
-                if (h->direct_wgs_per_cu == 0) {
-                    int nb = 0;
-                    const void* fn = h->dp_direct == 8 ? (const void*)k_direct_mvn<8> : h->dp_direct == 16 ? (const void*)k_direct_mvn<16>
-                                     : h->dp_direct == 32 ? (const void*)k_direct_mvn<32> : (const void*)k_direct_mvn<64>;
-                    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 256, 0));
-                    h->direct_wgs_per_cu = nb > 0 ? nb : 1;
-                }
+                const Inst<ChunkFn>* e = nullptr;
+                PICK(e, "k_direct_mvn", kDirect, h->dp_direct);
+                if (int rc = wgs_per_cu(h, (const void*)e->fn, &h->direct_wgs_per_cu)) return rc;
                 const int n_chunks = chunks_filling_rounds(blocks, cap, (double)h->direct_wgs_per_cu * h->n_cus);
-                h->last.k2 = 5; h->last.ks = h->dp_direct;
+                h->last.k2 = demc_handle::K2_DIRECT_MVN; h->last.k2_key = e->key;
                 // timing on: every workgroup also leaves its shader-clock / reference-clock ticks (demc_timing_clock)
                 unsigned long long* clk = nullptr;
                 if (int rc = clock_buffer(h, (size_t)blocks * (size_t)n_chunks, &clk)) return rc;
                 tick(h, 2, true);
-                const dim3 grid((unsigned)blocks, (unsigned)n_chunks);
-                switch (h->dp_direct) {
-                    case 8: LAUNCH_T(h, k_direct_mvn<8>, grid, dim3(256), 0, k, n_chunks, clk); break;
-                    case 16: LAUNCH_T(h, k_direct_mvn<16>, grid, dim3(256), 0, k, n_chunks, clk); break;
-                    case 32: LAUNCH_T(h, k_direct_mvn<32>, grid, dim3(256), 0, k, n_chunks, clk); break;
-                    default: LAUNCH_T(h, k_direct_mvn<64>, grid, dim3(256), 0, k, n_chunks, clk); break;
-                }
+                LAUNCH_T(h, e->fn, dim3((unsigned)blocks, (unsigned)n_chunks), dim3(256), 0, k, n_chunks, clk);
                 tick(h, 2, false);
                 k.n_partials = n_chunks;
             } else if (!suff) {
-                h->last.k2 = 1; h->last.ks = h->ks_t <= 1 ? 1 : h->ks_t <= 2 ? 2 : h->ks_t <= 4 ? 4 : h->ks_t <= 8 ? 8 : 16;
+                const Inst<CrossFn>* e = nullptr;  // (k-steps per pass: the next instance up, demc_set_model keeps them a power of two <= 16)
+                PICK(e, "k_cross_mfma", kCross, h->ks_t <= 1 ? 1 : h->ks_t <= 2 ? 2 : h->ks_t <= 4 ? 4 : h->ks_t <= 8 ? 8 : 16, 4);
+                h->last.k2 = demc_handle::K2_CROSS_MFMA; h->last.k2_key = e->key;
                 tick(h, 2, true);
                 // particle tiles of 256 (4 waves x MT=4 x 16) x observation chunks; chunks in multiples of 8 so that
                 // blockIdx % 8 (the XCD a block lands on) selects the chunk it streams
@@ -557,13 +558,8 @@ int launch_loglike(demc_handle* h, KParams& k) {
                 if (n_chunks < 1) return fail(h, DEMC_EINVAL, "data dimension too large for the partial-sum workspace");
                 const int grid2 = (int)(n_ptiles * n_chunks);
                 for (int kp = 0; kp < n_kpass; ++kp) {
-                    const int ks_here = h->ks_t;
                     const int k0 = kp * 4 * h->ks_t, part0 = kp * n_chunks;
-                    if (ks_here <= 1) launch_cross<1>(h, k, grid2, k0, n_chunks, part0);
-                    else if (ks_here <= 2) launch_cross<2>(h, k, grid2, k0, n_chunks, part0);
-                    else if (ks_here <= 4) launch_cross<4>(h, k, grid2, k0, n_chunks, part0);
-                    else if (ks_here <= 8) launch_cross<8>(h, k, grid2, k0, n_chunks, part0);
-                    else launch_cross<16>(h, k, grid2, k0, n_chunks, part0);
+                    LAUNCH_T(h, e->fn, dim3(grid2), dim3(256), 0, k, h->Ypad, h->dpad, k0, h->Xf, h->n_tiles, n_chunks, part0);
                 }
                 tick(h, 2, false);
                 k.n_partials = n_chunks * n_kpass;
@@ -577,36 +573,28 @@ int launch_loglike(demc_handle* h, KParams& k) {
             long long cap = h->N / 32;
             if (cap > h->partial_cap) cap = h->partial_cap;
             if (cap < 1 || h->family == FAM_RASTRIGIN) cap = 1;
-            if (h->obs_wgs_per_cu == 0) {
-                int nb = 0;
-                HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)k_obs_loglike, 256, 0));
-                h->obs_wgs_per_cu = nb > 0 ? nb : 1;
-            }
+            if (int rc = wgs_per_cu(h, (const void*)k_obs_loglike, &h->obs_wgs_per_cu)) return rc;
             int n_chunks = chunks_filling_rounds((n_prop + 255) / 256, cap, (double)h->obs_wgs_per_cu * h->n_cus);
             if (h->family == FAM_LBA) {
                 // a wave per proposal, lanes across the (sorted) trials: k_lba_wave.  Chunks of whole batches (512 trials), at least two a chunk.
-                if (h->lba_wave_wgs_per_cu == 0) {
-                    int nb = 0;
-                    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)k_lba_wave<3>, 256, 0));
-                    h->lba_wave_wgs_per_cu = nb > 0 ? nb : 1;
-                }
+                const Inst<ChunkFn>*e = nullptr, *e3 = nullptr;
+                PICK(e, "k_lba_wave", kLbaWave, h->n_acc == 3 ? 3 : h->n_acc == 2 ? 2 : 0);
+                PICK(e3, "k_lba_wave", kLbaWave, 3);  // (the occupancy that sizes the chunks is the three-accumulator instance's, whichever runs)
+                if (int rc = wgs_per_cu(h, (const void*)e3->fn, &h->lba_wave_wgs_per_cu)) return rc;
                 long long capw = h->N / 1024;
                 if (capw > h->partial_cap) capw = h->partial_cap;
                 if (capw < 1) capw = 1;
                 int nc = chunks_filling_rounds((n_prop + 3) / 4, capw, (double)h->lba_wave_wgs_per_cu * h->n_cus);
-                h->last.k2 = 8;
+                h->last.k2 = demc_handle::K2_LBA_WAVE;
                 unsigned long long* clk = nullptr;  // timing on: the clock the vector pipe held (demc_timing_clock)
                 if (int rc = clock_buffer(h, (size_t)((n_prop + 3) / 4) * (size_t)nc, &clk)) return rc;
                 tick(h, 2, true);
-                const dim3 grid((unsigned)((n_prop + 3) / 4), (unsigned)nc);
-                if (h->n_acc == 3) LAUNCH_T(h, k_lba_wave<3>, grid, dim3(256), 0, k, nc, clk);
-                else if (h->n_acc == 2) LAUNCH_T(h, k_lba_wave<2>, grid, dim3(256), 0, k, nc, clk);
-                else LAUNCH_T(h, k_lba_wave<0>, grid, dim3(256), 0, k, nc, clk);
+                LAUNCH_T(h, e->fn, dim3((unsigned)((n_prop + 3) / 4), (unsigned)nc), dim3(256), 0, k, nc, clk);
                 tick(h, 2, false);
                 k.n_partials = nc;
                 break;
             }
-            h->last.k2 = 2;
+            h->last.k2 = demc_handle::K2_OBS;
             tick(h, 2, true);
             LAUNCH_T(h, k_obs_loglike, dim3((unsigned)((n_prop + 255) / 256), (unsigned)n_chunks), dim3(256), 0,
                                k, n_chunks);
@@ -627,7 +615,7 @@ int launch_loglike(demc_handle* h, KParams& k) {
             u.data = h->data; u.hyper = h->user_hyper; u.dims = h->user_dims; u.glist = k.glist; u.ndims = h->user_ndims; u.pad = 0;
             size_t sz = sizeof u;
             void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &u, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
-            h->last.k2 = h->user_row ? 6 : 4;
+            h->last.k2 = h->user_row ? demc_handle::K2_USER_ROW : demc_handle::K2_USER;
             tick(h, 2, true, true);
             hipError_t e = h->user_row
                 ? hipModuleLaunchKernel(h->user_kernel, (unsigned)n_prop, 1, 1, 256, 1, 1, 0, h->stream, nullptr, cfg)
@@ -643,7 +631,7 @@ int launch_loglike(demc_handle* h, KParams& k) {
         } break;
         case FAM_HIER_BINOMIAL:
         case FAM_HIER_GAUSSIAN: {
-            h->last.k2 = 3;
+            h->last.k2 = demc_handle::K2_HIER;
             tick(h, 2, true);
             LAUNCH_T(h, k_hier_loglike, dim3((unsigned)n_prop), dim3(256), 0, k);
             tick(h, 2, false);
@@ -656,23 +644,6 @@ int launch_loglike(demc_handle* h, KParams& k) {
 }
 
 bool is_mvn(int fam) { return fam == FAM_MVN_FULL || fam == FAM_MVN_ISO; }
-
-// the K1 instance for (tile in LDS?, fused tail)
-using K1Fn = void (*)(KParams);
-// `lean`: 0 the general instance, 1 the default sampler only, 2 the default sampler + snooker (k_propose's LEAN)
-K1Fn k1_instance(bool tile, int tail, int lean, int wg = 256) {
-#define K1_ROW(WG_, TILE, RES_, LEAN_)                                                                              \
-    {k_propose<WG_, TILE, TAIL_NONE, RES_, LEAN_>, k_propose<WG_, TILE, TAIL_PREP, RES_, LEAN_>,                   \
-     k_propose<WG_, TILE, TAIL_PREP_MFMA, RES_, LEAN_>, k_propose<WG_, TILE, TAIL_OBS, RES_, LEAN_>}
-    static const K1Fn tab[7][4] = {K1_ROW(256, false, false, 0), K1_ROW(256, true, false, 0), K1_ROW(256, true, false, 1),
-                                   K1_ROW(512, false, false, 0), K1_ROW(256, true, false, 2), K1_ROW(256, false, false, 1),
-                                   K1_ROW(256, false, false, 2)};
-#undef K1_ROW
-    if (wg == 512) return tab[3][tail];  // a 512-thread workgroup per particle (very long rows, no tile)
-    // without a tile: the general instance, or the default sampler (+ snooker / block updates) with partners from the history
-    // (DE-MC_Z: lean_hist)
-    return tab[tile ? (lean == 1 ? 2 : lean == 2 ? 4 : 1) : (lean == 1 ? 5 : lean == 2 ? 6 : 0)][tail];
-}
 
 // which tail K1 carries for this model, mode and schedule
 void set_tail_flags(demc_handle* h, KParams& k) {
@@ -830,13 +801,11 @@ int launch_phase(demc_handle* h, KParams k) {
                 k.snap_theta = h->snap2; k.snap_weight = h->snap2_w;
                 h->snap2_iter = (int64_t)k.iter; h->snap2_sweep = (int)k.sweep + 1;
             }
-            h->last = demc_handle::LastPlan();
-            h->last.k1 = 5; h->last.wg = 256; h->last.big = big;
+            const K1Inst* e = nullptr;
+            PICK(e, "k_frozen_sweep", kFrozen, 256, 3, 2, big);
+            h->last = demc_handle::LastPlan{e};
             tick(h, 0, true);
-            if (big)
-                LAUNCH_T(h, (k_frozen_sweep<256, 3, 2, true>), dim3((unsigned)n_prop), dim3(256), 0, k);
-            else
-                LAUNCH_T(h, k_frozen_sweep<256>, dim3((unsigned)n_prop), dim3(256), 0, k);
+            LAUNCH_T(h, e->fn, dim3((unsigned)n_prop), dim3(256), 0, k);
             tick(h, 0, false);
             return DEMC_OK;
         }
@@ -849,14 +818,17 @@ int launch_phase(demc_handle* h, KParams k) {
         // step, one's prologue and row moves under the other's pass -- when two rows fit in the CU's LDS.
         if (h->lr_two_lds != lr_lds) {  // (asked once per row size)
             int nb = 0;
-            HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)k_longrow<256>, 256, lr_lds));
+            const K1Inst* e256 = nullptr;
+            PICK(e256, "k_longrow", kLongrow, 256);
+            HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)e256->fn, 256, lr_lds));
             h->lr_two_lds = lr_lds;
             h->lr_two_fit = nb >= 2;
         }
         const bool two_per_cu = (long long)h->geo_groups * k.n_act >= 2LL * h->n_cus && h->lr_two_fit;
         const int wg_lr = two_per_cu ? 256 : 512;
-        h->last = demc_handle::LastPlan();
-        h->last.k1 = 1; h->last.wg = wg_lr;
+        const K1Inst* e = nullptr;
+        PICK(e, "k_longrow", kLongrow, wg_lr);
+        h->last = demc_handle::LastPlan{e};
         tick(h, 0, true);
         // persistent: as many workgroups as are resident at once, each takes particles blockIdx.x, + gridDim.x, ... (the
         // row moves of one particle then run inside the span loops of the next: demc_longrow.hpp).  A multiple of 8 keeps
@@ -864,25 +836,24 @@ int launch_phase(demc_handle* h, KParams k) {
         long long grid_lr = (long long)(wg_lr == 512 ? 1 : 2) * h->n_cus;
         if (grid_lr > n_prop || grid_lr < 1) grid_lr = n_prop;
         if ((k.n_groups & 7) == 0 && grid_lr >= 8) grid_lr &= ~7LL;
-        if (wg_lr == 256)
-            LAUNCH_T(h, k_longrow<256>, dim3((unsigned)grid_lr), dim3(256), lr_lds, k);
-        else
-            LAUNCH_T(h, k_longrow<512>, dim3((unsigned)grid_lr), dim3(512), lr_lds, k);
+        LAUNCH_T(h, e->fn, dim3((unsigned)grid_lr), dim3(wg_lr), lr_lds, k);
         tick(h, 0, false);
         return DEMC_OK;
     }
-    tick(h, 0, true);
-    const int tail = tail_of(k);
     const size_t lds = tile ? lds_tile + (k.plan ? plan_bytes : 0) : h->k1_lds - h->k1_tile_bytes;
+    // LEAN: the general instance (0), the default sampler (1), + snooker / block updates (2) -- without a tile for partners from the
+    // history (DE-MC_Z: lean_hist); a 512-thread workgroup per particle (very long rows, no tile) has the general instance only
     const int lean = (tile && wg == 256) ? lean_level(h, k) : (!tile && wg == 256) ? lean_hist(h, k) : 0;
-    h->last = demc_handle::LastPlan();
-    h->last.k1 = 0; h->last.wg = wg; h->last.tile = tile; h->last.tail = tail; h->last.plain = lean;
-    LAUNCH_T(h, k1_instance(tile, tail, lean, wg), dim3(k.n_groups * n_split), dim3(wg), lds, k);
+    const K1Inst* e = nullptr;
+    PICK(e, "k_propose", kPropose, wg, tile, tail_of(k), false, lean);
+    h->last = demc_handle::LastPlan{e};
+    tick(h, 0, true);
+    LAUNCH_T(h, e->fn, dim3(k.n_groups * n_split), dim3(wg), lds, k);
     tick(h, 0, false);
     if (k.fuse_accept) return DEMC_OK;
     int rc = launch_loglike(h, k);
     if (rc != DEMC_OK) return rc;
-    h->last.k3 = 1;
+    h->last.k3 = true;
     tick(h, 3, true);
     LAUNCH_T(h, k_accept_store, dim3((unsigned)((n_prop + ppp3 - 1) / ppp3)), dim3(256), 0, k);
     tick(h, 3, false);
@@ -890,30 +861,21 @@ int launch_phase(demc_handle* h, KParams k) {
 }
 
 // ---- resident form of K1: one workgroup per group, both colour phases of several iterations in one launch ----
-K1Fn k1_resident_instance(int wg, int tail, int lean) {
-#define K1_ROW(WG_, LEAN_)                                                                                      \
-    {k_propose<WG_, true, TAIL_NONE, true, LEAN_>, k_propose<WG_, true, TAIL_PREP, true, LEAN_>,               \
-     k_propose<WG_, true, TAIL_PREP_MFMA, true, LEAN_>, k_propose<WG_, true, TAIL_OBS, true, LEAN_>}
-    static const K1Fn tab[6][4] = {K1_ROW(256, 0), K1_ROW(512, 0), K1_ROW(256, 1), K1_ROW(512, 1), K1_ROW(256, 2), K1_ROW(512, 2)};
-#undef K1_ROW
-    return tab[(wg == 512 ? 1 : 0) + 2 * lean][tail];
-}
-
 // Decides once per model whether the resident form applies and with which geometry (lanes per particle, workgroup size,
 // LDS bytes).  It needs the fused accept tail (the whole update inside K1), the two_colour schedule (a phase writes only
 // rows nobody reads), partners from the current population, and the whole group + its scratch in LDS.
-void plan_resident(demc_handle* h) {
+int plan_resident(demc_handle* h) {
     const demc_config& c = h->c;
     h->res_ok = false;
-    if (c.fuse != 0 || c.schedule != DEMC_SCHED_TWO_COLOUR || c.partner_kind != DEMC_PARTNER_CURRENT || c.Np < 4) return;
+    if (c.fuse != 0 || c.schedule != DEMC_SCHED_TWO_COLOUR || c.partner_kind != DEMC_PARTNER_CURRENT || c.Np < 4) return DEMC_OK;
     int lpp_max = pow2_ceil((c.D + 1) / 2);
-    if (lpp_max > 64) return;
+    if (lpp_max > 64) return DEMC_OK;
     const int n_act = c.Np - c.Np / 2;
     const size_t D = (size_t)c.D, Np = (size_t)c.Np, d = (size_t)h->d;
     const bool mvn = is_mvn(h->family);
     // geometry for a thread budget: lanes per particle so that the moving half fills one pass when possible (never below
     // 4 lanes), workgroup size, LDS bytes; false when the update cannot be fused or the group does not fit
-    int lpp = 0, wg = 0;
+    int lpp = 0, wg = 0, tail = TAIL_NONE;
     size_t bytes = 0, scr_doubles = 0;
     auto geometry = [&](int budget) -> bool {
         lpp = 4;
@@ -925,6 +887,7 @@ void plan_resident(demc_handle* h) {
         k.mode = MODE_STEP;
         set_tail_flags(h, k);
         if (!k.fuse_accept) return false;
+        tail = tail_of(k);
         scr_doubles = (k.fuse_prep || k.fuse_obs) ? (size_t)(wg / lpp) * (D + 2) : 0;
         const size_t doubles =
             Np * D + Np + (Np + (Np + 15) / 16) + ((h->family == FAM_MVN_FULL && h->ainv_lds) ? d * d : 0) + (mvn ? d : 0) + scr_doubles;
@@ -934,8 +897,10 @@ void plan_resident(demc_handle* h) {
     // More groups than CUs: two 256-thread workgroups per CU keep twice as many groups in flight as one of 512 -- when
     // two of them fit in a CU's LDS (measured at 1024 groups x 64: 0.082 -> see DESIGN.md section 6).
     const bool two_per_cu = h->geo_groups > 256 && geometry(256) && bytes <= 75 * 1024;
-    if (!two_per_cu && !geometry(512)) return;
+    if (!two_per_cu && !geometry(512)) return DEMC_OK;
+    for (int lean = 0; lean < 3; ++lean) PICK(h->res_k1[lean], "k_propose", kPropose, wg, true, tail, true, lean);
     h->res_ok = true; h->res_lpp = lpp; h->res_wg = wg; h->res_lds = bytes; h->res_scr_doubles = (int)scr_doubles;
+    return DEMC_OK;
 }
 
 int launch_resident(demc_handle* h, long long iter0, int n_iters) {
@@ -949,17 +914,16 @@ int launch_resident(demc_handle* h, long long iter0, int n_iters) {
     k.n_split = 1; k.exclude_self = 0; k.own_in_pool = 1; k.tile_rows = c.Np; k.tile_in_lds = 1;
     k.scr_doubles = h->res_scr_doubles;
     k.plan = (k.lpp >= 4) ? 1 : 0;
-    h->last = demc_handle::LastPlan();
-    h->last.k1 = 2; h->last.wg = h->res_wg; h->last.tile = 1; h->last.tail = tail_of(k); h->last.plain = lean_level(h, k);
+    const K1Inst* e = h->res_k1[lean_level(h, k)];
+    h->last = demc_handle::LastPlan{e};
     tick(h, 0, true);
-    LAUNCH_T(h, k1_resident_instance(h->res_wg, tail_of(k), lean_level(h, k)), dim3(k.n_groups), dim3(h->res_wg), h->res_lds,
-                       k);
+    LAUNCH_T(h, e->fn, dim3(k.n_groups), dim3(h->res_wg), h->res_lds, k);
     tick(h, 0, false);
     return DEMC_OK;
 }
 
 // ---- lean resident kernel (demc_resmvn.hpp): default sampler, MvNormal full Sigma, D = d <= 32, one pass per phase ----
-void plan_lean(demc_handle* h) {
+int plan_lean(demc_handle* h) {
     const demc_config& c = h->c;
     h->lean_ok = h->lean_stream_ok = h->lean_hist_ok = h->lean_direct_ok = false;
     // The per-observation families under the default sampler (demc_resobs.hpp): Gaussian, Binomial and the LNR with a handful of
@@ -967,6 +931,9 @@ void plan_lean(demc_handle* h) {
     // group, its scratch rows and -- LNR -- the log Phi(-z) table in LDS.  Whether the SAMPLER is the default one is asked per step
     // (is_plain: a replay or a trace takes the general kernel).
     h->lean_obs_ok = false;
+    h->lean_k1 = h->lean_obs_k1 = nullptr;
+    // instances with the row length folded in (cfg3: 32, cfg2: 8) when the prior table is one segment
+    const int dt = (h->n_seg == 1 && (c.D == 32 || c.D == 8)) ? c.D : 0;
     if ((h->family == FAM_GAUSSIAN || h->family == FAM_BINOMIAL || h->family == FAM_LNR) && c.D <= 16 && c.fuse == 0 &&
         c.schedule == DEMC_SCHED_TWO_COLOUR && c.partner_kind == DEMC_PARTNER_CURRENT && c.Np >= 4 && c.Np <= 512 && h->n_seg >= 1 &&
         h->N / 16 <= 512) {
@@ -974,7 +941,10 @@ void plan_lean(demc_handle* h) {
         for (const DimTab& t : h->h_tab) ref = ref || t.kind == PR_NORMAL_REF;
         const size_t doubles = (size_t)c.Np * c.D + (size_t)c.Np + (size_t)(c.Np - c.Np / 2) + (size_t)(256 / 16) * c.D +
                                (h->family == FAM_LNR ? (size_t)kLogPhiRows * kLogPhiRow : 0);
-        if (!ref && doubles * sizeof(double) <= kMaxDynLds) { h->lean_obs_ok = true; h->lean_obs_lds = doubles * sizeof(double); }
+        if (!ref && doubles * sizeof(double) <= kMaxDynLds) {
+            PICK(h->lean_obs_k1, "k_res_obs", kResObs, 256);
+            h->lean_obs_ok = true; h->lean_obs_lds = doubles * sizeof(double);
+        }
     }
     // DE-MC_Z (history partners, the synchronous schedule) on the same family in SUFFSTAT mode: the lean body with partner rows
     // from the history, one launch per iteration (step_body) -- all it needs in LDS are select_base's cumulative weights and the
@@ -994,16 +964,16 @@ void plan_lean(demc_handle* h) {
             // sum_i x~_i [2][32]: demc_resmvn.hpp, pend_l / iso_l
             h->lean_hist_lds = ((size_t)c.Np + 16 + (size_t)(wgh / 4) * ((size_t)c.D + 2) + 16 * 64 + 2 + (size_t)wgh * 8 + 64) * sizeof(double);
         }
-        return;
+        return DEMC_OK;
     }
     if (h->family != FAM_MVN_FULL || c.D != h->d || h->d > 32 || c.fuse != 0 || c.schedule != DEMC_SCHED_TWO_COLOUR ||
         c.partner_kind != DEMC_PARTNER_CURRENT || c.Np < 4)
-        return;
-    if (h->n_seg < 1) return;  // (the prior table must fit its run-length form)
+        return DEMC_OK;
+    if (h->n_seg < 1) return DEMC_OK;  // (the prior table must fit its run-length form)
     for (const DimTab& t : h->h_tab)
-        if (t.kind == PR_NORMAL_REF) return;  // (hierarchical scale priors: the general kernel)
+        if (t.kind == PR_NORMAL_REF) return DEMC_OK;  // (hierarchical scale priors: the general kernel)
     const int nact_max = c.Np - c.Np / 2;
-    if (nact_max * 4 > 512) return;
+    if (nact_max * 4 > 512) return DEMC_OK;
     // (DIRECT at D = 8: 512 threads whatever the group's size -- two waves per SIMD for the residual loop, which one wave per SIMD runs
     // at half the vector pipe's rate: nothing else hides its LDS reads and dependent FP64 pairs)
     const bool dir8 = c.loglike_mode == DEMC_LOGLIKE_DIRECT && c.D == 8 && nact_max * 4 <= 256;
@@ -1011,25 +981,28 @@ void plan_lean(demc_handle* h) {
     const size_t D = (size_t)c.D, Np = (size_t)c.Np;
     const size_t base = (Np * D + Np + (size_t)nact_max + 16 + (size_t)(wg / 4) * (D + 2)) * sizeof(double);
     if (c.loglike_mode == DEMC_LOGLIKE_SUFFSTAT) {
-        if (base > kMaxDynLds || !h->res_ok) return;
+        if (base > kMaxDynLds || !h->res_ok) return DEMC_OK;
+        PICK(h->lean_k1, "k_res_mvn", kResMvn, wg, false, dt, 0, 1);
         h->lean_ok = true; h->lean_wg = wg; h->lean_lds = base;
-        return;
+        return DEMC_OK;
     }
     // STREAMING: only where the streaming-resident form applies (plan_stream: small populations), and only with one wave per
     // SIMD (256 threads: what the observation stage needs beyond 256 VGPRs then lives in AGPRs, not scratch)
     const bool dir = c.loglike_mode == DEMC_LOGLIKE_DIRECT;
-    if (!(dir ? h->st_dir_geo : h->st_ok) || (wg != 256 && !dir8)) return;
+    if (!(dir ? h->st_dir_geo : h->st_ok) || (wg != 256 && !dir8)) return DEMC_OK;
     // (DIRECT: the instances with the row length compiled in, the chunk of whitened rows in LDS, MvNormal-full)
-    if (dir && !(h->family == FAM_MVN_FULL && h->n_seg == 1 && (c.D == 8 || c.D == 32) && h->dp_direct == c.D && h->dpad == c.D && h->st_x_lds)) return;
+    if (dir && !(h->family == FAM_MVN_FULL && h->n_seg == 1 && (c.D == 8 || c.D == 32) && h->dp_direct == c.D && h->dpad == c.D && h->st_x_lds)) return DEMC_OK;
     size_t bytes = base + ((size_t)(wg / 4) * h->dpad + (size_t)(dir ? wg / 16 : wg / 64) * nact_max) * sizeof(double) + 16;  // (DIRECT: a partial sum per 16-lane row)
-    if (bytes > kMaxDynLds) return;
+    if (bytes > kMaxDynLds) return DEMC_OK;
     const size_t xbytes = (size_t)(h->st_chunk_tiles + 1) * (h->dpad / 4) * 64 * sizeof(double);
     // (the X chunk rides in LDS exactly when plan_stream found room for it; this kernel's other buffers are no larger)
     if (h->st_x_lds) {
-        if (bytes + xbytes > kMaxDynLds) return;
+        if (bytes + xbytes > kMaxDynLds) return DEMC_OK;
         bytes += xbytes;
     }
+    PICK(h->lean_k1, "k_res_mvn", kResMvn, wg, true, dt, 0, 1, false, dir);  // (DIRECT: <512, 8> and <256, 32>, what the tests above leave)
     h->lean_stream_ok = !dir; h->lean_direct_ok = dir; h->lean_wg = wg; h->lean_stream_lds = bytes;
+    return DEMC_OK;
 }
 
 int launch_lean(demc_handle* h, long long iter0, int n_iters, bool stream) {
@@ -1048,17 +1021,8 @@ int launch_lean(demc_handle* h, long long iter0, int n_iters, bool stream) {
     tick(h, 0, true);
     const unsigned grid = (unsigned)(k.n_groups * (stream ? h->st_C : 1));
     const size_t lds = stream ? h->lean_stream_lds : h->lean_lds;
-    // instances with the row length folded in (cfg3: 32, cfg2: 8) when the prior table is one segment
-    const int dt = (h->n_seg == 1 && (c.D == 32 || c.D == 8)) ? c.D : 0;
-    h->last = demc_handle::LastPlan();
-    h->last.k1 = 4; h->last.wg = h->lean_wg; h->last.stream = stream; h->last.dt = dt;
-    h->last.big = stream && h->lean_direct_ok;  // (the DIRECT instance: named below)
-    void (*fn)(KParams) = nullptr;
-    if (stream && h->lean_direct_ok) fn = dt == 8 ? k_res_mvn<512, true, 8, 0, 1, false, true> : k_res_mvn<256, true, 32, 0, 1, false, true>;
-    else if (stream) fn = dt == 8 ? k_res_mvn<256, true, 8> : dt == 32 ? k_res_mvn<256, true, 32> : k_res_mvn<256, true, 0>;
-    else if (h->lean_wg == 512) fn = dt == 8 ? k_res_mvn<512, false, 8> : dt == 32 ? k_res_mvn<512, false, 32> : k_res_mvn<512, false, 0>;
-    else fn = dt == 8 ? k_res_mvn<256, false, 8> : dt == 32 ? k_res_mvn<256, false, 32> : k_res_mvn<256, false, 0>;
-    LAUNCH_T(h, fn, dim3(grid), dim3(h->lean_wg), lds, k);
+    h->last = demc_handle::LastPlan{h->lean_k1};  // (plan_lean's choice: SUFFSTAT, STREAMING or DIRECT, the row length folded in)
+    LAUNCH_T(h, h->lean_k1->fn, dim3(grid), dim3(h->lean_wg), lds, k);
     tick(h, 0, false);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(h, DEMC_EHIP, std::string("lean resident launch: ") + hipGetErrorString(e));
@@ -1070,10 +1034,9 @@ int launch_lean_obs(demc_handle* h, long long iter0, int n_iters) {
     const demc_config& c = h->c;
     KParams k = base_params(h);
     k.iter = iter0; k.n_iters = n_iters; k.n_rows = h->hist ? c.n_rows : 0;
-    h->last = demc_handle::LastPlan();
-    h->last.k1 = 6; h->last.wg = 256;
+    h->last = demc_handle::LastPlan{h->lean_obs_k1};
     tick(h, 0, true);
-    LAUNCH_T(h, k_res_obs<256>, dim3((unsigned)k.n_groups), dim3(256), h->lean_obs_lds, k);
+    LAUNCH_T(h, h->lean_obs_k1->fn, dim3((unsigned)k.n_groups), dim3(256), h->lean_obs_lds, k);
     tick(h, 0, false);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(h, DEMC_EHIP, std::string("lean per-observation launch: ") + hipGetErrorString(e));
@@ -1087,60 +1050,34 @@ int launch_lean_hist(demc_handle* h, long long iter, bool snooker) {
     k.iter = iter; k.n_iters = 1; k.n_rows = h->hist ? c.n_rows : 0;
     k.sx = h->sx;
     k.Ainv = h->Ainv;
-    tick(h, 0, true);
     const bool iso = h->family == FAM_MVN_ISO;
     // (ISO: the row length of the reference's own test -- 30 means and sigma -- has an instance with D compiled in)
     // (... which reads the prior table as [one entry for the 30 means | one for sigma]: any other table takes the general row length)
     const int dt = iso ? ((c.D == 31 && h->n_seg == 2 && h->seg_start[1] == 30) ? 31 : 0) : (h->n_seg == 1 && (c.D == 32 || c.D == 8)) ? c.D : 0;
-    h->last = demc_handle::LastPlan();
     const bool base = iter <= c.burnin;  // random_gamma reads a base particle (crossover.jl:164): the instance that loads its row
-    h->last.k1 = 4; h->last.wg = h->lean_wg; h->last.stream = 0; h->last.dt = dt; h->last.hist = snooker ? 3 : base ? 2 : 1;
-    h->last.iso = iso;
-    void (*fn)(KParams) = nullptr;
-    if (iso) {
-        const int hi = snooker ? 3 : base ? 2 : 1;
-        static void (*const tab[2][2][3])(KParams) = {
-            {{k_res_mvn<256, false, 0, 1, 1, true>, k_res_mvn<256, false, 0, 2, 1, true>, k_res_mvn<256, false, 0, 3, 1, true>},
-             {k_res_mvn<256, false, 31, 1, 1, true>, k_res_mvn<256, false, 31, 2, 1, true>, k_res_mvn<256, false, 31, 3, 1, true>}},
-            {{k_res_mvn<512, false, 0, 1, 1, true>, k_res_mvn<512, false, 0, 2, 1, true>, k_res_mvn<512, false, 0, 3, 1, true>},
-             {k_res_mvn<512, false, 31, 1, 1, true>, k_res_mvn<512, false, 31, 2, 1, true>, k_res_mvn<512, false, 31, 3, 1, true>}}};
-        fn = tab[h->lean_wg == 512 ? 1 : 0][dt == 31 ? 1 : 0][hi - 1];
-    } else if (snooker && h->lean_wg == 512) fn = dt == 8 ? k_res_mvn<512, false, 8, 3> : dt == 32 ? k_res_mvn<512, false, 32, 3> : k_res_mvn<512, false, 0, 3>;
-    else if (snooker) fn = dt == 8 ? k_res_mvn<256, false, 8, 3> : dt == 32 ? k_res_mvn<256, false, 32, 3> : k_res_mvn<256, false, 0, 3>;
-    else if (h->lean_wg == 512 && !base) fn = dt == 8 ? k_res_mvn<512, false, 8, 1> : dt == 32 ? k_res_mvn<512, false, 32, 1> : k_res_mvn<512, false, 0, 1>;
-    else if (h->lean_wg == 512) fn = dt == 8 ? k_res_mvn<512, false, 8, 2> : dt == 32 ? k_res_mvn<512, false, 32, 2> : k_res_mvn<512, false, 0, 2>;
-    else if (!base) fn = dt == 8 ? k_res_mvn<256, false, 8, 1> : dt == 32 ? k_res_mvn<256, false, 32, 1> : k_res_mvn<256, false, 0, 1>;
-    else fn = dt == 8 ? k_res_mvn<256, false, 8, 2> : dt == 32 ? k_res_mvn<256, false, 32, 2> : k_res_mvn<256, false, 0, 2>;
+    const K1Inst* e = nullptr;
+    PICK(e, "k_res_mvn", kResMvn, h->lean_wg, false, dt, snooker ? 3 : base ? 2 : 1, 1, iso);
+    h->last = demc_handle::LastPlan{e};
     // (the HIST instances hold back the first half's stores for ONE iteration's store_row and form the cdf once per launch: the
     // precondition is checked here, and again by the kernel -- its phase loop runs no trip for any other count)
     if (k.n_iters != 1) return fail(h, DEMC_EINVAL, "lean DE-MC_Z kernel: one iteration per launch");
-    LAUNCH_T(h, fn, dim3((unsigned)k.n_groups), dim3(h->lean_wg), h->lean_hist_lds, k);
+    tick(h, 0, true);
+    LAUNCH_T(h, e->fn, dim3((unsigned)k.n_groups), dim3(h->lean_wg), h->lean_hist_lds, k);
     tick(h, 0, false);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(h, DEMC_EHIP, std::string("lean DE-MC_Z launch: ") + hipGetErrorString(e));
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return fail(h, DEMC_EHIP, std::string("lean DE-MC_Z launch: ") + hipGetErrorString(err));
     return DEMC_OK;
 }
 
 // ---- streaming-resident form: resident K1 with the observation stream inside (k_propose<..., STREAM>) ----
 // 256-thread form: one wave per SIMD, i.e. the whole register file (512 per lane, AGPRs included) behind each wave -- what does
 // not fit the 256 architectural VGPRs spills to AGPRs instead of scratch memory; 512 threads when a colour needs the lanes.
-K1Fn k1_stream_instance(int wg, int tail, int lean) {
-    static const K1Fn tab[2][3][2] = {
-        {{k_propose<256, true, TAIL_PREP, true, 0, true>, k_propose<256, true, TAIL_PREP_MFMA, true, 0, true>},
-         {k_propose<256, true, TAIL_PREP, true, 1, true>, k_propose<256, true, TAIL_PREP_MFMA, true, 1, true>},
-         {k_propose<256, true, TAIL_PREP, true, 2, true>, k_propose<256, true, TAIL_PREP_MFMA, true, 2, true>}},
-        {{k_propose<512, true, TAIL_PREP, true, 0, true>, k_propose<512, true, TAIL_PREP_MFMA, true, 0, true>},
-         {k_propose<512, true, TAIL_PREP, true, 1, true>, k_propose<512, true, TAIL_PREP_MFMA, true, 1, true>},
-         {k_propose<512, true, TAIL_PREP, true, 2, true>, k_propose<512, true, TAIL_PREP_MFMA, true, 2, true>}}};
-    return tab[wg == 512 ? 1 : 0][lean][tail == TAIL_PREP_MFMA ? 1 : 0];
-}
-
 // Decides once per model whether the streaming-resident form applies.  It is for populations too small to fill the chip
 // with one K1 -> K2 -> K3 chain per colour phase (launch- and latency-bound): MvNormal family, STREAMING likelihood,
 // two_colour, current-population partners, at most one group per CU, the group and its per-particle scratch in LDS, and a
 // colour phase whose matrix work is in the launch-overhead range.  Large populations keep the per-phase chain, whose
 // k_cross_mfma runs at the matrix peak.
-void plan_stream(demc_handle* h) {
+int plan_stream(demc_handle* h) {
     const demc_config& c = h->c;
     h->st_ok = false;
     h->st_dir_geo = false;
@@ -1150,17 +1087,17 @@ void plan_stream(demc_handle* h) {
     if (!is_mvn(h->family) || (c.loglike_mode != DEMC_LOGLIKE_STREAMING && !direct) || c.fuse != 0 || c.schedule != DEMC_SCHED_TWO_COLOUR ||
         c.partner_kind != DEMC_PARTNER_CURRENT || c.Np < 4 || h->n_cus < 1 || h->geo_groups > h->n_cus || c.n_groups > h->n_cus ||
         h->dpad > 64 || h->n_kpass != 1)
-        return;
+        return DEMC_OK;
     // Whether the form applies and into how many chunks C a group's observation tiles are cut is decided from the groups of
     // the WHOLE population (geometry_groups), not from this shard's: C fixes the summation order of the cross terms, and a
     // shard must make the choices of the unsharded run to reproduce it bit for bit (demc_create_multi, demc.h).
     const int gg = h->geo_groups > c.n_groups ? h->geo_groups : c.n_groups;
     const int nact_max = c.Np - c.Np / 2;
-    if (nact_max > 512) return;
+    if (nact_max > 512) return DEMC_OK;
     const double phase_flop = 2.0 * (double)nact_max * gg * (double)h->N * h->dpad;
-    if (phase_flop / 78.6e12 > 300e-6) return;
+    if (phase_flop / 78.6e12 > 300e-6) return DEMC_OK;
     int lpp_max = pow2_ceil((c.D + 1) / 2);
-    if (lpp_max > 64) return;
+    if (lpp_max > 64) return DEMC_OK;
     int lpp = 4;
     while (lpp * 2 <= lpp_max && nact_max * lpp * 2 <= 512) lpp *= 2;
     if (lpp > lpp_max) lpp = lpp_max;
@@ -1175,20 +1112,28 @@ void plan_stream(demc_handle* h) {
                            (size_t)rows * h->dpad + (size_t)(wg / 64) * nact_max;
     size_t bytes = doubles * sizeof(double) + (size_t)nact_max * (4 * sizeof(double) + 4 * sizeof(int)) +
                    2 * sizeof(unsigned) * (size_t)C * nact_max + 16;
-    if (bytes > kMaxDynLds) return;
+    if (bytes > kMaxDynLds) return DEMC_OK;
     const size_t xbytes = (size_t)(chunk + 1) * (h->dpad / 4) * 64 * sizeof(double);  // + the all-zero tail tile
     const int x_lds = (bytes + xbytes <= kMaxDynLds) ? 1 : 0;
     if (x_lds) bytes += xbytes;
     // hand-over granules [2][n_groups][C][nact_max][2] and the time-out word
     if (h->st_gran) { hipFree(h->st_gran); h->st_gran = nullptr; }
-    if (hipMalloc((void**)&h->st_gran, 2 * (size_t)c.n_groups * C * nact_max * 2 * sizeof(unsigned long long)) != hipSuccess) return;
+    if (hipMalloc((void**)&h->st_gran, 2 * (size_t)c.n_groups * C * nact_max * 2 * sizeof(unsigned long long)) != hipSuccess) return DEMC_OK;
     if (!h->st_err) {
-        if (hipHostMalloc((void**)&h->st_err, sizeof(unsigned), hipHostMallocMapped) != hipSuccess) return;
+        if (hipHostMalloc((void**)&h->st_err, sizeof(unsigned), hipHostMallocMapped) != hipSuccess) return DEMC_OK;
         *h->st_err = 0u;
+    }
+    if (!direct) {  // (k_propose's streaming form has the two tails an MvNormal model can take: PREP_MFMA, else PREP)
+        KParams k = base_params(h);
+        k.lpp = lpp;
+        set_tail_flags(h, k);
+        const int tail = tail_of(k) == TAIL_PREP_MFMA ? TAIL_PREP_MFMA : TAIL_PREP;
+        for (int lean = 0; lean < 3; ++lean) PICK(h->st_k1[lean], "k_propose", kPropose, wg, true, tail, true, lean, true);
     }
     h->st_ok = !direct; h->st_dir_geo = direct;
     h->st_C = C; h->st_nact_max = nact_max; h->st_rows = rows; h->st_x_lds = x_lds; h->st_chunk_tiles = chunk;
     h->st_lpp = lpp; h->st_scr_doubles = (int)scr_doubles; h->st_lds = bytes; h->st_wg = wg;
+    return DEMC_OK;
 }
 
 int launch_stream(demc_handle* h, long long iter0, int n_iters) {
@@ -1213,13 +1158,12 @@ int launch_stream(demc_handle* h, long long iter0, int n_iters) {
     // grid is sized for that by construction -- at most one workgroup per CU (plan_stream: n_groups * C <= CUs, and each
     // takes most of a CU's LDS) -- so a plain launch has the same residency as a cooperative one, without its launch-time
     // cost (+15-19 us, MI355X_MICROARCH.md "coop-launch"); every spin in the kernel is bounded regardless.
-    h->last = demc_handle::LastPlan();
-    h->last.k1 = 3; h->last.wg = h->st_wg; h->last.tile = 1; h->last.tail = tail_of(k); h->last.plain = lean_level(h, k); h->last.stream = 1;
-    LAUNCH_T(h, k1_stream_instance(h->st_wg, tail_of(k), lean_level(h, k)), dim3(c.n_groups * h->st_C), dim3(h->st_wg), h->st_lds,
-                       k);
-    const hipError_t e = hipGetLastError();
+    const K1Inst* e = h->st_k1[lean_level(h, k)];
+    h->last = demc_handle::LastPlan{e};
+    LAUNCH_T(h, e->fn, dim3(c.n_groups * h->st_C), dim3(h->st_wg), h->st_lds, k);
+    const hipError_t err = hipGetLastError();
     tick(h, 0, false);
-    if (e != hipSuccess) return fail(h, DEMC_EHIP, std::string("streaming-resident launch: ") + hipGetErrorString(e));
+    if (err != hipSuccess) return fail(h, DEMC_EHIP, std::string("streaming-resident launch: ") + hipGetErrorString(err));
     return DEMC_OK;
 }
 
@@ -1312,6 +1256,13 @@ int plan_snap2(demc_handle* h) {
     return DEMC_OK;
 }
 
+// every instance of a table may ask for the whole dynamic-LDS budget
+template <typename I, size_t N>
+int raise_dyn_lds(demc_handle* h, const I (&tab)[N]) {
+    for (const I& e : tab) HIPCHK(hipFuncSetAttribute((const void*)e.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynLds));
+    return DEMC_OK;
+}
+
 // K1 LDS carve-up (must match k_propose): group tile (if it fits) | Np prefix sums | A^-1 [d][d] | theta' scratch
 int size_k1_lds(demc_handle* h) {
     const demc_config& c = h->c;
@@ -1335,47 +1286,14 @@ int size_k1_lds(demc_handle* h) {
     if (h->k1_lds > kMaxDynLds) return fail(h, DEMC_EINVAL, "K1 LDS budget exceeded (Np too large for this D)");
     // the attribute is per function, not per handle: always raise it to the same ceiling so that handles of different
     // sizes in one process do not lower each other's limit
-    for (int t = 0; t < 2; ++t)
-        for (int tail = 0; tail < 4; ++tail)
-            for (int lean = 0; lean < 3; ++lean) {
-                HIPCHK(hipFuncSetAttribute((const void*)k1_instance(t != 0, tail, lean),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynLds));
-                HIPCHK(hipFuncSetAttribute((const void*)k1_resident_instance(t ? 512 : 256, tail, lean),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynLds));
-                HIPCHK(hipFuncSetAttribute((const void*)k1_instance(false, tail, 0, 512),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynLds));
-            }
-    for (int wgs = 256; wgs <= 512; wgs += 256)
-        for (int tail = 1; tail <= 2; ++tail)
-            for (int lean = 0; lean < 3; ++lean)
-                HIPCHK(hipFuncSetAttribute((const void*)k1_stream_instance(wgs, tail, lean),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynLds));
-    HIPCHK(hipFuncSetAttribute((const void*)k_longrow<512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynLds));
-    HIPCHK(hipFuncSetAttribute((const void*)k_longrow<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynLds));
-    {
-        void (*lean[])(KParams) = {k_res_mvn<256, false, 0>, k_res_mvn<256, false, 8>, k_res_mvn<256, false, 32>,
-                                   k_res_mvn<512, false, 0>, k_res_mvn<512, false, 8>, k_res_mvn<512, false, 32>,
-                                   k_res_mvn<256, true, 0>,  k_res_mvn<256, true, 8>,  k_res_mvn<256, true, 32>,
-                                   k_res_mvn<512, true, 8, 0, 1, false, true>, k_res_mvn<256, true, 32, 0, 1, false, true>,
-                                   k_res_mvn<256, false, 0, 1>, k_res_mvn<256, false, 8, 1>, k_res_mvn<256, false, 32, 1>,
-                                   k_res_mvn<512, false, 0, 1>, k_res_mvn<512, false, 8, 1>, k_res_mvn<512, false, 32, 1>,
-                                   k_res_mvn<256, false, 0, 2>, k_res_mvn<256, false, 8, 2>, k_res_mvn<256, false, 32, 2>,
-                                   k_res_mvn<512, false, 0, 2>, k_res_mvn<512, false, 8, 2>, k_res_mvn<512, false, 32, 2>,
-                                   k_res_mvn<256, false, 0, 3>, k_res_mvn<256, false, 8, 3>, k_res_mvn<256, false, 32, 3>,
-                                   k_res_mvn<512, false, 0, 3>, k_res_mvn<512, false, 8, 3>, k_res_mvn<512, false, 32, 3>,
-                                   k_res_mvn<256, false, 0, 1, 1, true>, k_res_mvn<256, false, 0, 2, 1, true>, k_res_mvn<256, false, 0, 3, 1, true>,
-                                   k_res_mvn<512, false, 0, 1, 1, true>, k_res_mvn<512, false, 0, 2, 1, true>, k_res_mvn<512, false, 0, 3, 1, true>,
-                                   k_res_mvn<256, false, 31, 1, 1, true>, k_res_mvn<256, false, 31, 2, 1, true>, k_res_mvn<256, false, 31, 3, 1, true>,
-                                   k_res_mvn<512, false, 31, 1, 1, true>, k_res_mvn<512, false, 31, 2, 1, true>, k_res_mvn<512, false, 31, 3, 1, true>};
-        for (auto f : lean) HIPCHK(hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynLds));
-        HIPCHK(hipFuncSetAttribute((const void*)k_res_obs<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynLds));
-#define DEMC_X_(...) HIPCHK(hipFuncSetAttribute((const void*)k_sim_loglike<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynLds));
-        DEMC_SIM_INSTANCES(DEMC_X_)
-#undef DEMC_X_
-    }
-    plan_resident(h);
-    plan_stream(h);
-    plan_lean(h);
+    if (int rc = raise_dyn_lds(h, kPropose)) return rc;
+    if (int rc = raise_dyn_lds(h, kLongrow)) return rc;
+    if (int rc = raise_dyn_lds(h, kResMvn)) return rc;
+    if (int rc = raise_dyn_lds(h, kResObs)) return rc;
+    if (int rc = raise_dyn_lds(h, kSim)) return rc;
+    if (int rc = plan_resident(h)) return rc;
+    if (int rc = plan_stream(h)) return rc;
+    if (int rc = plan_lean(h)) return rc;
     HIPCHK(hipFuncSetAttribute((const void*)k_mig_pack, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynLds));
     return plan_snap2(h);
 }
@@ -1986,8 +1904,7 @@ static int upload_dimtab(demc_handle* h) {
     HIPCHK(hipMemcpy(h->dimseg, segs, sizeof segs, hipMemcpyHostToDevice));
     // the lean resident kernel reads the table in its run-length form and knows no Normal(a, theta[ref]) prior: priors and
     // bounds arrive AFTER demc_set_model in every caller, so its plan is taken again whenever the table changes
-    if (h->family >= 0) plan_lean(h);
-    return DEMC_OK;
+    return h->family >= 0 ? plan_lean(h) : DEMC_OK;
 }
 
 int32_t demc_set_priors(demc_handle* h, const int32_t* kind, const double* a, const double* b, const int32_t* ref) {
@@ -3011,40 +2928,18 @@ int32_t demc_last_kernels(demc_handle* h, char* out, int32_t nbytes) {
     return guarded(h, [&]() -> int32_t {
     if (!h || !out || nbytes < 1) return DEMC_EINVAL;
     const demc_handle::LastPlan& L = h->last;
-    static const char* const tails[4] = {"TAIL_NONE", "TAIL_PREP", "TAIL_PREP_MFMA", "TAIL_OBS"};
-    char buf[256];
-    buf[0] = '\0';
-    const char* tf[3] = {"false", "true", "2"};  // (the LEAN level: 0 general, 1 plain, 2 plain + snooker)
-    switch (L.k1) {
-        case 0:
-            std::snprintf(buf, sizeof buf, "k_propose<%d,%s,%s,false,%s>", L.wg, tf[L.tile != 0], tails[L.tail & 3], tf[L.plain]);
-            break;
-        case 1: std::snprintf(buf, sizeof buf, "k_longrow<%d>", L.wg); break;
-        case 5: std::snprintf(buf, sizeof buf, "k_frozen_sweep<%d%s>", L.wg, L.big ? ",big" : ""); break;
-        case 6: std::snprintf(buf, sizeof buf, "k_res_obs<%d>", L.wg); break;
-        case 2:
-            std::snprintf(buf, sizeof buf, "k_propose<%d,true,%s,true,%s>", L.wg, tails[L.tail & 3], tf[L.plain]);
-            break;
-        case 3:
-            std::snprintf(buf, sizeof buf, "k_propose<%d,true,%s,true,%s,true>", L.wg, tails[L.tail & 3], tf[L.plain]);
-            break;
-        case 4:
-            if (L.hist && L.iso) std::snprintf(buf, sizeof buf, "k_res_mvn<%d,%s,%d,%d,iso>", L.wg, tf[L.stream != 0], L.dt, L.hist);
-            else if (L.hist) std::snprintf(buf, sizeof buf, "k_res_mvn<%d,%s,%d,%d>", L.wg, tf[L.stream != 0], L.dt, L.hist);
-            else if (L.big) std::snprintf(buf, sizeof buf, "k_res_mvn<%d,%s,%d,direct>", L.wg, tf[L.stream != 0], L.dt);
-            else std::snprintf(buf, sizeof buf, "k_res_mvn<%d,%s,%d>", L.wg, tf[L.stream != 0], L.dt);
-            break;
-        default: break;
+    std::string s = L.k1 ? L.k1->name(L.k1->key) : "";
+    switch (L.k2) {
+        case demc_handle::K2_NONE: break;
+        case demc_handle::K2_CROSS_MFMA: s += " + " + name_cross(L.k2_key); break;
+        case demc_handle::K2_DIRECT_MVN: s += " + " + name_direct(L.k2_key); break;
+        case demc_handle::K2_OBS: s += " + k_obs_loglike"; break;
+        case demc_handle::K2_LBA_WAVE: s += " + " + name_lba_wave(L.k2_key); break;
+        case demc_handle::K2_HIER: s += " + k_hier_loglike"; break;
+        case demc_handle::K2_USER: s += " + k_user_loglike"; break;
+        case demc_handle::K2_USER_ROW: s += " + k_user_row"; break;
+        case demc_handle::K2_SIM: s += " + " + name_sim(L.k2_key); break;
     }
-    std::string s = buf;
-    if (L.k2 == 1) s += " + k_cross_mfma<" + std::to_string(L.ks) + ",4>";
-    else if (L.k2 == 2) s += " + k_obs_loglike";
-    else if (L.k2 == 8) s += " + k_lba_wave";
-    else if (L.k2 == 3) s += " + k_hier_loglike";
-    else if (L.k2 == 4) s += " + k_user_loglike";
-    else if (L.k2 == 5) s += " + k_direct_mvn<" + std::to_string(L.ks) + ">";
-    else if (L.k2 == 6) s += " + k_user_row";
-    else if (L.k2 == 9) s += std::string(" + k_sim_loglike<") + (h->sim_est == EST_KDE ? "kde" : "frequency") + "," + sim_name(h->sim_kind) + ">";
     if (L.k3) s += " + k_accept_store";
     std::snprintf(out, (size_t)nbytes, "%s", s.c_str());
     return DEMC_OK;

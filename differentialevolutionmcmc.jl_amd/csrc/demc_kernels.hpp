@@ -1924,7 +1924,7 @@ __global__ __launch_bounds__(WG, (WG == 256 && !STREAM) ? 2 : 1) void k_propose(
 }
 
 // ------------------------------------------------------------------------------------------------
-// The k_propose instances the runtime launches (k1_instance / k1_resident_instance / k1_stream_instance in demc_hip.cpp), in three
+// The k_propose instances the runtime launches (it builds its table kPropose from these lists: demc_instances.hpp), in three
 // lists: demc_k1_phase.cpp, demc_k1_res.cpp and demc_k1_stream.cpp instantiate one each -- 64 instances of a kernel whose colour
 // phase is ~10 000 instructions are most of the library's compile time, and `make -j` builds the units side by side --, and
 // demc_hip.cpp declares them extern (DEMC_K1_EXTERN).  <WG, TILE, TAIL, RES, LEAN, STREAM>
@@ -2059,6 +2059,7 @@ __global__ __launch_bounds__(256, 2) void k_cross_mfma(KParams p, const double* 
             if ((lane & 15) == 0 && q < n_prop) p.partial[(size_t)(part0 + chunk) * p.P + slot_of(p, q)] = v;
         }
 }
+#define DEMC_CROSS_INSTANCES(X) X(1, 4) X(2, 4) X(4, 4) X(8, 4) X(16, 4)  // <KS, MT>: the instances the runtime launches
 
 // ------------------------------------------------------------------------------------------------
 // K2 (MvNormal, DIRECT mode): the residual form the reference's loglike implies (test/multivariate_normal_tests.jl:31-33:
@@ -2128,6 +2129,7 @@ __global__ __launch_bounds__(256) void k_direct_mvn(KParams p, int n_chunks, uns
         }
     }
 }
+#define DEMC_DIRECT_INSTANCES(X) X(8) X(16) X(32) X(64)  // <DP>
 
 // ------------------------------------------------------------------------------------------------
 // K2 (scalar-data families): thread-per-proposal streaming likelihoods.  All lanes of a wave visit the same observation,
@@ -2252,6 +2254,7 @@ __global__ __launch_bounds__(256, 2) void k_lba_wave(KParams p, int n_chunks, un
         }
     }
 }
+#define DEMC_LBA_WAVE_INSTANCES(X) X(3) X(2) X(0)  // <NA>: three or two accumulators compiled in, 0: any count
 #endif
 
 // ------------------------------------------------------------------------------------------------

@@ -9,6 +9,7 @@
 #include "demc_longrow.hpp"
 
 namespace demc {
-template __global__ void k_longrow<256>(KParams);
-template __global__ void k_longrow<512>(KParams);
+#define DEMC_X_(...) template __global__ void k_longrow<__VA_ARGS__>(KParams);
+DEMC_LONGROW_INSTANCES(DEMC_X_)
+#undef DEMC_X_
 }  // namespace demc

@@ -1146,9 +1146,11 @@ __global__ __launch_bounds__(WG, (WG / 64 * PER_CU + 3) / 4) void k_longrow(KPar
     }
 }
 
+#define DEMC_LONGROW_INSTANCES(X) X(256) X(512)
 #ifdef DEMC_LONGROW_EXTERN  // the instances live in demc_longrow.cpp (its own translation unit, its own compiler flags)
-extern template __global__ void k_longrow<256>(KParams);
-extern template __global__ void k_longrow<512>(KParams);
+#define DEMC_X_(...) extern template __global__ void k_longrow<__VA_ARGS__>(KParams);
+DEMC_LONGROW_INSTANCES(DEMC_X_)
+#undef DEMC_X_
 #endif
 
 }  // namespace demc

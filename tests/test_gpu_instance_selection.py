@@ -1,0 +1,97 @@
+"""Which kernel instance the runtime picks, by name only: the selector branches that the production and edge-case tests do not
+reach.  Every case builds a tiny engine (2 groups, 64 observations), runs two iterations and compares `last_kernels()` with a
+string written out here, derived by hand from the selection rules of csrc/demc_hip.cpp:
+
+  * workgroup: 256 threads, 512 when the moving half of a group at four lanes a particle needs more, (Np - Np/2) * 4 > 256 --
+    Np = 130 is the smallest such group -- or when a particle takes 512 lanes (D >= 4096);
+  * k_res_mvn's DT: the row length where an instance has it compiled in (8 and 32 with a one-segment prior table; 31 for
+    MvNormal-iso with 30 means), else 0;  its HIST: 2 inside burn-in (a base row is read), 1 past it, 3 with snooker updates;
+  * k_propose's LEAN: 1 for the default sampler, 2 with snooker updates, 0 with a trace (the general instance);  TILE: the group in
+    LDS, never with partners from the history;  TAIL: the MvNormal preparation on the matrix cores for MvNormal-full with d <= 32
+    (TAIL_PREP_MFMA), on the vector pipe for MvNormal-iso (TAIL_PREP), the subject sums of a hierarchical family (TAIL_OBS).
+Nothing numerical is checked: the instances themselves are held to the oracle elsewhere."""
+import numpy as np
+import pytest
+
+from conftest import make_problem, setup_engine
+
+pytestmark = pytest.mark.gpu
+
+
+def names_of(demc, fam, Np, history=False, **cfg):
+    """the names after each of two single-iteration steps (with history partners: iterations 3 and 4 behind two prior rows, and
+    burnin = 3, so that the first lies inside burn-in and the second past it)"""
+    prob = make_problem(fam[0], np.random.default_rng(17), **fam[1])
+    P = 2 * Np
+    if history:
+        cfg = dict(schedule=1, partner_kind=1, n_initial=2, burnin=3, **cfg)
+    eng = demc.HipEngine(n_groups=2, Np=Np, D=prob["D"], n_rows=8, seed=11, alpha=0.0, **cfg)
+    setup_engine(eng, prob)
+    if history:
+        eng.set_history_rows(0, np.stack([prob["init"](P) for _ in range(2)]))
+    eng.set_state(prob["init"](P))
+    first = 3 if history else 1
+    out = []
+    for it in (first, first + 1):
+        eng.step(it, 1)
+        out.append(eng.last_kernels())
+    eng.close()
+    return out
+
+
+def mvn(d):
+    return ("mvn_full", dict(N=64, d=d))
+
+
+def iso(d):
+    return ("mvn_iso", dict(N=64, d=d))
+
+
+@pytest.mark.parametrize("Np,wg", [(8, 256), (130, 512)])
+@pytest.mark.parametrize("d,dt", [(5, 0), (8, 8), (32, 32)])
+def test_lean_suffstat_instance_by_workgroup_and_row_length(demc, Np, wg, d, dt):
+    """the default sampler on MvNormal-full, SUFFSTAT, two_colour: k_res_mvn<WG, false, DT>"""
+    assert names_of(demc, mvn(d), Np, loglike_mode=1) == [f"k_res_mvn<{wg},false,{dt}>"] * 2
+
+
+@pytest.mark.parametrize("Np,wg", [(8, 256), (130, 512)])
+@pytest.mark.parametrize("fam,dt,tag", [(mvn(5), 0, ""), (mvn(8), 8, ""), (mvn(32), 32, ""), (iso(5), 0, ",iso"), (iso(30), 31, ",iso")])
+def test_lean_de_mc_z_instance_by_workgroup_row_length_and_burn_in(demc, Np, wg, fam, dt, tag):
+    """DE-MC_Z (history partners, synchronous) in SUFFSTAT mode: k_res_mvn<WG, false, DT, HIST[, iso]> -- HIST = 2 at iteration 3
+    (burnin = 3), 1 at iteration 4, and 3 at both with snooker updates"""
+    assert names_of(demc, fam, Np, history=True, loglike_mode=1) == [f"k_res_mvn<{wg},false,{dt},2{tag}>", f"k_res_mvn<{wg},false,{dt},1{tag}>"]
+    assert names_of(demc, fam, Np, history=True, loglike_mode=1, theta_snooker=0.1) == [f"k_res_mvn<{wg},false,{dt},3{tag}>"] * 2
+
+
+@pytest.mark.parametrize("Np,wg", [(8, 256), (130, 512)])
+@pytest.mark.parametrize("cfg,lean", [(dict(trace=1), "false"), (dict(), "true"), (dict(theta_snooker=0.1), "2")])
+def test_resident_instance_by_workgroup_and_lean_level(demc, Np, wg, cfg, lean):
+    """the general resident form (MvNormal-iso, SUFFSTAT, two_colour: no lean kernel serves it): k_propose<WG, true, TAIL_PREP,
+    true, LEAN>"""
+    assert names_of(demc, iso(5), Np, loglike_mode=1, **cfg) == [f"k_propose<{wg},true,TAIL_PREP,true,{lean}>"] * 2
+
+
+def test_per_phase_general_instance_with_a_tile(demc):
+    """a trace on the per-phase chain (fuse = 2; STREAMING, d = 5: two k-steps per pass): the general instance over the LDS tile"""
+    chain = "k_propose<256,true,TAIL_PREP_MFMA,false,false> + k_cross_mfma<2,4> + k_accept_store"
+    assert names_of(demc, mvn(5), 8, loglike_mode=0, fuse=2, trace=1) == [chain] * 2
+
+
+def test_per_phase_general_instance_without_a_tile(demc):
+    """history partners with a trace: no tile, the general instance; SUFFSTAT fuses the whole update into K1 past burn-in, inside it
+    (the base row is another workgroup's) the accept kernel follows"""
+    k1 = "k_propose<256,false,TAIL_PREP_MFMA,false,false>"
+    assert names_of(demc, mvn(5), 8, history=True, loglike_mode=1, trace=1) == [k1 + " + k_accept_store", k1]
+
+
+@pytest.mark.parametrize("snooker,lean", [(0.0, "true"), (0.1, "2")])
+def test_per_phase_lean_instances_without_a_tile(demc, snooker, lean):
+    """DE-MC_Z on the STREAMING chain (the lean DE-MC_Z body is SUFFSTAT only): the no-tile lean rows of k_propose, d = 5"""
+    chain = f"k_propose<256,false,TAIL_PREP_MFMA,false,{lean}> + k_cross_mfma<2,4> + k_accept_store"
+    assert names_of(demc, mvn(5), 8, history=True, loglike_mode=0, theta_snooker=snooker) == [chain] * 2
+
+
+def test_per_phase_instance_of_512_threads(demc):
+    """a particle of D = 4096 scalars takes a whole 512-thread workgroup (hierarchical Binomial, 4094 subjects, their terms summed in
+    K1: TAIL_OBS); fuse = 2 keeps the per-phase kernel where the long-row kernel would take over"""
+    assert names_of(demc, ("hier_binomial", dict(S=4094)), 8, fuse=2, trace=1) == ["k_propose<512,false,TAIL_OBS,false,false>"] * 2
