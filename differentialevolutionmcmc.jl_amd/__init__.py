@@ -9,7 +9,7 @@ from ._ffi import DemcError, HipEngine, MultiEngine
 from .chains import Chains
 from .families import (Beta, BinomialLikelihood, Cauchy, Exponential, Flat, Gamma, GaussianLikelihood, LogNormal, HierBinomialLikelihood,
                        HierGaussianLikelihood, LBALikelihood, LNRLikelihood, MvNormalFullLikelihood,
-                       MvNormalIsoLikelihood, Normal, Priors, RastriginObjective, SimBinomial, SimNormal, SimSource,
+                       MvNormalIsoLikelihood, Normal, Priors, RastriginObjective, SimBinomial, SimLNR, SimNormal, SimSource,
                        SimulatedLikelihood, SourceLikelihood, TruncatedCauchy, Uniform)
 from .sampler import get_optimal, optimize, sample
 from .structs import (DE, DEModel, HIPBackend, MCMCThreads, Particle, as_union, compute_posterior, evaluate_fun,

@@ -270,11 +270,15 @@ class HipEngine:
     def set_model_sim(self, simulator, estimator, n_sim, data, hyper=None, source=None):
         """simulation-based likelihood (demc_set_model_sim, include/demc.h): `simulator` / `estimator` are the DEMC_SIM_* /
         DEMC_SIMEST_* codes, data the scalar observations, hyper = [bandwidth, the simulator's own ...], source the HIP text of
-        demc_user_sim for DEMC_SIM_USER"""
+        demc_user_sim for DEMC_SIM_USER.  DEMC_SIMEST_KDE_CHOICE (2): data = [choices..., response times...], n_obs = half its
+        length, source defines demc_user_sim_choice"""
         data = np.ascontiguousarray(np.asarray(data, dtype=np.float64).ravel())
         hyper = None if hyper is None else np.ascontiguousarray(np.asarray(hyper, dtype=np.float64).ravel())
+        if estimator == 2 and data.size % 2:
+            raise ValueError("set_model_sim: the kde_choice estimator reads [choices..., response times...]: an even number of values")
+        n_obs = data.size // 2 if estimator == 2 else data.size
         self._ck(self.L.demc_set_model_sim(self.h, simulator, estimator, n_sim, None if source is None else source.encode(),
-                                           _d(data), data.size, _d(hyper), 0 if hyper is None else hyper.size))
+                                           _d(data), n_obs, _d(hyper), 0 if hyper is None else hyper.size))
 
     def set_priors(self, kind, a, b, ref=None):
         kind = np.ascontiguousarray(kind, dtype=np.int32)

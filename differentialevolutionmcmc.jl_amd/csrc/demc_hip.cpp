@@ -99,6 +99,7 @@ struct demc_handle {
     int user_ndims = 0;
     // simulation-based likelihood (demc_set_model_sim, demc_simlike.hpp); a user simulator's module lives in user_module / user_kernel
     int sim_kind = -1, sim_est = 0, sim_n = 0;
+    int sim_kmax = 0;               // KDE_CHOICE: the largest observed choice
     double sim_bw = 0.0;
     double* sim_logtab = nullptr;   // [n_sim + 1] log(c / n_sim): the frequency estimator's terms
     unsigned sim_entity_base = 0;   // demc_logpost: row r of a call is evaluated at entity r
@@ -491,8 +492,8 @@ int launch_sim_loglike(demc_handle* h, KParams& k, long long n_prop) {
     s.n_obs = h->N; s.iter = k.iter; s.seed = k.seed; s.sweep = k.sweep; s.entity_base = h->sim_entity_base;
     s.bandwidth = h->sim_bw; s.n_pow = std::pow((double)h->sim_n, -0.2);
     s.prop = k.prop; s.partial = k.partial; s.obs = h->data; s.hyper = h->user_hyper ? h->user_hyper + 1 : nullptr;
-    s.logtab = h->sim_logtab; s.glist = k.glist;
-    const size_t lds = (size_t)h->sim_n * sizeof(double);
+    s.logtab = h->sim_logtab; s.glist = k.glist; s.k_max = h->sim_kmax;
+    const size_t lds = h->sim_est == EST_KDE_CHOICE ? sim_choice_lds(h->sim_n) : (size_t)h->sim_n * sizeof(double);
     h->last.k2 = demc_handle::K2_SIM; h->last.k2_key = InstKey{{h->sim_kind, h->sim_est}};
     if (h->sim_kind == SIM_USER) {
         size_t sz = sizeof s;
@@ -1792,24 +1793,33 @@ int32_t demc_set_model_source_row(demc_handle* h, const char* hip_source, const 
 }
 
 // Simulation-based likelihood (demc_simlike.hpp).  hyper[0] = the KDE bandwidth (<= 0 or absent: the rule of thumb), hyper[1..] the
-// simulator's own hyper-parameters.
+// simulator's own hyper-parameters.  DEMC_SIMEST_KDE_CHOICE: data = the n_obs choices, then the n_obs response times.
 int32_t demc_set_model_sim(demc_handle* h, int32_t simulator, int32_t estimator, int64_t n_sim, const char* hip_source,
                            const double* data, int64_t n_obs, const double* hyper, int32_t nhyper) {
     return guarded(h, [&]() -> int32_t {
     if (!h) return DEMC_EINVAL;
     USE_DEVICE(h);
-    if (simulator != DEMC_SIM_NORMAL && simulator != DEMC_SIM_BINOMIAL && simulator != DEMC_SIM_USER)
+    if (simulator != DEMC_SIM_NORMAL && simulator != DEMC_SIM_BINOMIAL && simulator != DEMC_SIM_LNR && simulator != DEMC_SIM_USER)
         return fail(h, DEMC_EINVAL, "demc_set_model_sim: unknown simulator");
-    if (estimator != DEMC_SIMEST_KDE_EPANECHNIKOV && estimator != DEMC_SIMEST_FREQUENCY)
+    if (estimator != DEMC_SIMEST_KDE_EPANECHNIKOV && estimator != DEMC_SIMEST_FREQUENCY && estimator != DEMC_SIMEST_KDE_CHOICE)
         return fail(h, DEMC_EINVAL, "demc_set_model_sim: unknown estimator");
+    const bool pairs = estimator == DEMC_SIMEST_KDE_CHOICE;
+    if (simulator == DEMC_SIM_LNR && !pairs)
+        return fail(h, DEMC_EINVAL, std::string("demc_set_model_sim: DEMC_SIM_LNR simulates (choice, time) pairs and cannot be scored by the scalar estimator ") +
+                                        (estimator == DEMC_SIMEST_FREQUENCY ? "DEMC_SIMEST_FREQUENCY" : "DEMC_SIMEST_KDE_EPANECHNIKOV") + " (use DEMC_SIMEST_KDE_CHOICE)");
+    if (pairs && (simulator == DEMC_SIM_NORMAL || simulator == DEMC_SIM_BINOMIAL))
+        return fail(h, DEMC_EINVAL, std::string("demc_set_model_sim: ") + (simulator == DEMC_SIM_NORMAL ? "DEMC_SIM_NORMAL" : "DEMC_SIM_BINOMIAL") +
+                                        " simulates scalars and cannot be scored by DEMC_SIMEST_KDE_CHOICE (use DEMC_SIM_LNR or a user simulator of pairs)");
     if (n_sim < 2) return fail(h, DEMC_EINVAL, "demc_set_model_sim: n_sim < 2 (a density estimate needs at least two simulated values)");
-    if (n_sim > kSimMaxN)
-        return fail(h, DEMC_EINVAL, "demc_set_model_sim: n_sim = " + std::to_string(n_sim) + " is above the cap of " + std::to_string(kSimMaxN) +
+    const int64_t cap = pairs ? kSimChoiceMaxN : kSimMaxN;
+    static_assert(sim_choice_lds(kSimChoiceMaxN) <= kMaxDynLds && sim_choice_lds(10000) <= kMaxDynLds, "k_sim_choice: the cap does not fit the LDS of a launch");
+    if (n_sim > cap)
+        return fail(h, DEMC_EINVAL, "demc_set_model_sim: n_sim = " + std::to_string(n_sim) + " is above the cap of " + std::to_string(cap) +
                                         " simulated values (the sample of a proposal is held in LDS)");
     if (n_obs < 1 || !data) return fail(h, DEMC_EINVAL, "demc_set_model_sim: n_obs >= 1 observations required");
     if (nhyper < 0 || (nhyper > 0 && !hyper)) return fail(h, DEMC_EINVAL, "demc_set_model_sim: nhyper > 0 without hyper");
     if (simulator == DEMC_SIM_USER && (!hip_source || !hip_source[0]))
-        return fail(h, DEMC_EINVAL, "demc_set_model_sim: DEMC_SIM_USER needs hip_source (a definition of demc_user_sim)");
+        return fail(h, DEMC_EINVAL, "demc_set_model_sim: DEMC_SIM_USER needs hip_source (a definition of demc_user_sim; demc_user_sim_choice under DEMC_SIMEST_KDE_CHOICE)");
     if (simulator != DEMC_SIM_USER && hip_source && hip_source[0])
         return fail(h, DEMC_EINVAL, "demc_set_model_sim: hip_source given with a registered simulator");
     if (simulator == DEMC_SIM_NORMAL && h->c.D != 2) return fail(h, DEMC_EINVAL, "SIM_NORMAL: theta=(mu,sigma)");
@@ -1818,6 +1828,22 @@ int32_t demc_set_model_sim(demc_handle* h, int32_t simulator, int32_t estimator,
         if (nhyper < 2 || !(hyper[1] >= 1.0 && hyper[1] <= 1024.0 && hyper[1] == std::floor(hyper[1])))
             return fail(h, DEMC_EINVAL, "SIM_BINOMIAL: hyper=[bandwidth, n_trials], n_trials an integer in [1, 1024]");
         if (n_sim * (((int64_t)hyper[1] + 3) / 4) > 0x7fffffffLL) return fail(h, DEMC_EINVAL, "SIM_BINOMIAL: too many Philox blocks per proposal");
+    }
+    if (simulator == DEMC_SIM_LNR) {
+        if (h->c.D < 3 || h->c.D > 9) return fail(h, DEMC_EINVAL, "SIM_LNR: theta=(nu[K],tau), K = D - 1 in [2, 8]");
+        if (nhyper < 2 || !(hyper[1] > 0.0)) return fail(h, DEMC_EINVAL, "SIM_LNR: hyper=[bandwidth, sigma], sigma > 0");
+    }
+    int kmax = 0;
+    if (pairs) {  // host_data = the n_obs choices, then the n_obs times
+        const int hi = simulator == DEMC_SIM_LNR ? h->c.D - 1 : 255;
+        for (int64_t j = 0; j < n_obs; ++j) {
+            const double c = data[j];
+            if (!(c >= 1.0 && c <= (double)hi && c == std::floor(c)))
+                return fail(h, DEMC_EINVAL, "demc_set_model_sim: the choice of observation " + std::to_string(j) + " is not an integer in [1, " + std::to_string(hi) + "]");
+            if (!std::isfinite(data[n_obs + j]))
+                return fail(h, DEMC_EINVAL, "demc_set_model_sim: the response time of observation " + std::to_string(j) + " is not finite");
+            kmax = std::max(kmax, (int)c);
+        }
     }
     if (estimator == DEMC_SIMEST_FREQUENCY)
         for (int64_t j = 0; j < n_obs; ++j)
@@ -1856,8 +1882,10 @@ int32_t demc_set_model_sim(demc_handle* h, int32_t simulator, int32_t estimator,
         HIPCHK(hipModuleGetFunction(&h->user_kernel, h->user_module, "k_sim_loglike_user"));
     }
     h->N = n_obs;
-    ALLOC(h->data, (size_t)n_obs);
-    HIPCHK(hipMemcpy(h->data, data, sizeof(double) * (size_t)n_obs, hipMemcpyHostToDevice));
+    const size_t n_data = (size_t)n_obs * (pairs ? 2 : 1);
+    ALLOC(h->data, n_data);
+    HIPCHK(hipMemcpy(h->data, data, sizeof(double) * n_data, hipMemcpyHostToDevice));
+    h->sim_kmax = kmax;
     // hyper as the kernels see it: [bandwidth, the simulator's own ...]
     h->user_nhyper = nhyper > 0 ? nhyper : 1;
     {

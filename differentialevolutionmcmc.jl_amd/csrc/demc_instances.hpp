@@ -62,8 +62,8 @@ inline std::string name_cross(const InstKey& k) { return "k_cross_mfma<" + int_l
 inline std::string name_direct(const InstKey& k) { return "k_direct_mvn<" + int_list(k, 1) + ">"; }
 inline std::string name_lba_wave(const InstKey&) { return "k_lba_wave"; }
 inline std::string name_sim(const InstKey& k) {  // <SIM, EST>; SIM_USER: the instance hiprtc compiled around the caller's simulator
-    return std::string("k_sim_loglike<") + (k.v[1] == EST_KDE ? "kde" : "frequency") + "," +
-           (k.v[0] == SIM_NORMAL ? "normal" : k.v[0] == SIM_BINOMIAL ? "binomial" : "user") + ">";
+    return std::string("k_sim_loglike<") + (k.v[1] == EST_KDE ? "kde" : k.v[1] == EST_FREQ ? "frequency" : "kde_choice") + "," +
+           (k.v[0] == SIM_NORMAL ? "normal" : k.v[0] == SIM_BINOMIAL ? "binomial" : k.v[0] == SIM_LNR ? "lnr" : "user") + ">";
 }
 
 // ---- the tables
@@ -82,6 +82,7 @@ using SimFn = void (*)(SimKParams);
 #define DEMC_E_CROSS(...) DEMC_ENTRY(k_cross_mfma, name_cross, __VA_ARGS__)
 #define DEMC_E_LBA_WAVE(...) DEMC_ENTRY(k_lba_wave, name_lba_wave, __VA_ARGS__)
 #define DEMC_E_SIM(...) DEMC_ENTRY(k_sim_loglike, name_sim, __VA_ARGS__)
+#define DEMC_E_SIM_CHOICE(SIM) {k_sim_choice<SIM>, {{SIM, EST_KDE_CHOICE}}, name_sim},  // (the pair kernel: its estimator is its own)
 constexpr K1Inst kPropose[] = {DEMC_K1_PHASE_INSTANCES(DEMC_E_PROPOSE) DEMC_K1_RES_INSTANCES(DEMC_E_PROPOSE) DEMC_K1_STREAM_INSTANCES(DEMC_E_PROPOSE)};
 constexpr K1Inst kResMvn[] = {DEMC_RESMVN_INSTANCES(DEMC_E_RES_MVN) DEMC_RESMVN_INSTANCES_DIR(DEMC_E_RES_MVN)};
 constexpr K1Inst kFrozen[] = {DEMC_FROZEN_INSTANCES(DEMC_E_FROZEN)};
@@ -90,7 +91,7 @@ constexpr K1Inst kResObs[] = {DEMC_RESOBS_INSTANCES(DEMC_E_RES_OBS)};
 constexpr Inst<ChunkFn> kDirect[] = {DEMC_DIRECT_INSTANCES(DEMC_E_DIRECT)};
 constexpr Inst<CrossFn> kCross[] = {DEMC_CROSS_INSTANCES(DEMC_E_CROSS)};
 constexpr Inst<ChunkFn> kLbaWave[] = {DEMC_LBA_WAVE_INSTANCES(DEMC_E_LBA_WAVE)};
-constexpr Inst<SimFn> kSim[] = {DEMC_SIM_INSTANCES(DEMC_E_SIM)};
+constexpr Inst<SimFn> kSim[] = {DEMC_SIM_INSTANCES(DEMC_E_SIM) DEMC_SIM_CHOICE_INSTANCES(DEMC_E_SIM_CHOICE)};
 static_assert(unique_keys(kPropose) && unique_keys(kResMvn) && unique_keys(kFrozen) && unique_keys(kLongrow) && unique_keys(kResObs) &&
                   unique_keys(kCross) && unique_keys(kDirect) && unique_keys(kLbaWave) && unique_keys(kSim),
               "an instance list names the same template arguments twice");

@@ -12,9 +12,10 @@ FAM_GAUSSIAN, FAM_MVN_ISO, FAM_MVN_FULL, FAM_BINOMIAL, FAM_HIER_BINOMIAL, FAM_HI
     FAM_RASTRIGIN = range(9)
 FAM_USER = 100
 # simulation-based likelihoods (demc_set_model_sim): simulator and estimator codes (include/demc.h)
-SIM_NORMAL, SIM_BINOMIAL, SIM_USER = 0, 1, 100
-SIMEST_KDE_EPANECHNIKOV, SIMEST_FREQUENCY = 0, 1
+SIM_NORMAL, SIM_BINOMIAL, SIM_LNR, SIM_USER = 0, 1, 2, 100
+SIMEST_KDE_EPANECHNIKOV, SIMEST_FREQUENCY, SIMEST_KDE_CHOICE = 0, 1, 2
 SIM_MAX_N = 16384
+SIM_CHOICE_MAX_N = 15000  # the cap of the "kde_choice" estimator: a choice byte beside every simulated time, and the per-choice tables
 PRIOR_FLAT, PRIOR_NORMAL, PRIOR_HALFCAUCHY, PRIOR_UNIFORM, PRIOR_BETA, PRIOR_NORMAL_REF, PRIOR_GAMMA, \
     PRIOR_EXPONENTIAL, PRIOR_LOGNORMAL, PRIOR_CAUCHY = range(10)
 
@@ -234,6 +235,7 @@ class Simulator:
     code = None
     source = None
     n_params = None  # scalars of theta the simulator reads (None: any)
+    pairs = False    # True: a simulated value is a (choice, response time) pair -- the "kde_choice" estimator's simulators
 
     def hyper(self):
         return []
@@ -259,18 +261,40 @@ class SimBinomial(Simulator):
         return [float(self.n)]
 
 
+class SimLNR(Simulator):
+    """The log-normal race of LNRLikelihood as a simulator of (choice, response time) pairs: theta = (nu[K], tau), K in [2, 8];
+    T_k = exp(nu_k + sigma z_k), choice = 1 + argmin_k T_k, rt = tau + min_k T_k.  For the "kde_choice" estimator."""
+    code = SIM_LNR
+    pairs = True
+
+    def __init__(self, sigma=1.0):
+        if not float(sigma) > 0:
+            raise ValueError("SimLNR(sigma): sigma > 0")
+        self.sigma = float(sigma)
+
+    def hyper(self):
+        return [self.sigma]
+
+
 class SimSource(Simulator):
     """A simulator written as a HIP device function, one call per simulated value:
 
         __device__ double demc_user_sim(const double* theta, int D, const double* hyper, int nhyper, demc_sim_rng* rng);
 
-    which draws with demc_sim_uniform(rng) / demc_sim_normal(rng) / demc_sim_u32(rng) (include/demc.h)."""
+    which draws with demc_sim_uniform(rng) / demc_sim_normal(rng) / demc_sim_u32(rng) (include/demc.h).  choice=True: a simulator
+    of (choice, response time) pairs for the "kde_choice" estimator,
+
+        __device__ double demc_user_sim_choice(const double* theta, int D, const double* hyper, int nhyper,
+                                               demc_sim_rng* rng, int* choice);   // returns t, sets *choice in [0, 255]
+
+    (choice 0: no response)."""
     code = SIM_USER
 
-    def __init__(self, source, hyper=None):
+    def __init__(self, source, hyper=None, choice=False):
         if not isinstance(source, str) or not source.strip():
-            raise ValueError("SimSource(source): HIP source defining demc_user_sim")
+            raise ValueError("SimSource(source): HIP source defining demc_user_sim (demc_user_sim_choice with choice=True)")
         self.source = source
+        self.pairs = bool(choice)
         self._hyper = [] if hyper is None else [float(x) for x in np.asarray(hyper, dtype=np.float64).ravel()]
 
     def hyper(self):
@@ -281,23 +305,45 @@ class SimulatedLikelihood(Likelihood):
     """A likelihood without a closed form, estimated per proposal from n_sim simulated values (demc_set_model_sim):
     estimator "kde" = sum(log(max(1e-10, pdf(kde, x)))) with an Epanechnikov kernel (Examples/KDE_Example.jl:10-18; bandwidth
     0.0 = the rule of thumb 0.9 sd n^(-1/5)), "frequency" = log(#{sim == x} / n_sim) summed over the observations
-    (Examples/Binomial_ABC.jl:15-22).  Data: scalar observations (or the reference's (N=..., k=...) with a SimBinomial)."""
+    (Examples/Binomial_ABC.jl:15-22).  Data: scalar observations (or the reference's (N=..., k=...) with a SimBinomial).
+    "kde_choice" = choice and response-time models: the simulator (SimLNR(), SimSource(..., choice=True)) gives (choice, rt) pairs,
+    the data are (choice, rt) as for LBALikelihood / LNRLikelihood, and each observation is scored under the defective
+    Epanechnikov density of its choice, normalised by ALL n_sim values (include/demc.h: DEMC_SIMEST_KDE_CHOICE)."""
     family = None  # not a DEMC_FAM_* family: sampler.configure_engine routes it to set_model_sim
-    ESTIMATORS = {"kde": SIMEST_KDE_EPANECHNIKOV, "frequency": SIMEST_FREQUENCY}
+    ESTIMATORS = {"kde": SIMEST_KDE_EPANECHNIKOV, "frequency": SIMEST_FREQUENCY, "kde_choice": SIMEST_KDE_CHOICE}
 
     def __init__(self, simulator, estimator="kde", n_sim=10_000, bandwidth=0.0):
         if not isinstance(simulator, Simulator) or simulator.code is None:
-            raise TypeError("SimulatedLikelihood(simulator): SimNormal(), SimBinomial(n) or SimSource(source)")
+            raise TypeError("SimulatedLikelihood(simulator): SimNormal(), SimBinomial(n), SimLNR() or SimSource(source)")
         if estimator not in self.ESTIMATORS:
             raise ValueError(f"estimator must be one of {sorted(self.ESTIMATORS)}")
-        if int(n_sim) != n_sim or not 2 <= int(n_sim) <= SIM_MAX_N:
-            raise ValueError(f"n_sim must be an integer in [2, {SIM_MAX_N}] (the sample of a proposal is held in LDS)")
+        if simulator.pairs != (estimator == "kde_choice"):
+            raise ValueError(f"{type(simulator).__name__} simulates {'(choice, rt) pairs' if simulator.pairs else 'scalars'}: "
+                             f"it cannot be scored by the {estimator!r} estimator")
+        cap = SIM_CHOICE_MAX_N if estimator == "kde_choice" else SIM_MAX_N
+        if int(n_sim) != n_sim or not 2 <= int(n_sim) <= cap:
+            raise ValueError(f"n_sim must be an integer in [2, {cap}] (the sample of a proposal is held in LDS)")
         if not np.isfinite(bandwidth) or bandwidth < 0:
             raise ValueError("bandwidth must be finite and >= 0 (0: the rule of thumb)")
         self.simulator, self.estimator, self.n_sim, self.bandwidth = simulator, estimator, int(n_sim), float(bandwidth)
 
     def pack(self, data, shapes):
-        """-> (observations, [N], hyper = [bandwidth, the simulator's own ...])"""
+        """-> (observations, [N], hyper = [bandwidth, the simulator's own ...]); "kde_choice": observations = [choices..., rts...]"""
+        D = int(sum(int(np.prod(s)) if len(s) else 1 for s in shapes))
+        if self.estimator == "kde_choice":
+            c = np.atleast_1d(np.asarray(data[0], dtype=np.float64)).ravel()
+            rt = np.atleast_1d(np.asarray(data[1], dtype=np.float64)).ravel()
+            if c.size < 1 or c.size != rt.size:
+                raise ValueError("SimulatedLikelihood: data = (choice, rt), two arrays of the same length >= 1")
+            lnr = isinstance(self.simulator, SimLNR)
+            if lnr and not 2 <= D - 1 <= 8:
+                raise ValueError(f"SimLNR reads (nu[K], tau) with K in [2, 8], the model has {D} parameters")
+            hi = D - 1 if lnr else 255
+            if not np.all((c == np.floor(c)) & (c >= 1) & (c <= hi)):
+                raise ValueError(f"choices must be integers in [1, {hi}]")
+            if not np.all(np.isfinite(rt)):
+                raise ValueError("response times must be finite")
+            return np.concatenate([c, rt]), [c.size], [self.bandwidth] + list(self.simulator.hyper())
         if isinstance(data, dict) or hasattr(data, "k"):  # the reference's NamedTuple (N = ..., k = ...)
             data = data["k"] if isinstance(data, dict) else data.k
         x = np.atleast_1d(np.asarray(data, dtype=np.float64)).ravel()
@@ -305,7 +351,6 @@ class SimulatedLikelihood(Likelihood):
             raise ValueError("SimulatedLikelihood: no observations")
         if self.estimator == "frequency" and not np.all(x == np.floor(x)):
             raise ValueError("the frequency estimator needs integer-valued data")
-        D = int(sum(int(np.prod(s)) if len(s) else 1 for s in shapes))
         if self.simulator.n_params is not None and D != self.simulator.n_params:
             raise ValueError(f"{type(self.simulator).__name__} reads {self.simulator.n_params} parameters, the model has {D}")
         return x, [x.size], [self.bandwidth] + list(self.simulator.hyper())

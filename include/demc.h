@@ -191,7 +191,7 @@ int32_t demc_set_model_source_row(demc_handle* h, const char* hip_source, const 
  * n_sim simulated values -- probability density approximation (Examples/KDE_Example.jl, with Examples/KDE.jl: 10 000 draws of
  * Normal(mu, sigma), an Epanechnikov kernel density estimate, sum_i log max(1e-10, pdf(kde, x_i))) and approximate Bayesian
  * computation by matching counts (Examples/Binomial_ABC.jl:15-22: 10 000 Binomial(N, theta) counts, log(#{sim == k} / n_sim)).
- * host_data = n_obs scalar observations.  For a proposal row theta evaluated at (iter, sweep, entity):
+ * host_data = n_obs scalar observations (DEMC_SIMEST_KDE_CHOICE: 2 n_obs doubles, see below).  For a proposal row theta evaluated at (iter, sweep, entity):
  *   simulated sample s_0 .. s_{n_sim-1} from the addressed Philox stream 7 (DESIGN.md "Randomness"); entity = the GLOBAL slot
  *   (group_offset + g) Np + p in a step -- shards draw what the single handle draws -- ; demc_set_state (weight == NULL) uses
  *   iter = sweep = 0 and the global slot, demc_logpost iter = sweep = 0 and group_offset Np + the row's index in the call, so
@@ -199,6 +199,11 @@ int32_t demc_set_model_source_row(demc_handle* h, const char* hip_source, const 
  *     DEMC_SIM_NORMAL    theta = (mu, sigma): s_i = mu + sigma z_i, four Box-Muller normals per Philox block
  *     DEMC_SIM_BINOMIAL  theta = p, host_hyper = [bandwidth, n_trials], n_trials <= 1024: count i = successes among the words of
  *                        its ceil(n_trials / 4) blocks, a trial succeeds when its 32-bit uniform is below p
+ *     DEMC_SIM_LNR       PAIRS (choice, response time): the log-normal race of DEMC_FAM_LNR under the same parameter convention,
+ *                        theta = (nu[0 .. K-1], tau), K = D - 1 in [2, 8], host_hyper = [bandwidth, sigma], sigma > 0.  Value i uses
+ *                        the Philox blocks [i B, (i+1) B), B = ceil(K / 4); accumulator k takes normal k of those blocks (per
+ *                        block: box_muller(x, y).{x, y}, box_muller(z, w).{x, y}); T_k = exp(nu_k + sigma z_k),
+ *                        c_i = 1 + argmin_k T_k (ties to the lower k), t_i = tau + min_k T_k.  Only with DEMC_SIMEST_KDE_CHOICE.
  *     DEMC_SIM_USER      hip_source defines
  *         __device__ double demc_user_sim(const double* theta, int D, const double* hyper, int nhyper, demc_sim_rng* rng);
  *                        (hyper = host_hyper + 1, nhyper - 1 entries), called once per simulated value; it draws with
@@ -206,6 +211,11 @@ int32_t demc_set_model_source_row(demc_handle* h, const char* hip_source, const 
  *                        consume the words of the Philox blocks (i << 8) | k, k = 0, 1, ... (mod 256) of value i in order.
  *                        Compiled for gfx950 at this call (hiprtc) into the same kernel text as the registered simulators;
  *                        compile errors come back through demc_last_error.  NULL for a registered simulator.
+ *                        Under DEMC_SIMEST_KDE_CHOICE hip_source defines instead
+ *         __device__ double demc_user_sim_choice(const double* theta, int D, const double* hyper, int nhyper,
+ *                                                demc_sim_rng* rng, int* choice);
+ *                        which returns t_i and sets *choice = c_i in [0, 255] (same generator, same block addressing); a choice
+ *                        outside [0, 255] makes the log-likelihood -Inf.
  *   estimator
  *     DEMC_SIMEST_KDE_EPANECHNIKOV  f(x) = 1/(n h) sum_i 3/4 max(0, 1 - ((x - s_i)/h)^2), loglike = sum_j log max(1e-10, f(x_j)),
  *                        h = host_hyper[0] when nhyper >= 1 and it is > 0, else 0.9 sd n^(-1/5), sd the sample standard deviation
@@ -214,14 +224,30 @@ int32_t demc_set_model_source_row(demc_handle* h, const char* hip_source, const 
  *                        grid and interpolated, and the bandwidth rule leaves out min(sd, IQR / 1.34).
  *     DEMC_SIMEST_FREQUENCY  loglike = sum_j log(#{s_i == x_j} / n); a count of zero gives -Inf (Binomial_ABC.jl:21); the data
  *                        must be integer valued.
+ *     DEMC_SIMEST_KDE_CHOICE  choice and response-time models (probability density approximation, Turner & Sederberg): a simulated
+ *                        value is a pair (c_i, t_i), c_i an integer in [0, 255]; an observation is a pair (c_j, x_j), c_j >= 1.
+ *                        host_data = the n_obs choices, then the n_obs response times (the layout of DEMC_FAM_LBA / DEMC_FAM_LNR);
+ *                        choices must be integers in [1, 255] -- in [1, K] with DEMC_SIM_LNR --, times finite, else DEMC_EINVAL
+ *                        naming the observation.  The per-choice DEFECTIVE density
+ *                          f(c, x) = 1/(n h_c) sum_{i: c_i = c} 3/4 max(0, 1 - ((x - t_i)/h_c)^2),
+ *                        loglike = sum_j log max(1e-10, f(c_j, x_j)): the normaliser is n, all simulated values, not n_c, so
+ *                        f(c, .) integrates to n_c / n.  Choice 0 = "no response": it counts towards n and belongs to no density;
+ *                        its t is ignored.  h_c = host_hyper[0] when > 0 (the same for every choice), else 0.9 sd_c n_c^(-1/5),
+ *                        sd_c the two-pass standard deviation (n_c - 1) of the t_i of choice c, n_c^(-1/5) one pow(n_c, -0.2)
+ *                        per choice in the kernel.  A choice without an estimate -- n_c < 2 or sd_c == 0 under the rule of
+ *                        thumb, n_c == 0 under a fixed bandwidth -- gives each of its observations exactly log(1e-10): the
+ *                        log-likelihood stays finite.  A non-finite t_i with c_i >= 1 makes it -Inf.  n_sim in [2, 15000] here
+ *                        (kSimChoiceMaxN: 9 bytes a value plus the per-choice tables in LDS).  Pairs and scalars do not mix:
+ *                        DEMC_SIM_LNR with a scalar estimator, DEMC_SIM_NORMAL / DEMC_SIM_BINOMIAL with this one: DEMC_EINVAL
+ *                        naming the pair.
  *   A non-finite simulated value makes the log-likelihood -Inf.  n_sim in [2, 16384] (the sample of a proposal is held in LDS;
  *   above it: DEMC_EINVAL, nothing is truncated).  Pseudo-marginal semantics as in the reference: a particle keeps the noisy weight
  *   it was accepted with, nothing is simulated again for a resting particle.  All sums run in a fixed order: same seed, same bits,
  *   whatever the sharding.  Priors and bounds: demc_set_priors / demc_set_bounds, as for every family.  The update always runs
  *   as proposal kernel -> k_sim_loglike<estimator,simulator> -> k_accept_store; demc_last_kernels names the middle one
- *   "k_sim_loglike<kde|frequency,normal|binomial|user>". */
-enum { DEMC_SIM_NORMAL = 0, DEMC_SIM_BINOMIAL = 1, DEMC_SIM_USER = 100 };
-enum { DEMC_SIMEST_KDE_EPANECHNIKOV = 0, DEMC_SIMEST_FREQUENCY = 1 };
+ *   "k_sim_loglike<kde|frequency,normal|binomial|user>", for pairs "k_sim_loglike<kde_choice,lnr|user>". */
+enum { DEMC_SIM_NORMAL = 0, DEMC_SIM_BINOMIAL = 1, DEMC_SIM_LNR = 2, DEMC_SIM_USER = 100 };
+enum { DEMC_SIMEST_KDE_EPANECHNIKOV = 0, DEMC_SIMEST_FREQUENCY = 1, DEMC_SIMEST_KDE_CHOICE = 2 };
 int32_t demc_set_model_sim(demc_handle* h, int32_t simulator, int32_t estimator, int64_t n_sim, const char* hip_source,
                            const double* host_data, int64_t n_obs, const double* host_hyper, int32_t nhyper);
 int32_t demc_set_priors(demc_handle* h, const int32_t* kind, const double* a, const double* b, const int32_t* ref);

@@ -53,6 +53,11 @@ Simulation-based model (include/demc.h, demc_set_model_sim): a simulator instead
 Examples/KDE_Example.jl (`simulator = :normal`, `estimator = :kde`) and Examples/Binomial_ABC.jl (`simulator = :binomial`,
 `estimator = :frequency`, `sim_hyper = [N]`); `simulator = :user` with `source` = HIP text defining `demc_user_sim`.
 `data` are the scalar observations, `bandwidth = 0.0` the rule-of-thumb bandwidth, priors as in `ModelSpec`.
+
+Choice and response-time models: `estimator = :kde_choice` scores (choice, rt) pairs under the per-choice defective density of
+the simulated pairs; `simulator = :lnr` is the log-normal race (`sim_hyper = [sigma]`, theta = (nu[K], tau)), `simulator = :user`
+then reads `source` defining `demc_user_sim_choice`.  `data` = the observed choices (1-based), then the response times -- pass
+`choice` and `rt` instead and the constructor lays them out; the library is told `length(choice)` observations.
 """
 struct SimModelSpec
     simulator::Int32
@@ -66,12 +71,15 @@ struct SimModelSpec
     prior_b::Vector{Float64}
     prior_ref::Vector{Int32}
 end
-const SIMULATORS = Dict(:normal => Int32(0), :binomial => Int32(1), :user => Int32(100))
-const SIM_ESTIMATORS = Dict(:kde => Int32(0), :frequency => Int32(1))
-SimModelSpec(; simulator = :normal, estimator = :kde, n_sim = 10_000, source = "", data, bandwidth = 0.0,
+const SIMULATORS = Dict(:normal => Int32(0), :binomial => Int32(1), :lnr => Int32(2), :user => Int32(100))
+const SIM_ESTIMATORS = Dict(:kde => Int32(0), :frequency => Int32(1), :kde_choice => Int32(2))
+SimModelSpec(; simulator = :normal, estimator = :kde, n_sim = 10_000, source = "", choice = nothing, rt = nothing,
+    data = vcat(collect(Float64, choice), collect(Float64, rt)), bandwidth = 0.0,
     sim_hyper = Float64[], prior_kind, prior_a, prior_b, prior_ref = zeros(Int32, length(prior_kind))) =
     SimModelSpec(SIMULATORS[simulator], SIM_ESTIMATORS[estimator], n_sim, source, collect(Float64, data),
         vcat(Float64(bandwidth), collect(Float64, sim_hyper)), prior_kind, prior_a, prior_b, prior_ref)
+# observations the library is told: the pair layout holds two values (choice, rt) per observation
+n_obs(m::SimModelSpec) = m.estimator == SIM_ESTIMATORS[:kde_choice] ? length(m.data) ÷ 2 : length(m.data)
 const AnyModelSpec = Union{ModelSpec,SimModelSpec}
 
 struct HIPBackend
@@ -170,7 +178,7 @@ set_model!(h, m::ModelSpec) =
         Int32(length(m.dims))::Int32, m.hyper::Ptr{Float64}, Int32(length(m.hyper))::Int32)::Int32)
 set_model!(h, m::SimModelSpec) =
     check(h, @ccall LIB.demc_set_model_sim(h::Ptr{Cvoid}, m.simulator::Int32, m.estimator::Int32, m.n_sim::Int64,
-        (isempty(m.source) ? C_NULL : m.source)::Cstring, m.data::Ptr{Float64}, Int64(length(m.data))::Int64,
+        (isempty(m.source) ? C_NULL : m.source)::Cstring, m.data::Ptr{Float64}, Int64(n_obs(m))::Int64,
         m.hyper::Ptr{Float64}, Int32(length(m.hyper))::Int32)::Int32)
 
 function load_handle!(h, m::AnyModelSpec, de::DE, ps)

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Times the simulation-based likelihood path (demc_set_model_sim, k_sim_loglike) on the GPU, beside the same estimator in numpy on
 the host's threads: the KDE example (Examples/KDE_Example.jl) scaled to 64 groups x 64 particles, N = 50 observations,
-n_sim = 10 000 simulated values per proposal.
+n_sim = 10 000 simulated values per proposal.  `--model lnr`: the pair path instead (k_sim_choice) -- a two-accumulator log-normal
+race under the per-choice defective KDE, N = 50 (choice, response time) observations, the same population and n_sim.
 
-    python3 tools/simlike_bench.py [--steps 50] [--warmup 10] [--repeats 5] [--cpu-rows 64]
+    python3 tools/simlike_bench.py [--model normal|lnr] [--steps 50] [--warmup 10] [--repeats 5] [--cpu-rows 64]
 
 Per repeat: `steps` iterations of demc_step with demc_timing_enable (HIP events in the dispatch packets) after `warmup`
 iterations; prints one JSON object with the median and the spread over the repeats of the wall-clock ms per step, the likelihood
@@ -46,8 +47,24 @@ def numpy_row(theta, x, n, entity, seed):
     return float(np.log(np.maximum(1e-10, 0.75 * np.maximum(0.0, 1.0 - u * u).sum(1) / (n * h))).sum())
 
 
+def numpy_row_lnr(theta, oc, ox, n, entity, seed):
+    """the pair path's CPU side: the race (K = 2: one Philox block a value), per-choice rule-of-thumb bandwidths, the defective densities"""
+    w = [(v.astype(np.float64) + 0.5) / 4294967296.0 for v in philox(np.arange(n), entity, seed)]
+    r0 = np.sqrt(-2.0 * np.log(1.0 - w[0]))
+    T = np.exp(theta[None, :2] + np.stack([r0 * np.cos(2 * np.pi * w[1]), r0 * np.sin(2 * np.pi * w[1])], 1))
+    c, t = np.where(T[:, 1] < T[:, 0], 2, 1), theta[2] + T.min(1)
+    ll = 0.0
+    for k in (1, 2):
+        s, x = t[c == k], ox[oc == k]
+        h = 0.9 * s.std(ddof=1) * s.size ** -0.2
+        u = (x[:, None] - s[None, :]) / h
+        ll += float(np.log(np.maximum(1e-10, 0.75 * np.maximum(0.0, 1.0 - u * u).sum(1) / (n * h))).sum())
+    return ll
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--model", choices=("normal", "lnr"), default="normal")
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--repeats", type=int, default=5)
@@ -63,12 +80,22 @@ def main():
     x = rng.normal(0.0, 1.0, o.n_obs)
     P = o.groups * o.Np
     th0 = np.stack([rng.normal(0, 0.3, P), rng.uniform(0.8, 1.3, P)], 1)
+    lnr = o.model == "lnr"
+    if lnr:
+        T = np.exp(rng.normal([-1.0, -0.7], 1.0, (o.n_obs, 2)))
+        oc, ox = T.argmin(1) + 1, T.min(1) + 0.2
+        th0 = np.stack([rng.normal(-1.0, 0.2, P), rng.normal(-0.7, 0.2, P), rng.uniform(0.05, 0.9, P) * ox.min()], 1)
     n_it = o.warmup + o.repeats * o.steps
-    e = D.HipEngine(n_groups=o.groups, Np=o.Np, D=2, n_rows=n_it, seed=2024, burnin=n_it, schedule=2)
+    e = D.HipEngine(n_groups=o.groups, Np=o.Np, D=3 if lnr else 2, n_rows=n_it, seed=2024, burnin=n_it, schedule=2)
     try:
-        e.set_model_sim(0, 0, o.n_sim, x)
-        e.set_priors([1, 2], [0.0, 0.0], [1.0, 1.0])
-        e.set_bounds([-np.inf, 0.0], [np.inf, np.inf])
+        if lnr:
+            e.set_model_sim(2, 2, o.n_sim, np.concatenate([oc.astype(np.float64), ox]), hyper=[0.0, 1.0])
+            e.set_priors([1, 1, 0], [0.0, 0.0, 0.0], [3.0, 3.0, 1.0])
+            e.set_bounds([-np.inf, -np.inf, 0.0], [np.inf, np.inf, float(ox.min())])
+        else:
+            e.set_model_sim(0, 0, o.n_sim, x)
+            e.set_priors([1, 2], [0.0, 0.0], [1.0, 1.0])
+            e.set_bounds([-np.inf, 0.0], [np.inf, np.inf])
         e.set_state(th0)
         e.step(1, o.warmup)
         e.timing_enable(True)
@@ -91,10 +118,14 @@ def main():
     # the same estimator in numpy, `cpu-rows` proposals over the host's threads (numpy releases the GIL in its loops)
     t0 = time.perf_counter()
     with ThreadPoolExecutor(o.cpu_threads) as pool:
-        list(pool.map(lambda r: numpy_row(th0[r], x, o.n_sim, r, 2024), range(o.cpu_rows)))
+        if lnr:
+            list(pool.map(lambda r: numpy_row_lnr(th0[r], oc, ox, o.n_sim, r, 2024), range(o.cpu_rows)))
+        else:
+            list(pool.map(lambda r: numpy_row(th0[r], x, o.n_sim, r, 2024), range(o.cpu_rows)))
     cpu_ms_per_prop = (time.perf_counter() - t0) * 1e3 / o.cpu_rows
     med = float(np.median(ms))
-    out = dict(workload=f"KDE example, {o.groups} groups x {o.Np} particles, N = {o.n_obs}, n_sim = {o.n_sim}", kernels=kernels,
+    what = "log-normal race (K = 2) under the per-choice KDE" if lnr else "KDE example"
+    out = dict(workload=f"{what}, {o.groups} groups x {o.Np} particles, N = {o.n_obs}, n_sim = {o.n_sim}", kernels=kernels,
                steps=o.steps, warmup=o.warmup, repeats=o.repeats, ms_per_step_median=med, ms_per_step_min=float(min(ms)),
                ms_per_step_max=float(max(ms)), loglike_kernel_ms_per_step_median=float(np.median(ll_ms)),
                loglike_share_of_device_time_median=float(np.median(share)), simulated_values_per_s=P * o.n_sim / (med * 1e-3),
