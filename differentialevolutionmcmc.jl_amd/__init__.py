@@ -8,9 +8,9 @@ from . import _ffi, families
 from ._ffi import DemcError, HipEngine, MultiEngine
 from .chains import Chains
 from .families import (Beta, BinomialLikelihood, Cauchy, Exponential, Flat, Gamma, GaussianLikelihood, LogNormal, HierBinomialLikelihood,
-                       HierGaussianLikelihood, LBALikelihood, LNRLikelihood, MvNormalFullLikelihood,
+                       HierGaussianLikelihood, LBALikelihood, LNRLikelihood, LotkaVolterraLikelihood, MvNormalFullLikelihood,
                        MvNormalIsoLikelihood, Normal, Priors, RastriginObjective, SimBinomial, SimLNR, SimNormal, SimSource,
-                       SimulatedLikelihood, SourceLikelihood, TruncatedCauchy, Uniform)
+                       SimulatedLikelihood, SourceLikelihood, TruncatedCauchy, TruncatedNormal, Uniform)
 from .sampler import get_optimal, optimize, sample
 from .structs import (DE, DEModel, HIPBackend, MCMCThreads, Particle, as_union, compute_posterior, evaluate_fun,
                       fixed_gamma, maximize, mh_update, minimize, project, random_gamma, resample, sample_current,

@@ -37,6 +37,8 @@
 #include "demc_resobs.hpp"
 #define DEMC_SIMLIKE_EXTERN  // k_sim_loglike in demc_simlike.cpp
 #include "demc_simlike.hpp"
+#define DEMC_ODE_EXTERN  // k_ode_loglike in demc_ode.cpp
+#include "demc_ode.hpp"
 #include "demc_instances.hpp"  // one table per templated kernel, built from the lists above: every choice of an instance goes through them
 
 using namespace demc;
@@ -103,6 +105,12 @@ struct demc_handle {
     double sim_bw = 0.0;
     double* sim_logtab = nullptr;   // [n_sim + 1] log(c / n_sim): the frequency estimator's terms
     unsigned sim_entity_base = 0;   // demc_logpost: row r of a call is evaluated at entity r
+    // ODE-trajectory likelihood (DEMC_FAM_ODE_LV, demc_ode.hpp): N = the observation times T, data = Y[T][DIM]
+    int ode_substeps = 0;
+    double ode_u0[4] = {0, 0, 0, 0}, ode_h = 0.0;
+    // DEMC_PRIOR_TRUNCNORMAL: the device's table holds a Normal entry whose constant carries the mass between the bounds; the scale
+    // the caller gave (0: the scalar's prior is not a truncated Normal) is kept here so that the constant follows the bounds
+    std::vector<double> trunc_sd;
     double c0 = 0, c1 = 0, c2 = 0;
     int partial_cap = 64;
     int lpp = 1;
@@ -185,7 +193,7 @@ struct demc_handle {
     struct demc_multi* multi = nullptr;
     bool multi_sealed = false;  // the set is built: demc_set_stream is refused from here on
     // which kernel instances the last update launched (demc_last_kernels: lets a test name the instance it compared)
-    enum K2Kind { K2_NONE, K2_CROSS_MFMA, K2_DIRECT_MVN, K2_OBS, K2_LBA_WAVE, K2_HIER, K2_USER, K2_USER_ROW, K2_SIM };
+    enum K2Kind { K2_NONE, K2_CROSS_MFMA, K2_DIRECT_MVN, K2_OBS, K2_LBA_WAVE, K2_HIER, K2_USER, K2_USER_ROW, K2_SIM, K2_ODE };
     struct LastPlan {
         const K1Inst* k1 = nullptr;  // the entry that was launched (its key names it)
         K2Kind k2 = K2_NONE;         // the likelihood kernel behind it (none: fused into K1) ...
@@ -512,6 +520,25 @@ int launch_sim_loglike(demc_handle* h, KParams& k, long long n_prop) {
     return DEMC_OK;
 }
 
+// K2 of an ODE-trajectory model: one thread per proposal, a grid row of workgroups per launch group (demc_ode.hpp)
+int launch_ode_loglike(demc_handle* h, KParams& k) {
+    OdeKParams o;
+    std::memset(&o, 0, sizeof o);
+    o.n_groups = k.n_groups; o.Np = k.Np; o.D = k.D; o.a_lo = k.a_lo; o.n_act = k.n_act;
+    o.T = (int)h->N; o.substeps = h->ode_substeps;
+    std::memcpy(o.u0, h->ode_u0, sizeof o.u0);
+    o.h = h->ode_h; o.h2 = 0.5 * h->ode_h; o.h6 = h->ode_h / 6.0;
+    o.prop = k.prop; o.partial = k.partial; o.obs = h->data; o.glist = k.glist;
+    const Inst<OdeFn>* e = nullptr;
+    PICK(e, "k_ode_loglike", kOde, ODE_LV);
+    h->last.k2 = demc_handle::K2_ODE; h->last.k2_key = e->key;
+    const size_t lds = (size_t)h->N * 2 * sizeof(double);
+    tick(h, 2, true);
+    LAUNCH_T(h, e->fn, dim3((unsigned)k.n_groups, (unsigned)((k.n_act + 255) / 256)), dim3(256), lds, o);
+    tick(h, 2, false);
+    return DEMC_OK;
+}
+
 // K2 dispatch for the active set described by k.  Sets k.n_partials.
 int launch_loglike(demc_handle* h, KParams& k) {
     const long long n_prop = (long long)k.n_groups * k.n_act;
@@ -628,6 +655,10 @@ int launch_loglike(demc_handle* h, KParams& k) {
         } break;
         case FAM_SIM: {
             if (int rc = launch_sim_loglike(h, k, n_prop)) return rc;
+            k.n_partials = 1;
+        } break;
+        case FAM_ODE_LV: {
+            if (int rc = launch_ode_loglike(h, k)) return rc;
             k.n_partials = 1;
         } break;
         case FAM_HIER_BINOMIAL:
@@ -1292,6 +1323,7 @@ int size_k1_lds(demc_handle* h) {
     if (int rc = raise_dyn_lds(h, kResMvn)) return rc;
     if (int rc = raise_dyn_lds(h, kResObs)) return rc;
     if (int rc = raise_dyn_lds(h, kSim)) return rc;
+    if (int rc = raise_dyn_lds(h, kOde)) return rc;
     if (int rc = plan_resident(h)) return rc;
     if (int rc = plan_stream(h)) return rc;
     if (int rc = plan_lean(h)) return rc;
@@ -1611,6 +1643,26 @@ int32_t demc_set_model(demc_handle* h, int32_t family, const double* data, const
         case DEMC_FAM_RASTRIGIN:
             h->N = 1;
             break;
+        case DEMC_FAM_ODE_LV: {
+            if (D != 5) return fail(h, DEMC_EINVAL, "ODE_LV: D = 5 required, theta=(alpha,beta,gamma,delta,sigma)");
+            if (ndims < 2 || dm[1] != 2) return fail(h, DEMC_EINVAL, "ODE_LV: dims[1] = 2 required, dims=[T,2] (the observed x and y per time)");
+            if (dm[0] < 1 || dm[0] > kOdeMaxT)
+                return fail(h, DEMC_EINVAL, "ODE_LV: T = dims[0] = " + std::to_string(dm[0]) + " is outside [1, " + std::to_string(kOdeMaxT) + "]");
+            if (nhyper != 4 || !hyper) return fail(h, DEMC_EINVAL, "ODE_LV: hyper=[x0, y0, dt, substeps] (nhyper = 4)");
+            if (!(hyper[3] >= 1.0 && hyper[3] <= (double)kOdeMaxSubsteps && hyper[3] == std::floor(hyper[3])))
+                return fail(h, DEMC_EINVAL, "ODE_LV: substeps (hyper[3]) must be an integer in [1, " + std::to_string(kOdeMaxSubsteps) + "]");
+            if (!(std::isfinite(hyper[2]) && hyper[2] > 0.0)) return fail(h, DEMC_EINVAL, "ODE_LV: dt (hyper[2]) must be finite and positive");
+            if (!std::isfinite(hyper[0]) || !std::isfinite(hyper[1])) return fail(h, DEMC_EINVAL, "ODE_LV: u0 = (x0, y0) (hyper[0], hyper[1]) must be finite");
+            if (!data) return fail(h, DEMC_EINVAL, "ODE_LV: data = Y[T][2] required");
+            for (long long i = 0; i < 2 * dm[0]; ++i)
+                if (!std::isfinite(data[i]))
+                    return fail(h, DEMC_EINVAL, "ODE_LV: data value " + std::to_string(i) + " (time " + std::to_string(i / 2) + ") is not finite");
+            h->N = dm[0];
+            h->ode_substeps = (int)hyper[3];
+            h->ode_u0[0] = hyper[0]; h->ode_u0[1] = hyper[1]; h->ode_u0[2] = h->ode_u0[3] = 0.0;
+            h->ode_h = hyper[2] / hyper[3];
+            dev.assign(data, data + 2 * dm[0]);
+        } break;
         case DEMC_FAM_MVN_ISO:
         case DEMC_FAM_MVN_FULL: {
             const long long N = dm[0];
@@ -1907,6 +1959,22 @@ int32_t demc_set_model_sim(demc_handle* h, int32_t simulator, int32_t estimator,
     });
 }
 
+// DEMC_PRIOR_TRUNCNORMAL: log(Phi((hi - a) / b) - Phi((lo - a) / b)), the mass of Normal(a, b) between the bounds of scalar j, from
+// erfc on the side of the mean where the difference does not cancel (both bounds above the mean: the upper tails).  DEMC_EINVAL
+// when the bounds are empty or the mass is 0 or not finite -- the density would be a division by it.
+static int truncnormal_log_mass(demc_handle* h, size_t j, double a, double b, double lo, double hi, double* out) {
+    const std::string who = "DEMC_PRIOR_TRUNCNORMAL, scalar " + std::to_string(j) + ": ";
+    if (!(std::isfinite(a) && std::isfinite(b) && b > 0.0)) return fail(h, DEMC_EINVAL, who + "Normal(a, b) needs a finite a and a finite b > 0");
+    if (!(lo < hi)) return fail(h, DEMC_EINVAL, who + "the bounds lo >= hi leave nothing to truncate to");
+    const double zl = (lo - a) / b, zh = (hi - a) / b, r = std::sqrt(0.5);
+    // Phi(z) = erfc(-z / sqrt 2) / 2; 1 - Phi(z) = erfc(z / sqrt 2) / 2
+    const double mass = zl > 0.0 ? 0.5 * (std::erfc(zl * r) - std::erfc(zh * r)) : 0.5 * (std::erfc(-zh * r) - std::erfc(-zl * r));
+    if (!(mass > 0.0) || !std::isfinite(mass))
+        return fail(h, DEMC_EINVAL, who + "the mass of the Normal between the bounds is 0 or not finite");
+    *out = std::log(mass);
+    return DEMC_OK;
+}
+
 static int upload_dimtab(demc_handle* h) {
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipMemcpy(h->dimtab, h->h_tab.data(), (size_t)h->c.D * sizeof(DimTab), hipMemcpyHostToDevice));
@@ -1941,21 +2009,37 @@ int32_t demc_set_priors(demc_handle* h, const int32_t* kind, const double* a, co
     USE_DEVICE(h);
     const size_t D = (size_t)h->c.D;
     for (size_t j = 0; j < D; ++j) {
-        if (kind[j] < 0 || kind[j] > DEMC_PRIOR_CAUCHY) return fail(h, DEMC_EUNSUPPORTED, "prior kind not registered");
+        if (kind[j] < 0 || kind[j] > DEMC_PRIOR_TRUNCNORMAL) return fail(h, DEMC_EUNSUPPORTED, "prior kind not registered");
         if (kind[j] == DEMC_PRIOR_NORMAL_REF && (!ref || ref[j] < 0 || ref[j] >= (int)D))
             return fail(h, DEMC_EINVAL, "prior ref out of range");
     }
+    // (checked against the bounds in force before anything is stored: a refused call leaves the table as it was)
+    for (size_t j = 0; j < D; ++j)
+        if (kind[j] == DEMC_PRIOR_TRUNCNORMAL) {
+            double lm = 0.0;
+            if (int rc = truncnormal_log_mass(h, j, a ? a[j] : 0.0, b ? b[j] : 1.0, h->h_tab[j].lo, h->h_tab[j].hi, &lm)) return rc;
+        }
+    h->trunc_sd.assign(D, 0.0);
     for (size_t j = 0; j < D; ++j) {
         DimTab& t = h->h_tab[j];
         const double aj = a ? a[j] : 0.0, bj = b ? b[j] : 1.0;
-        t.kind = kind[j];
+        // truncated(Normal(a, b), lo, hi): the device's Normal entry, its constant lowered by the log of the mass between the bounds
+        const bool trunc = kind[j] == DEMC_PRIOR_TRUNCNORMAL;
+        const int kd = trunc ? (int)PR_NORMAL : kind[j];
+        t.kind = kd;
         t.ref = ref ? ref[j] : 0;
         t.a = aj;
         // reciprocal scale for the location-scale families: no FP64 division per scalar in the kernels
-        const bool recip = kind[j] == PR_NORMAL || kind[j] == PR_HALFCAUCHY || kind[j] == PR_GAMMA ||
-                           kind[j] == PR_EXPONENTIAL || kind[j] == PR_LOGNORMAL || kind[j] == PR_CAUCHY;
+        const bool recip = kd == PR_NORMAL || kd == PR_HALFCAUCHY || kd == PR_GAMMA ||
+                           kd == PR_EXPONENTIAL || kd == PR_LOGNORMAL || kd == PR_CAUCHY;
         t.b = recip ? 1.0 / bj : bj;
-        t.c = prior_const(kind[j], aj, bj);
+        t.c = prior_const(kd, aj, bj);
+        if (trunc) {
+            double lm = 0.0;
+            truncnormal_log_mass(h, j, aj, bj, t.lo, t.hi, &lm);
+            t.c -= lm;
+            h->trunc_sd[j] = bj;
+        }
     }
     return upload_dimtab(h);
     });
@@ -1966,9 +2050,17 @@ int32_t demc_set_bounds(demc_handle* h, const double* lo, const double* hi) {
     if (!h || !lo || !hi) return DEMC_EINVAL;
     USE_DEVICE(h);
     const size_t D = (size_t)h->c.D;
+    // Truncated Normal priors: their constant holds the mass between the bounds, so it is formed again from the new ones -- priors
+    // and bounds arrive in either order.  Checked first: a refused call leaves the table as it was.
+    std::vector<double> lm(D, 0.0);
+    for (size_t j = 0; j < D; ++j)
+        if (j < h->trunc_sd.size() && h->trunc_sd[j] != 0.0)
+            if (int rc = truncnormal_log_mass(h, j, h->h_tab[j].a, h->trunc_sd[j], lo[j], hi[j], &lm[j])) return rc;
     for (size_t j = 0; j < D; ++j) {
         h->h_tab[j].lo = lo[j];
         h->h_tab[j].hi = hi[j];
+        if (j < h->trunc_sd.size() && h->trunc_sd[j] != 0.0)
+            h->h_tab[j].c = prior_const(PR_NORMAL, h->h_tab[j].a, h->trunc_sd[j]) - lm[j];
     }
     return upload_dimtab(h);
     });
@@ -2967,6 +3059,7 @@ int32_t demc_last_kernels(demc_handle* h, char* out, int32_t nbytes) {
         case demc_handle::K2_USER: s += " + k_user_loglike"; break;
         case demc_handle::K2_USER_ROW: s += " + k_user_row"; break;
         case demc_handle::K2_SIM: s += " + " + name_sim(L.k2_key); break;
+        case demc_handle::K2_ODE: s += " + " + name_ode(L.k2_key); break;
     }
     if (L.k3) s += " + k_accept_store";
     std::snprintf(out, (size_t)nbytes, "%s", s.c_str());

@@ -65,6 +65,7 @@ inline std::string name_sim(const InstKey& k) {  // <SIM, EST>; SIM_USER: the in
     return std::string("k_sim_loglike<") + (k.v[1] == EST_KDE ? "kde" : k.v[1] == EST_FREQ ? "frequency" : "kde_choice") + "," +
            (k.v[0] == SIM_NORMAL ? "normal" : k.v[0] == SIM_BINOMIAL ? "binomial" : k.v[0] == SIM_LNR ? "lnr" : "user") + ">";
 }
+inline std::string name_ode(const InstKey& k) { return std::string("k_ode_loglike<") + (k.v[0] == ODE_LV ? "lv" : "?") + ">"; }  // <SYS>
 
 // ---- the tables
 using K1Fn = void (*)(KParams);  // K1 and the kernels that carry a whole update: k_propose, k_longrow, k_res_mvn, k_frozen_sweep, k_res_obs
@@ -72,6 +73,7 @@ using K1Inst = Inst<K1Fn>;
 using ChunkFn = void (*)(KParams, int, unsigned long long*);  // k_direct_mvn, k_lba_wave
 using CrossFn = void (*)(KParams, const double*, int, int, const double*, int, int, int);
 using SimFn = void (*)(SimKParams);
+using OdeFn = void (*)(OdeKParams);
 #define DEMC_ENTRY(KERNEL, NAME, ...) {KERNEL<__VA_ARGS__>, {{__VA_ARGS__}}, NAME},
 #define DEMC_E_PROPOSE(...) DEMC_ENTRY(k_propose, name_propose, __VA_ARGS__)
 #define DEMC_E_RES_MVN(...) DEMC_ENTRY(k_res_mvn, name_res_mvn, __VA_ARGS__)
@@ -83,6 +85,7 @@ using SimFn = void (*)(SimKParams);
 #define DEMC_E_LBA_WAVE(...) DEMC_ENTRY(k_lba_wave, name_lba_wave, __VA_ARGS__)
 #define DEMC_E_SIM(...) DEMC_ENTRY(k_sim_loglike, name_sim, __VA_ARGS__)
 #define DEMC_E_SIM_CHOICE(SIM) {k_sim_choice<SIM>, {{SIM, EST_KDE_CHOICE}}, name_sim},  // (the pair kernel: its estimator is its own)
+#define DEMC_E_ODE(...) DEMC_ENTRY(k_ode_loglike, name_ode, __VA_ARGS__)
 constexpr K1Inst kPropose[] = {DEMC_K1_PHASE_INSTANCES(DEMC_E_PROPOSE) DEMC_K1_RES_INSTANCES(DEMC_E_PROPOSE) DEMC_K1_STREAM_INSTANCES(DEMC_E_PROPOSE)};
 constexpr K1Inst kResMvn[] = {DEMC_RESMVN_INSTANCES(DEMC_E_RES_MVN) DEMC_RESMVN_INSTANCES_DIR(DEMC_E_RES_MVN)};
 constexpr K1Inst kFrozen[] = {DEMC_FROZEN_INSTANCES(DEMC_E_FROZEN)};
@@ -92,8 +95,9 @@ constexpr Inst<ChunkFn> kDirect[] = {DEMC_DIRECT_INSTANCES(DEMC_E_DIRECT)};
 constexpr Inst<CrossFn> kCross[] = {DEMC_CROSS_INSTANCES(DEMC_E_CROSS)};
 constexpr Inst<ChunkFn> kLbaWave[] = {DEMC_LBA_WAVE_INSTANCES(DEMC_E_LBA_WAVE)};
 constexpr Inst<SimFn> kSim[] = {DEMC_SIM_INSTANCES(DEMC_E_SIM) DEMC_SIM_CHOICE_INSTANCES(DEMC_E_SIM_CHOICE)};
+constexpr Inst<OdeFn> kOde[] = {DEMC_ODE_INSTANCES(DEMC_E_ODE)};
 static_assert(unique_keys(kPropose) && unique_keys(kResMvn) && unique_keys(kFrozen) && unique_keys(kLongrow) && unique_keys(kResObs) &&
-                  unique_keys(kCross) && unique_keys(kDirect) && unique_keys(kLbaWave) && unique_keys(kSim),
+                  unique_keys(kCross) && unique_keys(kDirect) && unique_keys(kLbaWave) && unique_keys(kSim) && unique_keys(kOde),
               "an instance list names the same template arguments twice");
 
 }  // namespace demc

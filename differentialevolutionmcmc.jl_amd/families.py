@@ -10,7 +10,9 @@ import numpy as np
 # likelihood family ids (include/demc.h)
 FAM_GAUSSIAN, FAM_MVN_ISO, FAM_MVN_FULL, FAM_BINOMIAL, FAM_HIER_BINOMIAL, FAM_HIER_GAUSSIAN, FAM_LBA, FAM_LNR, \
     FAM_RASTRIGIN = range(9)
+FAM_ODE_LV = 9
 FAM_USER = 100
+ODE_MAX_T, ODE_MAX_SUBSTEPS = 4096, 1024  # the caps of DEMC_FAM_ODE_LV (csrc/demc_ode.hpp)
 # simulation-based likelihoods (demc_set_model_sim): simulator and estimator codes (include/demc.h)
 SIM_NORMAL, SIM_BINOMIAL, SIM_LNR, SIM_USER = 0, 1, 2, 100
 SIMEST_KDE_EPANECHNIKOV, SIMEST_FREQUENCY, SIMEST_KDE_CHOICE = 0, 1, 2
@@ -18,6 +20,7 @@ SIM_MAX_N = 16384
 SIM_CHOICE_MAX_N = 15000  # the cap of the "kde_choice" estimator: a choice byte beside every simulated time, and the per-choice tables
 PRIOR_FLAT, PRIOR_NORMAL, PRIOR_HALFCAUCHY, PRIOR_UNIFORM, PRIOR_BETA, PRIOR_NORMAL_REF, PRIOR_GAMMA, \
     PRIOR_EXPONENTIAL, PRIOR_LOGNORMAL, PRIOR_CAUCHY = range(10)
+PRIOR_TRUNCNORMAL = 10
 
 
 # ---- priors: named like Distributions.jl -------------------------------------------------------
@@ -93,6 +96,31 @@ class Cauchy(Prior):
 
     def __init__(self, loc=0.0, scale=1.0):
         self.a, self.b = float(loc), float(scale)
+
+
+class TruncatedNormal(Prior):
+    """truncated(Normal(mu, sd), lo, hi) with [lo, hi] the parameter's bounds in DE(bounds=...)
+    (Examples/Predator_Prey_Example.jl:28-31): the library divides the Normal density by its mass between the bounds."""
+    kind = PRIOR_TRUNCNORMAL
+
+    def __init__(self, mu=0.0, sd=1.0):
+        if not (np.isfinite(mu) and np.isfinite(sd) and float(sd) > 0):
+            raise ValueError("TruncatedNormal(mu, sd): a finite mu and a finite sd > 0")
+        self.a, self.b = float(mu), float(sd)
+
+    def log_mass(self, lo, hi):
+        """log(Phi((hi - mu) / sd) - Phi((lo - mu) / sd)) as the library forms it (erfc on the side of the mean where the
+        difference does not cancel): what demc_set_priors / demc_set_bounds take off the Normal's constant.  Raises where the
+        library refuses: lo >= hi, or a mass that is 0 or not finite."""
+        import math
+        lo, hi = float(lo), float(hi)
+        if not lo < hi:
+            raise ValueError("TruncatedNormal: the bounds lo >= hi leave nothing to truncate to")
+        zl, zh, r = (lo - self.a) / self.b, (hi - self.a) / self.b, math.sqrt(0.5)
+        mass = 0.5 * (math.erfc(zl * r) - math.erfc(zh * r)) if zl > 0.0 else 0.5 * (math.erfc(-zh * r) - math.erfc(-zl * r))
+        if not (mass > 0.0 and math.isfinite(mass)):
+            raise ValueError("TruncatedNormal: the mass of the Normal between the bounds is 0 or not finite")
+        return math.log(mass)
 
 
 class Priors:
@@ -196,6 +224,42 @@ class LNRLikelihood(Likelihood):
         c = np.asarray(data[0], dtype=np.float64).ravel()
         rt = np.asarray(data[1], dtype=np.float64).ravel()
         return np.concatenate([c, rt]), [c.size, int(np.prod(shapes[0])) if shapes[0] else 1], [self.sigma]
+
+
+class LotkaVolterraLikelihood(Likelihood):
+    """Examples/Predator_Prey_Example.jl:6-11,56-65: data[:, j] ~ MvNormal(u(t_j), sigma) with u = (x, y) the solution of
+    dx/dt = (alpha - beta y) x, dy/dt = (delta x - gamma) y from u0 at t = 0, observed at t_j = j dt; theta = (alpha, beta, gamma,
+    delta, sigma).  data: 2 x T as in the reference (row 0 = x, row 1 = y; T x 2 is taken as given when T != 2).  The library
+    integrates with classical RK4 at the fixed step dt / substeps, not with the reference's adaptive Tsit5(): DESIGN.md 5.4 has the
+    global error against substeps, from which the default is taken."""
+    family = FAM_ODE_LV
+
+    def __init__(self, u0=(1.0, 1.0), dt=0.1, substeps=10):
+        u0 = np.asarray(u0, dtype=np.float64).ravel()
+        if u0.size != 2 or not np.all(np.isfinite(u0)):
+            raise ValueError("LotkaVolterraLikelihood: u0 = (x0, y0), finite")
+        if not (np.isfinite(dt) and float(dt) > 0):
+            raise ValueError("LotkaVolterraLikelihood: dt must be finite and positive")
+        if int(substeps) != substeps or not 1 <= int(substeps) <= ODE_MAX_SUBSTEPS:
+            raise ValueError(f"LotkaVolterraLikelihood: substeps must be an integer in [1, {ODE_MAX_SUBSTEPS}]")
+        self.u0, self.dt, self.substeps = (float(u0[0]), float(u0[1])), float(dt), int(substeps)
+
+    def pack(self, data, shapes):
+        """-> (Y[T][2] row-major, [T, 2], [x0, y0, dt, substeps]); refuses what demc_set_model refuses"""
+        D = int(sum(int(np.prod(s)) if len(s) else 1 for s in shapes))
+        if D != 5:
+            raise ValueError(f"LotkaVolterraLikelihood reads theta = (alpha, beta, gamma, delta, sigma): D = 5, the model has {D}")
+        y = np.asarray(data, dtype=np.float64)
+        if y.ndim != 2 or 2 not in y.shape:
+            raise ValueError("LotkaVolterraLikelihood: data must be 2 x T (or T x 2): the observed x and y per time")
+        if y.shape[0] == 2:  # the reference's layout: a column per time
+            y = y.T
+        T = y.shape[0]
+        if not 1 <= T <= ODE_MAX_T:
+            raise ValueError(f"LotkaVolterraLikelihood: T = {T} observation times, must be in [1, {ODE_MAX_T}]")
+        if not np.all(np.isfinite(y)):
+            raise ValueError("LotkaVolterraLikelihood: data must be finite")
+        return np.ascontiguousarray(y), [T, 2], [self.u0[0], self.u0[1], self.dt, float(self.substeps)]
 
 
 class RastriginObjective(Likelihood):

@@ -88,6 +88,16 @@ enum {
     DEMC_FAM_LBA = 6,            /* theta=(nu[A],A,k,tau); data=[choice[N], rt[N]]; dims=[N,A] Examples/Run_LBA.jl:33-37 */
     DEMC_FAM_LNR = 7,            /* theta=(nu[A],tau); data=[choice[N], rt[N]]; dims=[N,A]; hyper=[sigma] test/lognormal_race_tests.jl:9-12 */
     DEMC_FAM_RASTRIGIN = 8,      /* objective only; dims=[]                                test/optimization_tests.jl:15-23 */
+    DEMC_FAM_ODE_LV,             /* 9: theta=(alpha,beta,gamma,delta,sigma), D=5; data Y[T][2], row j = the observed (x, y) at
+                                    t_j = j dt; dims=[T,2], 1 <= T <= 4096; hyper=[x0, y0, dt, substeps]
+                                    Examples/Predator_Prey_Example.jl:6-11,56-65.  dx/dt = (alpha - beta y) x,
+                                    dy/dt = (delta x - gamma) y from (x0, y0) at t_0 = 0, solved by classical RK4 with the fixed step
+                                    h = dt / substeps (substeps an integer in [1, 1024] steps between consecutive observations; the
+                                    reference's adaptive Tsit5() is NOT reproduced: DESIGN.md 5.4 has the error table);
+                                    loglike = sum_j sum_c logpdf(Normal(u_c(t_j), sigma), Y[j][c]); sigma <= 0 or any non-finite
+                                    state or residual gives -Inf.  The reference's saveat = 0.1 on (0, 10) is T = 101, dt = 0.1.
+                                    (The enumerators written `NAME = value` are mirrored value for value by the CPU test oracle;
+                                    this family has no CPU counterpart and takes the next value.) */
     DEMC_FAM_USER = 100          /* per-observation log-density supplied as HIP source, see demc_set_model_source */
 };
 
@@ -102,7 +112,12 @@ enum {
     DEMC_PRIOR_GAMMA = 6,       /* Gamma(shape a, scale b) */
     DEMC_PRIOR_EXPONENTIAL = 7, /* Exponential(scale b)      (Distributions.jl parameterisation) */
     DEMC_PRIOR_LOGNORMAL = 8,   /* LogNormal(a, b) */
-    DEMC_PRIOR_CAUCHY = 9       /* Cauchy(a, b) */
+    DEMC_PRIOR_CAUCHY = 9,      /* Cauchy(a, b) */
+    DEMC_PRIOR_TRUNCNORMAL      /* 10: truncated(Normal(a, b), lo, hi) with [lo, hi] the scalar's bounds (demc_set_bounds, in either
+                                   order with demc_set_priors): inside the bounds the Normal density over its mass between them,
+                                   Phi((hi-a)/b) - Phi((lo-a)/b); outside them a proposal is out of bounds and never scored.
+                                   DEMC_EINVAL while lo >= hi or that mass is 0 or not finite.  (No CPU-oracle counterpart, like
+                                   DEMC_FAM_ODE_LV.)  Examples/Predator_Prey_Example.jl:28-31 */
 };
 
 /* POD mirror of the DE keyword constructor (structs.jl:80-131). */

@@ -47,6 +47,12 @@ struct ModelSpec
     prior_b::Vector{Float64}
     prior_ref::Vector{Int32}
 end
+# The codes include/demc.h added last, by name.  DEMC_FAM_ODE_LV: Examples/Predator_Prey_Example.jl, theta = (α, β, γ, δ, σ),
+# `data` = Y[T][2] row-major (`vec(permutedims(data))` of the example's 2 x T array), `dims = [T, 2]`,
+# `hyper = [x0, y0, dt, substeps]` -- classical RK4 at the fixed step dt / substeps, not Tsit5().  DEMC_PRIOR_TRUNCNORMAL:
+# `truncated(Normal(a, b), lo, hi)` with (lo, hi) the scalar's entry of `de.bounds`.
+const FAM_ODE_LV = Int32(9)
+const PRIOR_TRUNCNORMAL = Int32(10)
 
 """
 Simulation-based model (include/demc.h, demc_set_model_sim): a simulator instead of a density -- the device form of
