@@ -2066,11 +2066,122 @@ __global__ __launch_bounds__(256, 2) void k_cross_mfma(KParams p, const double* 
 // logpdf(MvNormal(mu, Sigma), x_i) summed over i) with the whitening done once:  sum_i |z_i - m|^2,  z_i = L^-1 (x_i - xbar)
 // (demc_set_model),  m = L^-1 (theta' - xbar) (K1's preparation, on the matrix cores).  Unlike the expanded form this one
 // does not separate into data-only and proposal-only factors: every (proposal, observation) pair costs 3 d flop on the
-// FP64 vector pipe (SURVEY 8d's count), nothing collapses.  Thread per proposal with m in registers; all lanes of a wave
-// visit the same observation, so a z row is one wave-uniform (scalar) load and enters the VALU as an SGPR operand; per
-// dimension one v_add_f64 and one v_fma_f64.  DP = padded row length (host pads z rows and m with zeros).
-// grid = (proposal blocks of 256, observation chunks).
+// FP64 vector pipe (SURVEY 8d's count), nothing collapses.  The proposals' m in registers; all lanes of a wave visit the
+// same observation, so a z row is one wave-uniform (scalar) load and enters the VALU as an SGPR operand; per (proposal,
+// observation, dimension) one v_add_f64 and one v_fma_f64.  DP = padded row length (host pads z rows and m with zeros).
+// grid = (proposal blocks of 256, observation chunks); a workgroup is 256 proposals x one chunk in both bodies below:
+// DP = 32 (the headline) splits a row over wave pairs and prefetches it (direct_mvn_slices), the other lengths hold whole
+// rows, thread per proposal (direct_mvn_rows).
 // ------------------------------------------------------------------------------------------------
+// The whole-row body (DP = 8, 16, 64): thread per proposal, the DP values of m in registers, a row of z per trip.  The
+// s_load_dwordx16 of a row sit at the top of the trip with s_waitcnt lgkmcnt(0) right behind them: the wait is exposed per wave and
+// the other waves of the SIMD cover most of it.
+template <int DP>
+__device__ __forceinline__ void direct_mvn_rows(const KParams& p, int pblock, int chunk, int n_chunks) {
+    const int q = pblock * 256 + threadIdx.x;
+    const bool ok = q < p.n_groups * p.n_act;
+    const size_t slot = ok ? (size_t)slot_of(p, q) : 0;
+    double m[DP];
+    const double* mrow = p.Ypad + slot * p.dpad;
+#pragma unroll
+    for (int k = 0; k < DP; ++k) m[k] = (ok && k < p.d) ? mrow[k] : 0.0;
+    const long long per = (p.N + n_chunks - 1) / n_chunks;
+    const long long i0 = chunk * per, i1 = (i0 + per < p.N) ? i0 + per : p.N;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};  // four independent chains per lane
+    const double* z = p.data + i0 * DP;
+    for (long long i = i0; i < i1; ++i, z += DP) {
+#pragma unroll
+        for (int k = 0; k < DP; k += 4) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const double r = z[k + e] - m[k + e];
+                acc[e] = fma(r, r, acc[e]);
+            }
+        }
+    }
+    if (ok) p.partial[(size_t)chunk * p.P + slot] = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+}
+
+// The sliced body (DP = 32): a wave takes HALF the dimensions of TWICE the proposals.  Wave w of the workgroup: slice s = w >> 1
+// (dimensions 16 s ... 16 s + 15), proposal half h = w & 1; a lane holds the 16 m values of the proposals pblock * 256 + h * 128 +
+// lane and + 64 (64 registers of m, as the whole-row body).  A wave's share of a row is then 16 doubles = 32 SGPRs, and TWO fit:
+// the next row's slice is asked for before the current one is consumed --
+//     wait(A) . ask B = row i + 1 . 64 FP64 on A . wait(B) . ask A = row i + 2 . 64 FP64 on B
+// -- one wait per 64 FP64 instructions as in the whole-row body, but for a load issued 256 cycles of the wave's own arithmetic
+// earlier.  (SMEM returns out of order, so lgkmcnt can only be waited to 0: with whole rows per wave a prefetch means two waits a
+// row, each behind 128 cycles -- measured slower, profiles/r06/NOTES.md 1.)  The compiler folds a prefetch written in plain C++ back
+// to load-then-wait, so the loads and the wait are asm statements: the loads write 16-dword SGPR tuples, the wait takes the tuples
+// as in/out operands so that their consumers stay behind it, and a scheduling barrier behind each keeps the arithmetic from
+// being moved across.  The prefetch address is clamped to the chunk's last row (the buffer ends at row N - 1), and a last wait
+// leaves no load in flight when the loop's results are used.  The two slices' sums meet in LDS: slice 0 stores own + other, one
+// partial per (chunk, proposal) in a fixed order.
+typedef int zs16 __attribute__((ext_vector_type(16)));
+typedef double zd8 __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ void zslice_ask(zs16& lo, zs16& hi, const double* row) {  // row: wave-uniform, 16 doubles
+    asm volatile("s_load_dwordx16 %0, %2, 0x0\n\ts_load_dwordx16 %1, %2, 0x40" : "=&s"(lo), "=&s"(hi) : "s"(row) : "memory");
+    __builtin_amdgcn_sched_barrier(0);
+}
+__device__ __forceinline__ void zslice_wait(zs16& lo, zs16& hi) {
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(lo), "+s"(hi));
+    __builtin_amdgcn_sched_barrier(0);
+}
+__device__ __forceinline__ void zslice_fma(const zs16& lo, const zs16& hi, const double (&m0)[16], const double (&m1)[16],
+                                           double (&a0)[2], double (&a1)[2]) {
+    const zd8 zl = __builtin_bit_cast(zd8, lo), zh = __builtin_bit_cast(zd8, hi);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {  // two chains per proposal, four per lane
+        const double z = k < 8 ? zl[k & 7] : zh[k & 7];
+        const double r0 = z - m0[k], r1 = z - m1[k];
+        a0[k & 1] = fma(r0, r0, a0[k & 1]);
+        a1[k & 1] = fma(r1, r1, a1[k & 1]);
+    }
+}
+__device__ __forceinline__ void direct_mvn_slices(const KParams& p, int pblock, int chunk, int n_chunks) {
+    __shared__ double s_other[256];  // slice 1's sums, by proposal of the block
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int s = wave >> 1, h = wave & 1;
+    const int n_prop = p.n_groups * p.n_act;
+    const int t0 = h * 128 + lane, t1 = t0 + 64;  // the lane's two proposals within the block
+    const bool ok0 = pblock * 256 + t0 < n_prop, ok1 = pblock * 256 + t1 < n_prop;
+    const size_t slot0 = ok0 ? (size_t)slot_of(p, pblock * 256 + t0) : 0, slot1 = ok1 ? (size_t)slot_of(p, pblock * 256 + t1) : 0;
+    double m0[16], m1[16];
+    const double *mrow0 = p.Ypad + slot0 * p.dpad + 16 * s, *mrow1 = p.Ypad + slot1 * p.dpad + 16 * s;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        m0[k] = (ok0 && 16 * s + k < p.d) ? mrow0[k] : 0.0;
+        m1[k] = (ok1 && 16 * s + k < p.d) ? mrow1[k] : 0.0;
+    }
+    const long long per = (p.N + n_chunks - 1) / n_chunks;
+    const long long i0 = chunk * per, i1 = (i0 + per < p.N) ? i0 + per : p.N;
+    const int n = (int)(i1 - i0);  // rows of the chunk (32-bit, so that the loop control stays on the scalar unit: 2^31 rows are 512 GB)
+    double a0[2] = {0.0, 0.0}, a1[2] = {0.0, 0.0};
+    if (n > 0) {
+        const double* z = p.data + i0 * 32 + 16 * s;
+        zs16 alo, ahi, blo, bhi;
+        zslice_ask(alo, ahi, z);
+        for (int left = n; left >= 2; left -= 2, z += 64) {
+            zslice_wait(alo, ahi);
+            zslice_ask(blo, bhi, z + 32);
+            zslice_fma(alo, ahi, m0, m1, a0, a1);
+            zslice_wait(blo, bhi);
+            zslice_ask(alo, ahi, left > 2 ? z + 64 : z + 32);  // never past the chunk's last row
+            zslice_fma(blo, bhi, m0, m1, a0, a1);
+        }
+        zslice_wait(alo, ahi);  // nothing in flight from here on
+        if (n & 1) zslice_fma(alo, ahi, m0, m1, a0, a1);  // the odd last row
+    }
+    const double sum0 = a0[0] + a0[1], sum1 = a1[0] + a1[1];
+    if (s == 1) {
+        s_other[t0] = sum0;
+        s_other[t1] = sum1;
+    }
+    __syncthreads();
+    if (s == 0) {
+        if (ok0) p.partial[(size_t)chunk * p.P + slot0] = sum0 + s_other[t0];
+        if (ok1) p.partial[(size_t)chunk * p.P + slot1] = sum1 + s_other[t1];
+    }
+}
+
 // `clk` (demc_timing_enable only, else null: a wave-uniform branch on a kernarg, AFTER the loop): every workgroup leaves the
 // shader-clock counter (s_memtime), the 100 MHz reference counter (s_memrealtime) and the CU it ran on as it ENDS, so that the host
 // can say which clock the vector pipe held under THIS kernel's load (demc_timing_clock: counter differences between the first and
@@ -2091,32 +2202,10 @@ __global__ __launch_bounds__(256) void k_direct_mvn(KParams p, int n_chunks, uns
         chunk = (int)((j / gridDim.x) * 8u + xcd);
         pblock = (int)(j % gridDim.x);
     }
-    const int q = pblock * 256 + threadIdx.x;
-    const int n_prop = p.n_groups * p.n_act;
-    const bool ok = q < n_prop;
-    const size_t slot = ok ? (size_t)slot_of(p, q) : 0;
-    double m[DP];
-    const double* mrow = p.Ypad + slot * p.dpad;
-#pragma unroll
-    for (int k = 0; k < DP; ++k) m[k] = (ok && k < p.d) ? mrow[k] : 0.0;
-    const long long per = (p.N + n_chunks - 1) / n_chunks;
-    const long long i0 = chunk * per, i1 = (i0 + per < p.N) ? i0 + per : p.N;
-    double acc[4] = {0.0, 0.0, 0.0, 0.0};  // four independent chains per lane
-    const double* z = p.data + i0 * DP;
-    for (long long i = i0; i < i1; ++i, z += DP) {
-#pragma unroll
-        for (int k = 0; k < DP; k += 4) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const double r = z[k + e] - m[k + e];
-                acc[e] = fma(r, r, acc[e]);
-            }
-        }
-    }
-    // (The four s_load_dwordx16 of a row sit at the top of the trip with s_waitcnt lgkmcnt(0) right behind them: the wait is exposed
-    // per wave and six waves per SIMD cover most of it.  A half-row pipeline written in the source -- each half of the NEXT row asked
-    // for as soon as the current half is consumed -- is folded back by the compiler into exactly this shape; profiles/r06/NOTES.md.)
-    if (ok) p.partial[(size_t)chunk * p.P + slot] = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+    if constexpr (DP == 32)
+        direct_mvn_slices(p, pblock, chunk, n_chunks);
+    else
+        direct_mvn_rows<DP>(p, pblock, chunk, n_chunks);
     if (clk) {
         const unsigned long long t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
         const unsigned xcc = __builtin_amdgcn_s_getreg(20 | (3 << 11)) & 15u;  // hwreg(HW_REG_XCC_ID, 0, 4)
