@@ -2114,7 +2114,8 @@ __device__ __forceinline__ void direct_mvn_rows(const KParams& p, int pblock, in
 // as in/out operands so that their consumers stay behind it, and a scheduling barrier behind each keeps the arithmetic from
 // being moved across.  The prefetch address is clamped to the chunk's last row (the buffer ends at row N - 1), and a last wait
 // leaves no load in flight when the loop's results are used.  The two slices' sums meet in LDS: slice 0 stores own + other, one
-// partial per (chunk, proposal) in a fixed order.
+// partial per (chunk, proposal) in a fixed order.  Nothing but the LDS index of the lane stays in vector registers over the row
+// loop for the stores behind it (profiles/r06/NOTES.md 9).
 typedef int zs16 __attribute__((ext_vector_type(16)));
 typedef double zd8 __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ void zslice_ask(zs16& lo, zs16& hi, const double* row) {  // row: wave-uniform, 16 doubles
@@ -2138,18 +2139,28 @@ __device__ __forceinline__ void zslice_fma(const zs16& lo, const zs16& hi, const
 }
 __device__ __forceinline__ void direct_mvn_slices(const KParams& p, int pblock, int chunk, int n_chunks) {
     __shared__ double s_other[256];  // slice 1's sums, by proposal of the block
+    // The lane's two slots are needed again only behind the row loop: they wait in LDS, not in registers (as 32-bit values: a slot is
+    // slot_of's int; kNoSlot: no such proposal), written and read by the SAME lane of a slice-0 wave, so no barrier is theirs.
+    __shared__ int s_slot[256];
+    constexpr int kNoSlot = -1;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int s = wave >> 1, h = wave & 1;
     const int n_prop = p.n_groups * p.n_act;
     const int t0 = h * 128 + lane, t1 = t0 + 64;  // the lane's two proposals within the block
-    const bool ok0 = pblock * 256 + t0 < n_prop, ok1 = pblock * 256 + t1 < n_prop;
-    const size_t slot0 = ok0 ? (size_t)slot_of(p, pblock * 256 + t0) : 0, slot1 = ok1 ? (size_t)slot_of(p, pblock * 256 + t1) : 0;
     double m0[16], m1[16];
-    const double *mrow0 = p.Ypad + slot0 * p.dpad + 16 * s, *mrow1 = p.Ypad + slot1 * p.dpad + 16 * s;
+    {
+        const bool ok0 = pblock * 256 + t0 < n_prop, ok1 = pblock * 256 + t1 < n_prop;
+        const int slot0 = ok0 ? slot_of(p, pblock * 256 + t0) : 0, slot1 = ok1 ? slot_of(p, pblock * 256 + t1) : 0;
+        if (s == 0) {
+            s_slot[t0] = ok0 ? slot0 : kNoSlot;
+            s_slot[t1] = ok1 ? slot1 : kNoSlot;
+        }
+        const double *mrow0 = p.Ypad + (size_t)slot0 * p.dpad + 16 * s, *mrow1 = p.Ypad + (size_t)slot1 * p.dpad + 16 * s;
 #pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        m0[k] = (ok0 && 16 * s + k < p.d) ? mrow0[k] : 0.0;
-        m1[k] = (ok1 && 16 * s + k < p.d) ? mrow1[k] : 0.0;
+        for (int k = 0; k < 16; ++k) {
+            m0[k] = (ok0 && 16 * s + k < p.d) ? mrow0[k] : 0.0;
+            m1[k] = (ok1 && 16 * s + k < p.d) ? mrow1[k] : 0.0;
+        }
     }
     const long long per = (p.N + n_chunks - 1) / n_chunks;
     const long long i0 = chunk * per, i1 = (i0 + per < p.N) ? i0 + per : p.N;
@@ -2177,8 +2188,10 @@ __device__ __forceinline__ void direct_mvn_slices(const KParams& p, int pblock, 
     }
     __syncthreads();
     if (s == 0) {
-        if (ok0) p.partial[(size_t)chunk * p.P + slot0] = sum0 + s_other[t0];
-        if (ok1) p.partial[(size_t)chunk * p.P + slot1] = sum1 + s_other[t1];
+        double* part = p.partial + (size_t)chunk * p.P;  // the chunk's row of partials
+        const int slot0 = s_slot[t0], slot1 = s_slot[t1];
+        if (slot0 != kNoSlot) part[slot0] = sum0 + s_other[t0];
+        if (slot1 != kNoSlot) part[slot1] = sum1 + s_other[t1];
     }
 }
 
