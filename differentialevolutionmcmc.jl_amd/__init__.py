@@ -6,12 +6,12 @@ any sampling call raises -- there is no CPU fallback.
 """
 from . import _ffi, families
 from ._ffi import DemcError, HipEngine, MultiEngine
-from .chains import Chains
+from .chains import Chains, Summary
 from .families import (Beta, BinomialLikelihood, Cauchy, Exponential, Flat, Gamma, GaussianLikelihood, LogNormal, HierBinomialLikelihood,
                        HierGaussianLikelihood, LBALikelihood, LNRLikelihood, LotkaVolterraLikelihood, MvNormalFullLikelihood,
                        MvNormalIsoLikelihood, Normal, Priors, RastriginObjective, SimBinomial, SimLNR, SimNormal, SimSource,
                        SimulatedLikelihood, SourceLikelihood, TruncatedCauchy, TruncatedNormal, Uniform)
-from .sampler import get_optimal, optimize, sample
+from .sampler import get_optimal, optimize, sample, summarize
 from .structs import (DE, DEModel, HIPBackend, MCMCThreads, Particle, as_union, compute_posterior, evaluate_fun,
                       fixed_gamma, maximize, mh_update, minimize, project, random_gamma, resample, sample_current,
                       variable_gamma)
@@ -20,4 +20,4 @@ DEMCMC = __name__
 
 __all__ = ["DE", "Particle", "DEModel", "sample", "MCMCThreads", "HIPBackend", "fixed_gamma", "variable_gamma",
            "random_gamma", "evaluate_fun", "compute_posterior", "optimize", "get_optimal", "resample", "as_union",
-           "mh_update", "maximize", "minimize", "Chains", "Priors", "HipEngine", "MultiEngine", "DemcError"]
+           "mh_update", "maximize", "minimize", "Chains", "Summary", "summarize", "Priors", "HipEngine", "MultiEngine", "DemcError"]

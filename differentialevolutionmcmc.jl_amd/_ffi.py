@@ -27,6 +27,7 @@ EXPORTS = [
     "demc_create_multi", "demc_destroy_multi", "demc_multi_last_error", "demc_multi_size", "demc_multi_shard", "demc_multi_step",
     "demc_set_model_sim",
 ]
+SUMMARY_EXPORTS = ["demc_summarize"]  # include/demc_summary.h: the header next to demc.h (what follows a run)
 COMM_ID_BYTES = 128
 _NOT_STATUS = {"demc_last_error": C.c_char_p, "demc_multi_last_error": C.c_char_p, "demc_multi_shard": C.c_void_p}
 
@@ -141,6 +142,7 @@ def load():
     L.demc_set_history_rows.argtypes = [H, C.c_int64, C.c_int64, _dp]
     L.demc_get_history.argtypes = [H, C.c_int64, C.c_int64, _dp, _bp, _dp, _lp]
     L.demc_export_chains.argtypes = [H, C.c_int64, C.c_int64, C.c_int32, _dp]
+    L.demc_summarize.argtypes = [H, C.c_int64, C.c_int64, C.c_int32, _dp, _dp, C.c_int64]
     L.demc_step.argtypes = [H, C.c_int64, C.c_int32]
     L.demc_update.argtypes = [H, C.c_int64, C.c_int32]
     L.demc_migration_due.argtypes = [C.POINTER(DemcConfig), C.c_int64]
@@ -173,7 +175,7 @@ def load():
     L.demc_multi_size.argtypes = [H]
     L.demc_multi_shard.argtypes = [H, C.c_int32]
     L.demc_multi_step.argtypes = [H, C.c_int64, C.c_int32]
-    for name in EXPORTS:  # every entry point returns an int32 status, except the error strings and the shard accessor
+    for name in EXPORTS + SUMMARY_EXPORTS:  # every entry point returns an int32 status, except the error strings and the shard accessor
         getattr(L, name).restype = _NOT_STATUS.get(name, C.c_int32)
     _lib = L
     return L
@@ -343,6 +345,14 @@ class HipEngine:
         out = np.empty((row1 - row0, self.D + 2, self.P))
         self._ck(self.L.demc_export_chains(self.h, row0, row1, 1, _d(out)))
         return out
+
+    def summarize(self, row0, row1, max_lag=0, rho_len=0):
+        """summary statistics of history rows [row0,row1) computed on the device (demc_summarize of include/demc_summary.h) ->
+        (out[D+2][6] = mean, std, rhat, ess, mcse, pairs per series; rho[D+2][rho_len] or None).  The history stays where it is."""
+        out = np.empty((self.D + 2, 6))
+        rho = np.empty((self.D + 2, rho_len)) if rho_len > 0 else None
+        self._ck(self.L.demc_summarize(self.h, row0, row1, max_lag, _d(out), _d(rho), rho_len))
+        return out, rho
 
     def step(self, iter0, n_iters=1):
         self._ck(self.L.demc_step(self.h, iter0, n_iters))

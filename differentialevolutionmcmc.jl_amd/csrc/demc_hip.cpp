@@ -9,6 +9,7 @@
 //
 // There is NO CPU fallback in this file: every compute entry point launches HIP kernels or fails.
 #include "../../include/demc.h"
+#include "../../include/demc_summary.h"  // demc_summarize
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -39,6 +40,7 @@
 #include "demc_simlike.hpp"
 #define DEMC_ODE_EXTERN  // k_ode_loglike in demc_ode.cpp
 #include "demc_ode.hpp"
+#include "demc_summary.hpp"  // demc_summarize: its kernels and their launches live in demc_summary.cpp
 #include "demc_instances.hpp"  // one table per templated kernel, built from the lists above: every choice of an instance goes through them
 
 using namespace demc;
@@ -2215,6 +2217,22 @@ int32_t demc_export_chains(demc_handle* h, int64_t row0, int64_t row1, int32_t l
     hipFree(dev);
     if (e != hipSuccess) return fail(h, DEMC_EHIP, std::string("demc_export_chains: ") + hipGetErrorString(e));
     return DEMC_OK;
+    });
+}
+
+int32_t demc_summarize(demc_handle* h, int64_t row0, int64_t row1, int32_t max_lag, double* out, double* rho_out, int64_t rho_len) {
+    return guarded(h, [&]() -> int32_t {
+    if (!h || !out || rho_len < 0 || max_lag < 0) return DEMC_EINVAL;
+    USE_DEVICE(h);
+    if (!h->hist) return fail(h, DEMC_EINVAL, "history is not stored on this handle");
+    if (row0 < 0 || row1 - row0 < 1 || row1 > h->c.n_rows) return fail(h, DEMC_EINVAL, "bad rows: demc_summarize needs at least one row of the history");
+    if (h->c.n_groups_total != h->c.n_groups)
+        return fail(h, DEMC_EINVAL, "sharded handle: gather demc_get_history from every rank and summarise on the host");
+    SumArgs a{h->hist, h->acc_hist, h->lp_hist, h->id_hist, h->P, (long long)row0, (long long)row1, (long long)h->c.group_offset * h->c.Np,
+              h->c.D, h->hist_ld, (int)max_lag};
+    std::string msg;
+    const int rc = summary_run(a, h->stream, out, rho_out && rho_len > 0 ? rho_out : nullptr, (long long)rho_len, msg);
+    return rc == DEMC_OK ? DEMC_OK : fail(h, rc, msg);
     });
 }
 

@@ -3,7 +3,7 @@ C-ABI engine.  The per-iteration work -- step!/pstep! (main.jl:84-107) -- happen
 import numpy as np
 
 from . import _ffi
-from .chains import Chains
+from .chains import Chains, Summary
 from .families import PRIOR_NORMAL_REF, Priors, SimulatedLikelihood, SourceLikelihood
 from .structs import (DE, HIPBackend, LOGLIKE_MODES, MCMCThreads, SCHEDULES, DEModel, Particle, maximize)
 
@@ -187,7 +187,7 @@ def _parse(args):
     return backend, int(rest[0])
 
 
-def _run(model, de, n_iter, backend, progress, engine_factory):
+def _run(model, de, n_iter, backend, progress, engine_factory, summary=None):
     if not isinstance(model, DEModel) or not isinstance(de, DE):
         raise TypeError("sample(model::DEModel, de::DE, ...)")
     theta0 = model.sample_prior()
@@ -221,6 +221,8 @@ def _run(model, de, n_iter, backend, progress, engine_factory):
             print()
         de.iter = n_iter + de.n_initial
         n_rows = n_iter + de.n_initial
+        if summary is not None and hasattr(eng, "summarize"):  # summarize(): the statistics on the device, no export at all
+            return lay, eng.summarize(summary[0], summary[1], summary[2])[0], None
         if hasattr(eng, "export_chains"):  # device-side re-key + layout (demc_export_chains)
             full = eng.export_chains(0, n_rows)  # [n_rows][D+2][P] by particle id
         else:  # engines without it (the CPU oracle injected by tests): re-key on the host
@@ -239,6 +241,21 @@ def sample(model, de, *args, progress=False, engine_factory=None, **kwargs):
     lay, full, _ = _run(model, de, n_iter, backend, progress, engine_factory)
     de.samples = full[:, :lay["D"], :]  # the reference's de.samples: (rows, parameters, particle id)
     return bundle_samples(model, de, lay, full, n_iter)
+
+
+def summarize(model, de, *args, max_lag=0, progress=False, engine_factory=None, **kwargs):
+    """summarize(model, de, [HIPBackend(...)], n_iter, max_lag=0): the run of sample() followed by the summary statistics of
+    the rows bundle_samples keeps (offset = burnin or 0, quirk q1 included) -- computed on the device by demc_summarize, so that
+    the history is never exported.  Returns a Summary (chains.py); equal to sample(...).summarystats(max_lag) for the same seed.
+    An engine without summarize (an injected one) exports as sample() does and summarises on the host."""
+    backend, n_iter = _parse(args)
+    Ns = n_iter - de.burnin if de.discard_burnin else n_iter
+    offset = de.burnin if de.discard_burnin else 0
+    lay, res, state = _run(model, de, n_iter, backend, progress, engine_factory, summary=(offset, offset + Ns, max_lag))
+    if state is None:
+        names = get_names(model, lay["shapes"])
+        return Summary(names, res)
+    return bundle_samples(model, de, lay, res, n_iter).summarystats(max_lag)
 
 
 def optimize(model, de, *args, progress=False, engine_factory=None, **kwargs):

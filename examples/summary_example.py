@@ -1,0 +1,28 @@
+#!/usr/bin/env python3
+"""The Gaussian example's run summarised on the device: summarize() is sample() followed by the summary table -- mean, std, split-R-hat,
+effective sample size, Monte-Carlo standard error -- computed from the history where it lives (demc_summarize), so that no chain is
+exported.  The host form of the same table is chains.summarystats()."""
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import demc_amd as D  # noqa: E402
+
+rng = np.random.default_rng(50514)
+data = rng.normal(0.0, 1.0, 50)
+
+
+def sample_prior():
+    return [rng.normal(0, 1), abs(rng.standard_cauchy())]
+
+
+model = D.DEModel(sample_prior=sample_prior, names=("μ", "σ"), data=data,
+                  prior_loglike=D.Priors(μ=D.Normal(0, 1), σ=D.TruncatedCauchy(0, 1)), loglike=D.GaussianLikelihood())
+de = D.DE(sample_prior=sample_prior, bounds=((-np.inf, np.inf), (0.0, np.inf)), burnin=1000, Np=6)
+summary = D.summarize(model, de, D.HIPBackend(seed=1), 2000)
+for name, s in summary.describe().items():
+    print(f"{name}: mean {s['mean']:.3f}  std {s['std']:.3f}  rhat {s['rhat']:.3f}  ess {s['ess']:.0f}  mcse {s['mcse']:.4f}  "
+          f"({s['pairs']:.0f} pairs of lags)")
+print(f"acceptance rate {summary['acceptance']['mean']:.3f}")

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define DEMC_VERSION 130 /* 0.1.3 */
+#define DEMC_VERSION 140 /* 0.1.4 */
 
 enum {
     DEMC_OK = 0,
@@ -288,6 +288,9 @@ int32_t demc_get_history(demc_handle* h, int64_t row0, int64_t row1, double* the
  *   layout 1: out[((row-row0)*(D+2) + j)*P + id]   = C order [n][D+2][P]
  * One kernel + one device-to-host copy; single-shard handles only (ids must be local). */
 int32_t demc_export_chains(demc_handle* h, int64_t row0, int64_t row1, int32_t layout, double* host_out);
+
+/* describe(chains) computed on the device from the same rows, without an export: demc_summarize, declared in the header of its
+ * own next to this one (chain summaries: mean, std, split-R-hat, effective sample size, MCSE, autocorrelation). */
 
 /* n_iters of step!/pstep! (main.jl:84-107) starting at de.iter == iter0 (1-based, n_initial included):
  * migration coin + exchange, update of every group, store.  On a sharded handle (n_groups_total > n_groups) the exchange is

@@ -274,6 +274,9 @@ function sample(model::DEModel, de::DE, b::HIPBackend, n_iter::Int; model_spec::
     return bundle_samples(model, de, [particles], n_iter)                   # src/main.jl:222-250, unchanged
 end
 
+# describe(chains) on the device (include/demc_summary.h): `summarize`, in a file of its own like the header it binds
+include("DEMCHIPSummary.jl")
+
 "final state of the particle objects behind handle `h` (bundle_samples reads accept/lp from them; Θ for completeness)"
 function pull_state!(h, particles, Pl, D, shapes, lens, offs)
     th = Vector{Float64}(undef, Pl * D); wt = Vector{Float64}(undef, Pl); idv = Vector{Int64}(undef, Pl)
