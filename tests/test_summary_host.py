@@ -101,8 +101,107 @@ def restate_all(value, max_lag=0, rho_len=0):
     return [restate(value[:, j, :], max_lag, rho_len) for j in range(value.shape[1])]
 
 
+def restate_np(x, max_lag=0, rho_len=0):
+    """the definition restate() states, once more: every chain at a time with numpy, in np.longdouble, for the sizes at which plain
+    loops take minutes.  Same dict, same pmin, same rule for which rho[t] are filled; nothing is shared with chains.py.  The CPU
+    test below holds it to restate() at rtol 1e-12."""
+    LD = np.longdouble
+    with np.errstate(all="ignore"):  # (inf - inf and 0 / 0 are NaNs by IEEE, which is what the definition asks for)
+        x = np.asarray(x, dtype=np.float64).astype(LD)
+        n, m = x.shape
+        mean = x.sum() / LD(n * m)
+        ss = np.square(x - mean).sum()
+        std = np.sqrt(ss / LD(n * m - 1)) if n * m > 1 and ss == ss else LD(NAN)
+        out = dict(mean=float(mean), std=float(std), rhat=NAN, ess=NAN, mcse=NAN, pairs=0.0, rho=[NAN] * rho_len, pmin=None)
+        h = n // 2
+        if h < 2:
+            return out
+        M = 2 * m
+        s = x[:2 * h].reshape(2, h, m).transpose(1, 0, 2).reshape(h, M)  # a column per split chain (their order does not matter)
+        mu = s.sum(axis=0) / LD(h)
+        y = s - mu
+
+        def gamma_mean(t):
+            return ((y[:h - t] * y[t:]).sum(axis=0) / LD(h)).sum() / LD(M)
+
+        W = gamma_mean(0) * LD(h) / LD(h - 1)
+        bh = np.square(mu - mu.sum() / LD(M)).sum() / LD(M - 1)
+        vplus = W * LD(h - 1) / LD(h) + bh
+        L = min(h - 1, max_lag) if max_lag > 0 else h - 1
+        cache = {}
+
+        def rho(t):
+            if t not in cache:
+                cache[t] = LD(1.0) if t == 0 else (LD(NAN) if vplus == 0 else LD(1.0) - (W - gamma_mean(t)) / vplus)
+            return cache[t]
+
+        def fill(b_last):
+            for t in range(min(rho_len, L + 1, LAG_BLOCK * (b_last + 1))):
+                out["rho"][t] = float(rho(t))
+
+        if W == 0:
+            fill(0)
+            return out
+        out["rhat"] = float(np.sqrt(vplus / W)) if W == W else NAN
+        if h < 4:
+            fill(0)
+            return out
+        K, total, prev, b_last, bad, pmin = 0, LD(0.0), None, L // LAG_BLOCK, False, None
+        while 2 * K + 1 <= L:
+            P = rho(2 * K) + rho(2 * K + 1)
+            if P == P:
+                pmin = abs(P) if pmin is None else min(pmin, abs(P))
+            if not P >= 0:
+                bad = bool(P != P)
+                b_last = (2 * K) // LAG_BLOCK
+                break
+            if prev is not None and prev < P:
+                P = prev
+            total += P
+            prev = P
+            K += 1
+        fill(b_last)
+        tau = max(LD(-1.0) + LD(2.0) * total, LD(1.0) / np.log10(LD(M * h)))
+        out["pairs"] = float(K)
+        out["pmin"] = None if pmin is None else float(pmin)
+        if not bad:
+            ess = LD(M * h) / tau
+            out["ess"] = float(ess)
+            out["mcse"] = float(std / np.sqrt(ess))
+        return out
+
+
+# ---- the launch geometry of the device code, restated: csrc/demc_summary.hpp's constants and summary_run's arithmetic.  The GPU
+# cases assert the geometry they were chosen for, so a changed constant fails them instead of moving them to another path.
+SUM_LAG_BLOCK, SUM_MAX_JT, SUM_MAX_WORKERS = 64, 8, 1024
+SUM_LDS_SMALL, SUM_LDS_MAX, SUM_GLOBAL_TILE = 64 * 1024, 144 * 1024, 64 << 20
+
+
+def geometry(n, P, D):
+    """what demc_summarize launches for n rows of P chains and D parameters (max_lag = 0) -> dict(mode: "lds64" | "lds144" |
+    "global", JT: series per tile, tiles: the width of every series tile, workers, chains_per_worker_max, lag_blocks)"""
+    D2, h = D + 2, n // 2
+    per_series = (n + 2 * SUM_LAG_BLOCK) * 8
+    workers = min(P, SUM_MAX_WORKERS)
+    if per_series <= SUM_LDS_SMALL:
+        mode, JT = "lds64", min(D2, SUM_MAX_JT, SUM_LDS_SMALL // per_series)
+    elif per_series <= SUM_LDS_MAX:
+        mode, JT = "lds144", 1
+    else:
+        mode, JT = "global", 1
+        workers = max(1, min(workers, SUM_GLOBAL_TILE // (n * D2 * 8)))
+    return dict(mode=mode, JT=JT, tiles=[min(JT, D2 - j0) for j0 in range(0, D2, JT)], workers=workers,
+                chains_per_worker_max=-(-P // workers), lag_blocks=(h - 1) // SUM_LAG_BLOCK + 1 if h >= 2 else 0)
+
+
 # ---- the deterministic inputs of the GPU tests: x_0 = e_0, x_i = phi x_{i-1} + e_i, shifted by 100 (|mean| / sd <= 100)
 AR1_CASES = [(64, 4, 0.0), (65, 4, 0.9), (129, 3, -0.5), (200, 8, 0.5), (1000, 16, 0.95)]
+# the inputs of the GPU cases that leave the smallest launch geometry (a list of its own: plain loops run over AR1_CASES), with
+# the lag caps each is summarised under and the number of series that are scaled (below)
+AR1_LARGE = [(16, 1024, 0.5), (16, 1025, 0.5), (130, 1025, 0.9), (130, 4096, 0.9), (2000, 8, 0.5), (3900, 8, 0.5), (18305, 64, 0.5),
+             (16, 8, 0.5)]
+LARGE_MAX_LAGS = {(1000, 16, 0.95): (63, 64, 65, 127, 128)}
+LARGE_SCALED = {(16, 1025, 0.5): 7, (130, 1025, 0.9): 7, (130, 4096, 0.9): 7, (18305, 64, 0.5): 6, (16, 8, 0.5): 70}
 SEEDS = (0, 1, 2)
 MARGIN = 1e-6  # an error of 1e-12 in rho cannot flip a pair that is this far from zero
 
@@ -114,6 +213,20 @@ def ar1(n, m, phi, seed):
     for i in range(1, n):
         x[i] = phi * x[i - 1] + e[i]
     return x + 100.0
+
+
+def scaled(x, j):
+    """series j of a case with more than three parameters: two series fed by the same seed still differ in mean and std"""
+    return x * (1.0 + j / 8.0)
+
+
+def nonfinite_inputs():
+    """a chain that never left the outside of the bounds (lp = -inf throughout), one such cell, one NaN cell"""
+    a, b, c = (ar1(40, 8, 0.5, 0) for _ in range(3))
+    a[:, 0:4] = -np.inf
+    b[3, 2] = -np.inf
+    c[3, 2] = np.nan
+    return [(("-inf chains",), a), (("-inf cell",), b), (("nan cell",), c)]
 
 
 def _pairs_numpy(x, max_lag=0):
@@ -162,13 +275,14 @@ def test_restatement_rhat_equals_chains_rhat(demc):
 
 
 def _close(a, b, rtol):
-    return (math.isnan(a) and math.isnan(b)) or abs(a - b) <= rtol * abs(b)
+    return a == b or (math.isnan(a) and math.isnan(b)) or abs(a - b) <= rtol * abs(b)
 
 
 @pytest.mark.parametrize("max_lag", [0, 5, 16])
 def test_summarystats_equals_the_restatement(demc, max_lag):
     cases = list(_small_inputs()) + [(("edge", n), ar1(n, 3, 0.5, 7)) for n in (1, 2, 3, 7, 8, 9)]
     cases.append((("const",), np.full((40, 3), 2.5)))
+    cases += nonfinite_inputs()
     for key, x in cases:
         val = np.stack([x, 2.0 - x], axis=1)  # two series
         ch = demc.Chains(val, ["a", "b"], ["a", "b"], internals=())
@@ -186,6 +300,63 @@ def test_summarystats_equals_the_restatement(demc, max_lag):
         assert set(d["a"]) == {"mean", "std", "rhat", "ess", "mcse", "pairs"}
     c = restate(np.full((40, 3), 2.5))
     assert c["std"] == 0.0 and math.isnan(c["rhat"]) and math.isnan(c["ess"]) and math.isnan(c["mcse"])
+
+
+@pytest.mark.parametrize("max_lag", [0, 5, 16])
+def test_vectorised_restatement_equals_the_plain_loops(max_lag):
+    """restate_np (the reference of the large GPU cases) against restate: numbers to rtol 1e-12, the bar between two host forms
+    above; `pairs` and the NaN pattern of every column and of rho exactly"""
+    cases = list(_small_inputs()) + [(("edge", n), ar1(n, 3, 0.5, 7)) for n in (1, 2, 3, 7, 8, 9)]
+    cases.append((("const",), np.full((40, 3), 2.5)))
+    cases += nonfinite_inputs()
+    worst = 0.0
+    for key, x in cases:
+        a, b = restate_np(x, max_lag, 70), restate(x, max_lag, 70)
+        assert set(a) == set(b)
+        for col in ("mean", "std", "rhat", "ess", "mcse"):
+            assert type(a[col]) is float and math.isnan(a[col]) == math.isnan(b[col]), (key, col, a[col], b[col])
+            assert _close(a[col], b[col], 1e-12), (key, col, a[col], b[col])
+            if math.isfinite(b[col]) and b[col] != 0:
+                worst = max(worst, abs(a[col] - b[col]) / abs(b[col]))
+        assert a["pairs"] == b["pairs"], key
+        assert (a["pmin"] is None) == (b["pmin"] is None) and (b["pmin"] is None or _close(a["pmin"], b["pmin"], 1e-9)), key
+        ra, rb = np.array(a["rho"]), np.array(b["rho"])
+        assert np.array_equal(np.isnan(ra), np.isnan(rb)), (key, ra, rb)
+        np.testing.assert_allclose(ra, rb, rtol=1e-12, atol=1e-12)
+    print(f"restate_np against restate, max_lag={max_lag}: max relative difference {worst:.3g}")
+    for key, x in nonfinite_inputs():  # what the definition gives for them, said once
+        r = restate_np(x, max_lag, 70)
+        assert (math.isnan(r["mean"]) if key == ("nan cell",) else r["mean"] == -math.inf), key
+        assert all(math.isnan(r[col]) for col in ("std", "rhat", "ess", "mcse")) and r["pairs"] == 0.0 and r["pmin"] is None, key
+        assert r["rho"][0] == 1.0 and np.isnan(r["rho"][1:]).all() and restate(x, max_lag, 70)["rho"][0] == 1.0, key
+
+
+def _header_constants():
+    import os
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    text = open(os.path.join(root, "differentialevolutionmcmc.jl_amd", "csrc", "demc_summary.hpp")).read()
+    vals = {}
+    for name, expr in re.findall(r"constexpr\s+\w+\s+(kSum\w+)\s*=\s*([^;]+);", text):
+        expr = expr.replace("(size_t)", "")
+        assert re.fullmatch(r"[0-9\s*<()+]+", expr), (name, expr)
+        vals[name] = eval(expr)  # (digits, *, <<, + and brackets only)
+    return vals
+
+
+def test_geometry_constants_are_the_headers():
+    c = _header_constants()
+    want = dict(kSumLagBlock=SUM_LAG_BLOCK, kSumMaxJT=SUM_MAX_JT, kSumMaxWorkers=SUM_MAX_WORKERS, kSumLdsSmall=SUM_LDS_SMALL,
+                kSumLdsMax=SUM_LDS_MAX, kSumGlobalTile=SUM_GLOBAL_TILE)
+    for name, v in want.items():
+        assert c[name] == v, (name, c.get(name), v)
+    assert LAG_BLOCK == SUM_LAG_BLOCK
+    # ... and the rule, at the sizes the header's comments and DESIGN.md 5.5 name
+    assert [geometry(n, 4, 1)["mode"] for n in (8064, 8065, 18304, 18305)] == ["lds64", "lds144", "lds144", "global"]
+    assert geometry(200, 8, 2) == dict(mode="lds64", JT=4, tiles=[4], workers=8, chains_per_worker_max=1, lag_blocks=2)
+    assert geometry(1000, 4096, 32)["JT"] == 7 and geometry(1000, 4096, 32)["tiles"] == [7, 7, 7, 7, 6]
+    assert geometry(1000, 4096, 32)["workers"] == 1024 and geometry(1000, 4096, 32)["chains_per_worker_max"] == 4
+    assert geometry(1, 3, 1)["lag_blocks"] == 0 and geometry(130, 3, 1)["lag_blocks"] == 2 and geometry(128, 3, 1)["lag_blocks"] == 1
 
 
 @pytest.mark.parametrize("phi", [0.0, 0.5, 0.9])
@@ -210,6 +381,19 @@ def test_no_synthetic_input_sits_on_a_zero_pair():
                 worst = min(worst, min(abs(p) for p in ps))
                 assert min(abs(p) for p in ps) >= MARGIN, (n, m, phi, seed, max_lag)
     print(f"smallest |P_k| over the synthetic inputs: {worst:.3g}")
+    # the inputs of the large GPU cases: the new lag caps on the slow-mixing case, max_lag = 0 on the others -- each as it is and
+    # with the factors its series are scaled by
+    for key in list(LARGE_MAX_LAGS) + AR1_LARGE:
+        worst = math.inf
+        for seed in SEEDS:
+            x = ar1(*key, seed)
+            for max_lag in LARGE_MAX_LAGS.get(key, (0,)):
+                for j in {0} | set(range(seed, LARGE_SCALED.get(key, 0), len(SEEDS))):  # series j is fed seed j % 3
+                    ps = _pairs_numpy(scaled(x, j), max_lag)
+                    assert ps, (key, seed)
+                    worst = min(worst, min(abs(p) for p in ps))
+                    assert min(abs(p) for p in ps) >= MARGIN, (key, seed, max_lag, j)
+        print(f"smallest |P_k| of {key}: {worst:.3g}")
     # ... and the numpy form used here names the same pairs as the restatement
     x = ar1(*AR1_CASES[1], 0)
     r = restate(x)
