@@ -100,8 +100,10 @@ def teacher_forced(demc, orc, prob, n_iter, n_initial=0, masks=None, check_hist=
         assert np.array_equal(hg[1][n_initial:], ho[1][n_initial:])  # accept flags
         np.testing.assert_allclose(hg[0], ho[0], rtol=1e-11, atol=1e-13)
         np.testing.assert_allclose(hg[2][n_initial:], ho[2][n_initial:], rtol=_rtol(prob))
+    ran = eng.last_kernels()
     eng.close()
     o.close()
+    return ran
 
 
 FAMILIES = ["gaussian", "binomial", "mvn_iso", "mvn_full", "hier_binomial", "hier_gaussian", "lba", "lnr"]
