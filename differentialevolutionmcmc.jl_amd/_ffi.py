@@ -28,6 +28,8 @@ EXPORTS = [
     "demc_set_model_sim",
 ]
 SUMMARY_EXPORTS = ["demc_summarize"]  # include/demc_summary.h: the header next to demc.h (what follows a run)
+QUANTILE_EXPORTS = ["demc_quantiles"]  # include/demc_quantile.h: the second table of describe(chains)
+QUANTILE_MAX_PROBS = 16  # DEMC_QUANTILE_MAX_PROBS
 COMM_ID_BYTES = 128
 _NOT_STATUS = {"demc_last_error": C.c_char_p, "demc_multi_last_error": C.c_char_p, "demc_multi_shard": C.c_void_p}
 
@@ -143,6 +145,7 @@ def load():
     L.demc_get_history.argtypes = [H, C.c_int64, C.c_int64, _dp, _bp, _dp, _lp]
     L.demc_export_chains.argtypes = [H, C.c_int64, C.c_int64, C.c_int32, _dp]
     L.demc_summarize.argtypes = [H, C.c_int64, C.c_int64, C.c_int32, _dp, _dp, C.c_int64]
+    L.demc_quantiles.argtypes = [H, C.c_int64, C.c_int64, _dp, C.c_int32, _dp]
     L.demc_step.argtypes = [H, C.c_int64, C.c_int32]
     L.demc_update.argtypes = [H, C.c_int64, C.c_int32]
     L.demc_migration_due.argtypes = [C.POINTER(DemcConfig), C.c_int64]
@@ -175,7 +178,7 @@ def load():
     L.demc_multi_size.argtypes = [H]
     L.demc_multi_shard.argtypes = [H, C.c_int32]
     L.demc_multi_step.argtypes = [H, C.c_int64, C.c_int32]
-    for name in EXPORTS + SUMMARY_EXPORTS:  # every entry point returns an int32 status, except the error strings and the shard accessor
+    for name in EXPORTS + SUMMARY_EXPORTS + QUANTILE_EXPORTS:  # every entry point returns an int32 status, except the error strings and the shard accessor
         getattr(L, name).restype = _NOT_STATUS.get(name, C.c_int32)
     _lib = L
     return L
@@ -353,6 +356,14 @@ class HipEngine:
         rho = np.empty((self.D + 2, rho_len)) if rho_len > 0 else None
         self._ck(self.L.demc_summarize(self.h, row0, row1, max_lag, _d(out), _d(rho), rho_len))
         return out, rho
+
+    def quantiles(self, row0, row1, probs):
+        """quantiles of history rows [row0,row1) selected on the device (demc_quantiles of include/demc_quantile.h),
+        chains pooled -> out[D+2][len(probs)], equal to chains.series_quantiles of the exported rows bit for bit"""
+        probs = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+        out = np.empty((self.D + 2, len(probs)))
+        self._ck(self.L.demc_quantiles(self.h, row0, row1, _d(probs), len(probs), _d(out)))
+        return out
 
     def step(self, iter0, n_iters=1):
         self._ck(self.L.demc_step(self.h, iter0, n_iters))

@@ -1,21 +1,28 @@
 """Minimal stand-in for MCMCChains.Chains: value array (iterations x parameters x chains) + names, and the
 summary statistics the reference's tests read from describe(chains)[1] (:mean, :std, :rhat), plus the effective sample size,
 its Monte-Carlo standard error and the autocorrelation MCMCChains adds to them (DESIGN.md section 5.5 is the definition; the device
-computes the same numbers from the history without exporting it: demc_summarize)."""
+computes the same numbers from the history without exporting it: demc_summarize), and the quantile table of describe(chains)
+(demc_quantiles on the device)."""
+import math
+
 import numpy as np
 
 SUMMARY_COLS = ("mean", "std", "rhat", "ess", "mcse", "pairs")  # the columns of demc_summarize's out (DEMC_SUMMARY_COLS)
+DEFAULT_QUANTILES = (0.025, 0.25, 0.5, 0.75, 0.975)  # MCMCChains' describe(chains)[2]
 
 
 class Summary:
     """The summary table of a run: `values[j]` = (mean, std, rhat, ess, mcse, pairs) of series names[j] -- the parameters,
-    then acceptance and lp.  `rho` (or None): [series][lags] autocorrelations, NaN beyond the lags that were evaluated."""
+    then acceptance and lp.  `rho` (or None): [series][lags] autocorrelations, NaN beyond the lags that were evaluated.
+    `quantiles` (or None): [series][len(probs)] quantiles at `probs`, chains pooled."""
 
-    def __init__(self, names, values, internals=("acceptance", "lp"), rho=None):
+    def __init__(self, names, values, internals=("acceptance", "lp"), rho=None, quantiles=None, probs=None):
         self.names = list(names)
         self.values = np.asarray(values, dtype=np.float64).reshape(len(self.names), len(SUMMARY_COLS))
         self.internals = list(internals)
         self.rho = rho
+        self.probs = None if quantiles is None else tuple(float(q) for q in probs)
+        self.quantiles = None if quantiles is None else np.asarray(quantiles, dtype=np.float64).reshape(len(self.names), len(self.probs))
 
     def __getitem__(self, name):
         return dict(zip(SUMMARY_COLS, (float(v) for v in self.values[self.names.index(name)])))
@@ -23,6 +30,53 @@ class Summary:
     def describe(self):
         """per parameter name the dict Chains.describe() gives (mean, std, rhat), extended by ess, mcse and pairs"""
         return {nm: self[nm] for nm in self.names if nm not in self.internals}
+
+    def quantile(self):
+        """per parameter name {q: value} at the probs the run was summarised with: what Chains.quantile(probs) gives"""
+        if self.quantiles is None:
+            raise ValueError("this Summary holds no quantiles: summarize(..., quantiles=DEFAULT_QUANTILES)")
+        return {nm: dict(zip(self.probs, (float(v) for v in self.quantiles[j])))
+                for j, nm in enumerate(self.names) if nm not in self.internals}
+
+
+_SIGN, _ALL = np.uint64(1 << 63), np.uint64(0xFFFFFFFFFFFFFFFF)
+_KEY_NEG_INF, _KEY_POS_INF = np.uint64(0x000FFFFFFFFFFFFF), np.uint64(0xFFF0000000000000)  # NaNs are the keys beyond them
+
+
+def series_quantiles(x, probs):
+    """DESIGN.md 5.6 for one series on the host: x (any shape; the chains are pooled) -> the quantiles at probs, Julia's default
+    (type 7) on the values ordered by their keys, to the operation -- what demc_quantiles selects on the device, bit for bit"""
+    b = np.ascontiguousarray(x, dtype=np.float64).reshape(-1).view(np.uint64)
+    N = b.size
+    if N < 1:
+        raise ValueError("series_quantiles needs at least one value")
+    k = np.sort(b ^ np.where(b >> np.uint64(63) != 0, _ALL, _SIGN))
+    out = np.full(len(probs), float("nan"))
+    if k[0] < _KEY_NEG_INF or k[-1] > _KEY_POS_INF:  # a NaN in the pool
+        return out
+    v = (k ^ np.where(k >> np.uint64(63) != 0, _SIGN, _ALL)).view(np.float64)  # x_(1) <= ... <= x_(N)
+    with np.errstate(all="ignore"):
+        for i, p in enumerate(probs):
+            p = float(p)
+            if not 0.0 <= p <= 1.0:
+                raise ValueError("a prob is outside [0, 1]")
+            if N == 1:
+                out[i] = v[0]
+                continue
+            aleph = float(N) * p + (1.0 - p)
+            j = max(1, min(int(math.trunc(aleph)), N - 1))
+            g = min(1.0, max(0.0, aleph - j))
+            a, c = float(v[j - 1]), float(v[j])
+            if math.isfinite(a) and math.isfinite(c):
+                d = np.float64(c) - np.float64(a)  # (numpy scalars: an overflow is an inf by IEEE, not an exception)
+                out[i] = np.float64(a) + np.float64(g) * d
+            elif g == 0.0:
+                out[i] = a
+            elif g == 1.0:
+                out[i] = c
+            else:
+                out[i] = np.float64(1.0 - g) * np.float64(a) + np.float64(g) * np.float64(c)
+    return out
 
 
 def series_summary(x, max_lag=0, rho_len=0):
@@ -115,6 +169,12 @@ class Chains:
 
     def mean(self):
         return {k: v["mean"] for k, v in self.describe().items()}
+
+    def quantile(self, q=DEFAULT_QUANTILES):
+        """per parameter name {q: value}, the chains pooled as MCMCChains' quantile(chains) pools them"""
+        q = tuple(float(v) for v in q)
+        return {nm: dict(zip(q, (float(v) for v in series_quantiles(self.value[:, j, :], q))))
+                for j, nm in enumerate(self.names) if nm not in self.internals}
 
     def summarystats(self, max_lag=0, rho_len=0):
         """The Summary of this object computed on the host (numpy): what demc_summarize computes on the device for a history that

@@ -10,6 +10,7 @@
 // There is NO CPU fallback in this file: every compute entry point launches HIP kernels or fails.
 #include "../../include/demc.h"
 #include "../../include/demc_summary.h"  // demc_summarize
+#include "../../include/demc_quantile.h"  // demc_quantiles
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -41,6 +42,7 @@
 #define DEMC_ODE_EXTERN  // k_ode_loglike in demc_ode.cpp
 #include "demc_ode.hpp"
 #include "demc_summary.hpp"  // demc_summarize: its kernels and their launches live in demc_summary.cpp
+#include "demc_quantile.hpp"  // demc_quantiles: likewise, demc_quantile.cpp
 #include "demc_instances.hpp"  // one table per templated kernel, built from the lists above: every choice of an instance goes through them
 
 using namespace demc;
@@ -2232,6 +2234,24 @@ int32_t demc_summarize(demc_handle* h, int64_t row0, int64_t row1, int32_t max_l
               h->c.D, h->hist_ld, (int)max_lag};
     std::string msg;
     const int rc = summary_run(a, h->stream, out, rho_out && rho_len > 0 ? rho_out : nullptr, (long long)rho_len, msg);
+    return rc == DEMC_OK ? DEMC_OK : fail(h, rc, msg);
+    });
+}
+
+int32_t demc_quantiles(demc_handle* h, int64_t row0, int64_t row1, const double* probs, int32_t n_probs, double* out) {
+    return guarded(h, [&]() -> int32_t {
+    if (!h || !out || !probs) return DEMC_EINVAL;
+    USE_DEVICE(h);
+    if (!h->hist) return fail(h, DEMC_EINVAL, "history is not stored on this handle");
+    if (row0 < 0 || row1 - row0 < 1 || row1 > h->c.n_rows) return fail(h, DEMC_EINVAL, "bad rows: demc_quantiles needs at least one row of the history");
+    if (n_probs < 1 || n_probs > DEMC_QUANTILE_MAX_PROBS) return fail(h, DEMC_EINVAL, "demc_quantiles: n_probs must be in 1 .. 16");
+    for (int k = 0; k < n_probs; ++k)
+        if (!(probs[k] >= 0.0 && probs[k] <= 1.0)) return fail(h, DEMC_EINVAL, "demc_quantiles: a prob is outside [0, 1]");
+    if (h->c.n_groups_total != h->c.n_groups)
+        return fail(h, DEMC_EINVAL, "sharded handle: gather demc_get_history from every rank and take the quantiles on the host");
+    QArgs a{h->hist, h->acc_hist, h->lp_hist, h->P, (long long)row0, (long long)row1, h->c.D, h->hist_ld};
+    std::string msg;
+    const int rc = quantile_run(a, h->stream, probs, (int)n_probs, out, msg);
     return rc == DEMC_OK ? DEMC_OK : fail(h, rc, msg);
     });
 }

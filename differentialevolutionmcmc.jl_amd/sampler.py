@@ -3,7 +3,7 @@ C-ABI engine.  The per-iteration work -- step!/pstep! (main.jl:84-107) -- happen
 import numpy as np
 
 from . import _ffi
-from .chains import Chains, Summary
+from .chains import Chains, Summary, series_quantiles
 from .families import PRIOR_NORMAL_REF, Priors, SimulatedLikelihood, SourceLikelihood
 from .structs import (DE, HIPBackend, LOGLIKE_MODES, MCMCThreads, SCHEDULES, DEModel, Particle, maximize)
 
@@ -221,8 +221,12 @@ def _run(model, de, n_iter, backend, progress, engine_factory, summary=None):
             print()
         de.iter = n_iter + de.n_initial
         n_rows = n_iter + de.n_initial
-        if summary is not None and hasattr(eng, "summarize"):  # summarize(): the statistics on the device, no export at all
-            return lay, eng.summarize(summary[0], summary[1], summary[2])[0], None
+        if summary is not None and hasattr(eng, "summarize") and (len(summary) < 4 or summary[3] is None or hasattr(eng, "quantiles")):
+            # summarize(): the statistics (and the quantiles, when asked for) on the device, no export at all
+            stats = eng.summarize(summary[0], summary[1], summary[2])[0]
+            if len(summary) < 4 or summary[3] is None:
+                return lay, stats, None
+            return lay, (stats, eng.quantiles(summary[0], summary[1], summary[3])), None
         if hasattr(eng, "export_chains"):  # device-side re-key + layout (demc_export_chains)
             full = eng.export_chains(0, n_rows)  # [n_rows][D+2][P] by particle id
         else:  # engines without it (the CPU oracle injected by tests): re-key on the host
@@ -243,19 +247,30 @@ def sample(model, de, *args, progress=False, engine_factory=None, **kwargs):
     return bundle_samples(model, de, lay, full, n_iter)
 
 
-def summarize(model, de, *args, max_lag=0, progress=False, engine_factory=None, **kwargs):
-    """summarize(model, de, [HIPBackend(...)], n_iter, max_lag=0): the run of sample() followed by the summary statistics of
-    the rows bundle_samples keeps (offset = burnin or 0, quirk q1 included) -- computed on the device by demc_summarize, so that
-    the history is never exported.  Returns a Summary (chains.py); equal to sample(...).summarystats(max_lag) for the same seed.
-    An engine without summarize (an injected one) exports as sample() does and summarises on the host."""
+def summarize(model, de, *args, max_lag=0, quantiles=None, progress=False, engine_factory=None, **kwargs):
+    """summarize(model, de, [HIPBackend(...)], n_iter, max_lag=0, quantiles=None): the run of sample() followed by the summary
+    statistics of the rows bundle_samples keeps (offset = burnin or 0, quirk q1 included) -- computed on the device by
+    demc_summarize, so that the history is never exported.  Returns a Summary (chains.py); equal to
+    sample(...).summarystats(max_lag) for the same seed.  quantiles: a tuple of probs (chains.DEFAULT_QUANTILES) -- the same run
+    also selects those quantiles of the kept rows on the device (demc_quantiles) and the Summary carries them: Summary.quantile()
+    equals sample(...).quantile(probs).  An engine without summarize or quantiles (an injected one) exports as sample() does and
+    computes on the host."""
     backend, n_iter = _parse(args)
     Ns = n_iter - de.burnin if de.discard_burnin else n_iter
     offset = de.burnin if de.discard_burnin else 0
-    lay, res, state = _run(model, de, n_iter, backend, progress, engine_factory, summary=(offset, offset + Ns, max_lag))
+    probs = None if quantiles is None else tuple(float(q) for q in quantiles)
+    lay, res, state = _run(model, de, n_iter, backend, progress, engine_factory, summary=(offset, offset + Ns, max_lag, probs))
     if state is None:
         names = get_names(model, lay["shapes"])
-        return Summary(names, res)
-    return bundle_samples(model, de, lay, res, n_iter).summarystats(max_lag)
+        if probs is None:
+            return Summary(names, res)
+        return Summary(names, res[0], quantiles=res[1], probs=probs)
+    chains = bundle_samples(model, de, lay, res, n_iter)
+    out = chains.summarystats(max_lag)
+    if probs is not None:
+        out.probs = probs
+        out.quantiles = np.stack([series_quantiles(chains.value[:, j, :], probs) for j in range(len(chains.names))])
+    return out
 
 
 def optimize(model, de, *args, progress=False, engine_factory=None, **kwargs):

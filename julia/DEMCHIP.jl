@@ -276,6 +276,8 @@ end
 
 # describe(chains) on the device (include/demc_summary.h): `summarize`, in a file of its own like the header it binds
 include("DEMCHIPSummary.jl")
+# ... and its quantile table (include/demc_quantile.h): `quantiles`, likewise
+include("DEMCHIPQuantile.jl")
 
 "final state of the particle objects behind handle `h` (bundle_samples reads accept/lp from them; Θ for completeness)"
 function pull_state!(h, particles, Pl, D, shapes, lens, offs)
