@@ -60,6 +60,42 @@ struct Timed {
     bool started = false;  // a kernel of the bracket carries the events (LAUNCH_T)
 };
 
+// The kernel forms that can carry an update.  FORM_PHASE -- a K1 [-> K2 -> K3] chain per sweep and colour phase, k_longrow and
+// k_frozen_sweep beneath it -- serves every configuration and is planned per launch (launch_phase).  The others run whole updates
+// in one launch: planned once per model into a FormPlan (size_k1_lds), chosen per step (choose_form), launched by launch_form.
+enum Form {
+    FORM_PHASE,
+    FORM_RESIDENT,        // k_propose<..., RES>: the group in LDS, both colour phases of several iterations
+    FORM_STREAM,          // k_propose<..., RES, LEAN, STREAM>: ... with the MvNormal observation stream inside
+    FORM_LEAN_SUFFSTAT,   // k_res_mvn<WG, false, DT>: the default sampler on MvNormal-full (demc_resmvn.hpp)
+    FORM_LEAN_STREAMING,  // k_res_mvn<WG, true, DT>
+    FORM_LEAN_DIRECT,     // k_res_mvn<WG, true, DT, direct>
+    FORM_LEAN_OBS,        // k_res_obs: the default sampler on the per-observation families (demc_resobs.hpp)
+    FORM_LEAN_Z,          // k_res_mvn<WG, false, DT, HIST>: DE-MC_Z, one iteration per launch
+    N_FORMS
+};
+// a group's observations in chunks, a workgroup each, which spin on each other's progress: the whole grid must be resident at once
+constexpr bool spin_waiting(Form f) { return f == FORM_STREAM || f == FORM_LEAN_STREAMING || f == FORM_LEAN_DIRECT; }
+
+struct FormPlan {
+    bool ok = false;           // the form serves this model and configuration
+    // the instance(s), resolved when the model is planned (a missing one fails there, not at step 1): per LEAN level for the two
+    // k_propose forms (a trace or a replay lowers it to 0 at run time: lean_level), per HIST - 1 for FORM_LEAN_Z, else [0]
+    const K1Inst* k1[3] = {};
+    int wg = 0;                // workgroup size
+    size_t lds = 0;            // dynamic LDS bytes
+    int lpp = 0, scr_doubles = 0;  // k_propose forms: lanes per particle, doubles of the theta' scratch
+};
+
+// Geometry of the observation stream inside a resident kernel (plan_stream), shared by the spin-waiting forms: a handle runs in one
+// likelihood mode, so at most one of FORM_STREAM / FORM_LEAN_STREAMING (STREAMING) and FORM_LEAN_DIRECT (DIRECT) reads it.
+struct StreamGeo {
+    bool ok = false;
+    int C = 0, nact_max = 0, rows = 0, x_lds = 0, chunk_tiles = 0;  // chunks per group, moving particles, scratch rows, X chunk in LDS, tiles per chunk
+    unsigned long long* gran = nullptr;  // hand-over granules (device), [2][n_groups][C][nact_max][2]
+    unsigned* err = nullptr;             // time-out flag (host-mapped, zero-copy)
+};
+
 }  // namespace
 
 struct demc_handle {
@@ -121,14 +157,8 @@ struct demc_handle {
     int tile_in_lds = 0;
     size_t k1_lds = 0, k1_tile_bytes = 0, k1_scr_bytes = 0;
     bool hier_scr = false;  // hierarchical family whose theta' scratch fits in LDS
-    bool res_ok = false;  // resident K1 (plan_resident)
-    int res_lpp = 0, res_wg = 0, res_scr_doubles = 0;
-    size_t res_lds = 0;
-    // the instances whose template arguments are fixed by the model, resolved when it is planned (a missing one fails there, not at
-    // step 1); the general resident forms per LEAN level (which a trace or a replay lowers to 0 at run time: lean_level)
-    const K1Inst *res_k1[3] = {}, *st_k1[3] = {}, *lean_k1 = nullptr, *lean_obs_k1 = nullptr;
-    // streaming-resident form (plan_stream): the MvNormal observation stream inside the resident kernel
-    bool st_ok = false;
+    FormPlan form[N_FORMS];  // the whole-update forms (size_k1_lds plans them; [FORM_PHASE] is not used)
+    StreamGeo st;
     bool tf_cheap_obs = false;  // set_tail_flags' "the likelihood is cheap enough for K1" of the last call (launch_phase reads it)
     // k_frozen_sweep: launch order of the groups per (iteration, block sweep) of the current demc_step call -- groups whose
     // mutation coin fires (main.jl:199-207) first: their workgroups move the whole row and take twice as long, and a slow
@@ -145,23 +175,11 @@ struct demc_handle {
     hipEvent_t frozen_order_ev = nullptr;   // the last copy out of the staging buffer has been consumed
     long long frozen_iter0 = 0;
     int frozen_iters = 0;
-    int st_C = 0, st_nact_max = 0, st_rows = 0, st_x_lds = 0, st_chunk_tiles = 0, st_lpp = 0, st_scr_doubles = 0, st_wg = 512;
-    size_t st_lds = 0;
-    unsigned long long* st_gran = nullptr;  // hand-over granules (device)
-    unsigned* st_err = nullptr;             // time-out flag (host-mapped, zero-copy)
     int n_cus = 0;
     bool bracket_open = false;  // timing: between tick(begin) and tick(end) of a bracket whose kernels carry the events
     size_t lr_two_lds = 0;     // long-row kernel: the dynamic LDS size lr_two_fit was asked for
     bool lr_two_fit = false;   // ... two 256-thread workgroups with that much LDS fit on a CU
     int ainv_lds = 1;
-    // lean resident kernel of the default sampler on MvNormal-full (demc_resmvn.hpp): geometry for SUFFSTAT / STREAMING
-    bool lean_ok = false, lean_stream_ok = false, lean_hist_ok = false;  // (lean_hist: DE-MC_Z past burn-in, k_res_mvn<..., HIST>)
-    bool st_dir_geo = false;   // plan_stream's geometry is valid for the DIRECT likelihood (k_res_mvn<..., DIR>; st_ok stays false)
-    bool lean_direct_ok = false;  // ... and the lean kernel's DIRECT streaming-resident instance serves this model
-    bool lean_obs_ok = false;  // lean resident kernel of the default sampler on the per-observation families (demc_resobs.hpp)
-    size_t lean_obs_lds = 0;
-    int lean_wg = 0;
-    size_t lean_lds = 0, lean_stream_lds = 0, lean_hist_lds = 0;
     // update of a subset of the groups (demc_update_groups_async): two device lists used alternately, and the one in force
     // Each call takes the next of kGlistRing slots: a pinned host copy of the list, a device copy, and an event that marks
     // the host copy as consumed.  The device copy is refilled by a copy ON THE HANDLE'S STREAM, i.e. behind every kernel that
@@ -711,25 +729,51 @@ void set_tail_flags(demc_handle* h, KParams& k) {
     k.fuse_accept = (((k.fuse_prep && suff) || k.fuse_obs) && c.fuse != 1 && phase_private) ? 1 : 0;
     k.write_prop = (!k.fuse_accept || k.trace) ? 1 : 0;
 }
-// the default sampler and nothing else: K1 has an instance with every other branch compiled out
-int lean_level(const demc_handle* h, const KParams& k) {
+// The default sampler and nothing else, with partners of `partner_kind`: the kernels have instances with every other branch compiled
+// out.  1: the default sampler; 2: + snooker updates / block updates, their own lean instance; 0: anything else -- a trace and a
+// replay among it -- takes the general instance.
+// (DEMC_PARTNER_HISTORY is DE-MC_Z, sample = resample, crossover.jl:113-124: partners are cells of the history, so there is no tile,
+// and the lean instances of the no-tile form serve it -- the reference's own DE-MC_Z runs use theta_snooker = 0.1,
+// test/multivariate_normal_tests.jl:50-59, Examples/Hierarchical_Example.jl:103-114)
+int lean_level(const demc_handle* h, int partner_kind, int mode = MODE_STEP) {
     const demc_config& c = h->c;
-    const bool base = k.mode == MODE_STEP && c.proposal_kind == 0 && c.partner_kind == DEMC_PARTNER_CURRENT && c.update_kind == 0 &&
-                      c.fitness_kind == 0 && c.kappa == 1.0 && !k.trace && !h->rp_active;
-    return !base ? 0 : (c.theta_snooker == 0.0 && c.n_blocks == 0) ? 1 : 2;  // + snooker / block updates: their own lean instance
-}
-bool is_plain(const demc_handle* h, const KParams& k) { return lean_level(h, k) == 1; }
-// DE-MC_Z (sample = resample, crossover.jl:113-124) with the rest of the sampler at its defaults: partners are cells of the
-// history, so there is no tile, and the plain instance of the no-tile form serves it
-// (1: the default sampler; 2: + snooker updates / block updates -- the reference's own DE-MC_Z runs use theta_snooker = 0.1,
-// test/multivariate_normal_tests.jl:50-59, Examples/Hierarchical_Example.jl:103-114; 0: the general instance)
-int lean_hist(const demc_handle* h, const KParams& k) {
-    const demc_config& c = h->c;
-    const bool base = k.mode == MODE_STEP && c.proposal_kind == 0 && c.partner_kind == DEMC_PARTNER_HISTORY && c.update_kind == 0 &&
-                      c.fitness_kind == 0 && c.kappa == 1.0 && !k.trace && !h->rp_active;
+    const bool base = mode == MODE_STEP && c.proposal_kind == 0 && c.partner_kind == partner_kind && c.update_kind == 0 &&
+                      c.fitness_kind == 0 && c.kappa == 1.0 && !c.trace && !h->rp_active;
     return !base ? 0 : (c.theta_snooker == 0.0 && c.n_blocks == 0) ? 1 : 2;
 }
 int tail_of(const KParams& k) { return k.prep_mfma ? TAIL_PREP_MFMA : k.fuse_prep ? TAIL_PREP : k.fuse_obs ? TAIL_OBS : TAIL_NONE; }
+
+// one launch in the K1 slot, inside its timing bracket; demc_last_kernels names the instance
+void launch_k1(demc_handle* h, const K1Inst* e, unsigned grid, int wg, size_t lds, const KParams& k) {
+    h->last = demc_handle::LastPlan{e};
+    tick(h, 0, true);
+    LAUNCH_T(h, e->fn, dim3(grid), dim3(wg), lds, k);
+    tick(h, 0, false);
+}
+
+// {scalars inside the block, its longest run} of a block mask in run-length form (demc_handle::MaskRuns / KParams::mrun_*)
+struct BlockSpan { int inside = 0, longest = 0; };
+BlockSpan block_span(int n_run, unsigned in, const int* start, int D) {
+    BlockSpan s;
+    for (int r = 0; r < n_run; ++r)
+        if ((in >> r) & 1u) {
+            const int len = (r + 1 < n_run ? start[r + 1] : D) - start[r];
+            s.inside += len;
+            s.longest = std::max(s.longest, len);
+        }
+    return s;
+}
+
+// Whether this configuration can take the frozen-row sweep (k_frozen_sweep) at all: a blocked hierarchical family with long rows,
+// the whole update fused, no trace, no recombination, and enough moving particles -- counted on the geometry's groups, so that a
+// shard takes the form of the whole run -- for two workgroups per CU.  launch_phase refines it per sweep (the block's scalars, the
+// phase's own particle count and pool); plan_frozen_order and plan_snap2 prepare nothing where it says no.
+bool frozen_possible(const demc_handle* h) {
+    const demc_config& c = h->c;
+    const int n_act = c.schedule == DEMC_SCHED_TWO_COLOUR ? c.Np - c.Np / 2 : c.schedule == DEMC_SCHED_SEQUENTIAL ? 1 : c.Np;
+    return (h->family == FAM_HIER_BINOMIAL || h->family == FAM_HIER_GAUSSIAN) && h->hier_scr && h->lpp > 64 && c.n_blocks >= 1 &&
+           c.fuse == 0 && !c.trace && c.kappa == 1.0 && (long long)h->geo_groups * n_act >= 2LL * h->n_cus;
+}
 
 // (`k` by value: the frozen-sweep / snapshot overrides below -- glist, base_*, snap_*, the fuse flags -- stay inside this launch;
 // run_sweep reuses its own copy for the second colour phase and for every particle of the sequential schedule)
@@ -804,25 +848,16 @@ int launch_phase(demc_handle* h, KParams k) {
     // <256,big>: 155; demc_frozen.hpp) -- instead of
     // the subject-sweep machinery of k_longrow at eight waves per CU.  Partners from the population or from the history, the
     // base row from the sweep-start snapshot when there is one.
-    if (lr_shape && k.fuse_obs && k.fuse_accept && k.mask && k.n_mrun > 0 && !k.trace &&
-        (h->family == FAM_HIER_BINOMIAL || h->family == FAM_HIER_GAUSSIAN) && c.kappa == 1.0 && k.pool_n <= 256) {
-        int inside = 0;
-        for (int r = 0; r < k.n_mrun; ++r)
-            if ((k.mrun_in >> r) & 1u) inside += (r + 1 < k.n_mrun ? k.mrun_start[r + 1] : c.D) - k.mrun_start[r];
+    if (frozen_possible(h) && lr_shape && k.fuse_obs && k.fuse_accept && k.mask && k.n_mrun > 0 && k.pool_n <= 256) {
+        const BlockSpan blk = block_span(k.n_mrun, k.mrun_in, k.mrun_start, c.D);
         // (enough moving particles for several workgroups per CU, counted on the geometry's groups so that a shard takes the form
         // of the whole run: with one particle per CU the launch is that particle's dependent prologue whatever follows it --
         // measured on cfg4's share: no form of this kernel beats k_longrow<512> there, profiles/r05/NOTES.md)
-        int longest = 0;
-        for (int r = 0; r < k.n_mrun; ++r)
-            if ((k.mrun_in >> r) & 1u) longest = std::max(longest, (r + 1 < k.n_mrun ? k.mrun_start[r + 1] : c.D) - k.mrun_start[r]);
         // (a long run inside the block -- the subject block -- takes the BIG instance: proposals formed on the fly, four scalars
         // per thread and round behind 16-byte loads, which the hierarchical Binomial family's even rows allow)
-        bool big = longest > 256;
-        bool on = inside >= 1 && (long long)h->geo_groups * k.n_act >= 2LL * h->n_cus;
-        if (big)
-            on = on && h->family == FAM_HIER_BINOMIAL && (c.D & 1) == 0;
-        else
-            on = on && inside <= kFrozenMax;
+        const bool big = blk.longest > 256;
+        const bool on = blk.inside >= 1 && (long long)h->geo_groups * k.n_act >= 2LL * h->n_cus &&
+                        (big ? h->family == FAM_HIER_BINOMIAL && (c.D & 1) == 0 : blk.inside <= kFrozenMax);
         if (on) {
             if (snapshot)
                 if (int rc = take_snapshot(true)) return rc;
@@ -839,10 +874,7 @@ int launch_phase(demc_handle* h, KParams k) {
             }
             const K1Inst* e = nullptr;
             PICK(e, "k_frozen_sweep", kFrozen, 256, 3, 2, big);
-            h->last = demc_handle::LastPlan{e};
-            tick(h, 0, true);
-            LAUNCH_T(h, e->fn, dim3((unsigned)n_prop), dim3(256), 0, k);
-            tick(h, 0, false);
+            launch_k1(h, e, (unsigned)n_prop, 256, 0, k);
             return DEMC_OK;
         }
     }
@@ -864,28 +896,22 @@ int launch_phase(demc_handle* h, KParams k) {
         const int wg_lr = two_per_cu ? 256 : 512;
         const K1Inst* e = nullptr;
         PICK(e, "k_longrow", kLongrow, wg_lr);
-        h->last = demc_handle::LastPlan{e};
-        tick(h, 0, true);
         // persistent: as many workgroups as are resident at once, each takes particles blockIdx.x, + gridDim.x, ... (the
         // row moves of one particle then run inside the span loops of the next: demc_longrow.hpp).  A multiple of 8 keeps
         // a workgroup's particles on its own XCD (the kernel's blockIdx -> group mapping).
         long long grid_lr = (long long)(wg_lr == 512 ? 1 : 2) * h->n_cus;
         if (grid_lr > n_prop || grid_lr < 1) grid_lr = n_prop;
         if ((k.n_groups & 7) == 0 && grid_lr >= 8) grid_lr &= ~7LL;
-        LAUNCH_T(h, e->fn, dim3((unsigned)grid_lr), dim3(wg_lr), lr_lds, k);
-        tick(h, 0, false);
+        launch_k1(h, e, (unsigned)grid_lr, wg_lr, lr_lds, k);
         return DEMC_OK;
     }
     const size_t lds = tile ? lds_tile + (k.plan ? plan_bytes : 0) : h->k1_lds - h->k1_tile_bytes;
     // LEAN: the general instance (0), the default sampler (1), + snooker / block updates (2) -- without a tile for partners from the
-    // history (DE-MC_Z: lean_hist); a 512-thread workgroup per particle (very long rows, no tile) has the general instance only
-    const int lean = (tile && wg == 256) ? lean_level(h, k) : (!tile && wg == 256) ? lean_hist(h, k) : 0;
+    // history (DE-MC_Z); a 512-thread workgroup per particle (very long rows, no tile) has the general instance only
+    const int lean = wg == 256 ? lean_level(h, tile ? DEMC_PARTNER_CURRENT : DEMC_PARTNER_HISTORY, k.mode) : 0;
     const K1Inst* e = nullptr;
     PICK(e, "k_propose", kPropose, wg, tile, tail_of(k), false, lean);
-    h->last = demc_handle::LastPlan{e};
-    tick(h, 0, true);
-    LAUNCH_T(h, e->fn, dim3(k.n_groups * n_split), dim3(wg), lds, k);
-    tick(h, 0, false);
+    launch_k1(h, e, (unsigned)(k.n_groups * n_split), wg, lds, k);
     if (k.fuse_accept) return DEMC_OK;
     int rc = launch_loglike(h, k);
     if (rc != DEMC_OK) return rc;
@@ -896,27 +922,51 @@ int launch_phase(demc_handle* h, KParams k) {
     return DEMC_OK;
 }
 
-// ---- resident form of K1: one workgroup per group, both colour phases of several iterations in one launch ----
-// Decides once per model whether the resident form applies and with which geometry (lanes per particle, workgroup size,
-// LDS bytes).  It needs the fused accept tail (the whole update inside K1), the two_colour schedule (a phase writes only
-// rows nobody reads), partners from the current population, and the whole group + its scratch in LDS.
+// ---- planning the whole-update forms: once per model (size_k1_lds), the lean ones again whenever the prior table changes ----
+
+// lanes per particle of a resident k_propose: as many as let the moving half fill one pass of `budget` threads -- from 4 up to one
+// lane per pair of scalars (fewer than 4 only where the row has fewer pairs)
+int resident_lpp(int n_act, int lpp_max, int budget) {
+    int lpp = 4;
+    while (lpp * 2 <= lpp_max && n_act * lpp * 2 <= budget) lpp *= 2;
+    return lpp > lpp_max ? lpp_max : lpp;
+}
+
+// the prior table has a Normal(a, theta[ref]) entry (hierarchical scale priors), which the lean kernels do not know
+bool has_normal_ref(const demc_handle* h) {
+    for (const DimTab& t : h->h_tab)
+        if (t.kind == PR_NORMAL_REF) return true;
+    return false;
+}
+
+// k_res_mvn's DT: the row length where an instance has it compiled in, else 0.  MvNormal-full: 32 and 8 (cfg3, cfg2) when the prior
+// table is one segment; MvNormal-iso: the row of the reference's own test -- 30 means and sigma -- whose instance reads the table
+// as [one entry for the 30 means | one for sigma]: any other table takes the general row length
+int compiled_row_length(const demc_handle* h) {
+    const int D = h->c.D;
+    if (h->family == FAM_MVN_ISO) return (D == 31 && h->n_seg == 2 && h->seg_start[1] == 30) ? 31 : 0;
+    return (h->n_seg == 1 && (D == 32 || D == 8)) ? D : 0;
+}
+
+// FORM_RESIDENT: one workgroup per group, both colour phases of several iterations in one launch.  It needs the fused accept tail
+// (the whole update inside K1), the two_colour schedule (a phase writes only rows nobody reads), partners from the current
+// population, and the whole group + its scratch in LDS.
 int plan_resident(demc_handle* h) {
     const demc_config& c = h->c;
-    h->res_ok = false;
+    FormPlan& f = h->form[FORM_RESIDENT];
+    f = FormPlan();
     if (c.fuse != 0 || c.schedule != DEMC_SCHED_TWO_COLOUR || c.partner_kind != DEMC_PARTNER_CURRENT || c.Np < 4) return DEMC_OK;
-    int lpp_max = pow2_ceil((c.D + 1) / 2);
+    const int lpp_max = pow2_ceil((c.D + 1) / 2);
     if (lpp_max > 64) return DEMC_OK;
     const int n_act = c.Np - c.Np / 2;
     const size_t D = (size_t)c.D, Np = (size_t)c.Np, d = (size_t)h->d;
     const bool mvn = is_mvn(h->family);
-    // geometry for a thread budget: lanes per particle so that the moving half fills one pass when possible (never below
-    // 4 lanes), workgroup size, LDS bytes; false when the update cannot be fused or the group does not fit
+    // geometry for a thread budget: lanes per particle, workgroup size, LDS bytes; false when the update cannot be fused or the
+    // group does not fit
     int lpp = 0, wg = 0, tail = TAIL_NONE;
     size_t bytes = 0, scr_doubles = 0;
     auto geometry = [&](int budget) -> bool {
-        lpp = 4;
-        while (lpp * 2 <= lpp_max && n_act * lpp * 2 <= budget) lpp *= 2;
-        if (lpp > lpp_max) lpp = lpp_max;
+        lpp = resident_lpp(n_act, lpp_max, budget);
         wg = (n_act * lpp > 256 && budget > 256) ? 512 : 256;
         KParams k = base_params(h);
         k.lpp = lpp;
@@ -934,191 +984,26 @@ int plan_resident(demc_handle* h) {
     // two of them fit in a CU's LDS (measured at 1024 groups x 64: 0.082 -> see DESIGN.md section 6).
     const bool two_per_cu = h->geo_groups > 256 && geometry(256) && bytes <= 75 * 1024;
     if (!two_per_cu && !geometry(512)) return DEMC_OK;
-    for (int lean = 0; lean < 3; ++lean) PICK(h->res_k1[lean], "k_propose", kPropose, wg, true, tail, true, lean);
-    h->res_ok = true; h->res_lpp = lpp; h->res_wg = wg; h->res_lds = bytes; h->res_scr_doubles = (int)scr_doubles;
+    for (int lean = 0; lean < 3; ++lean) PICK(f.k1[lean], "k_propose", kPropose, wg, true, tail, true, lean);
+    f.ok = true; f.wg = wg; f.lds = bytes; f.lpp = lpp; f.scr_doubles = (int)scr_doubles;
     return DEMC_OK;
 }
 
-int launch_resident(demc_handle* h, long long iter0, int n_iters) {
-    const demc_config& c = h->c;
-    KParams k = base_params(h);
-    k.lpp = h->res_lpp;
-    set_tail_flags(h, k);
-    k.iter = iter0; k.n_iters = n_iters; k.n_sweeps = c.n_blocks > 0 ? c.n_blocks : 1;
-    k.mask = c.n_blocks > 0 ? h->masks : nullptr;
-    k.n_rows = h->hist ? c.n_rows : 0;
-    k.n_split = 1; k.exclude_self = 0; k.own_in_pool = 1; k.tile_rows = c.Np; k.tile_in_lds = 1;
-    k.scr_doubles = h->res_scr_doubles;
-    k.plan = (k.lpp >= 4) ? 1 : 0;
-    const K1Inst* e = h->res_k1[lean_level(h, k)];
-    h->last = demc_handle::LastPlan{e};
-    tick(h, 0, true);
-    LAUNCH_T(h, e->fn, dim3(k.n_groups), dim3(h->res_wg), h->res_lds, k);
-    tick(h, 0, false);
-    return DEMC_OK;
-}
-
-// ---- lean resident kernel (demc_resmvn.hpp): default sampler, MvNormal full Sigma, D = d <= 32, one pass per phase ----
-int plan_lean(demc_handle* h) {
-    const demc_config& c = h->c;
-    h->lean_ok = h->lean_stream_ok = h->lean_hist_ok = h->lean_direct_ok = false;
-    // The per-observation families under the default sampler (demc_resobs.hpp): Gaussian, Binomial and the LNR with a handful of
-    // parameters (a lane per scalar of a sixteen-lane particle) and few enough observations for sixteen lanes to walk them; the
-    // group, its scratch rows and -- LNR -- the log Phi(-z) table in LDS.  Whether the SAMPLER is the default one is asked per step
-    // (is_plain: a replay or a trace takes the general kernel).
-    h->lean_obs_ok = false;
-    h->lean_k1 = h->lean_obs_k1 = nullptr;
-    // instances with the row length folded in (cfg3: 32, cfg2: 8) when the prior table is one segment
-    const int dt = (h->n_seg == 1 && (c.D == 32 || c.D == 8)) ? c.D : 0;
-    if ((h->family == FAM_GAUSSIAN || h->family == FAM_BINOMIAL || h->family == FAM_LNR) && c.D <= 16 && c.fuse == 0 &&
-        c.schedule == DEMC_SCHED_TWO_COLOUR && c.partner_kind == DEMC_PARTNER_CURRENT && c.Np >= 4 && c.Np <= 512 && h->n_seg >= 1 &&
-        h->N / 16 <= 512) {
-        bool ref = false;
-        for (const DimTab& t : h->h_tab) ref = ref || t.kind == PR_NORMAL_REF;
-        const size_t doubles = (size_t)c.Np * c.D + (size_t)c.Np + (size_t)(c.Np - c.Np / 2) + (size_t)(256 / 16) * c.D +
-                               (h->family == FAM_LNR ? (size_t)kLogPhiRows * kLogPhiRow : 0);
-        if (!ref && doubles * sizeof(double) <= kMaxDynLds) {
-            PICK(h->lean_obs_k1, "k_res_obs", kResObs, 256);
-            h->lean_obs_ok = true; h->lean_obs_lds = doubles * sizeof(double);
-        }
-    }
-    // DE-MC_Z (history partners, the synchronous schedule) on the same family in SUFFSTAT mode: the lean body with partner rows
-    // from the history, one launch per iteration (step_body) -- all it needs in LDS are select_base's cumulative weights and the
-    // centred rows
-    // (... and on MvNormal(mu, sigma^2 I) with sigma a parameter, D = d + 1: the ISO instances of the same body)
-    const bool lean_fam = (h->family == FAM_MVN_FULL && c.D == h->d) || (h->family == FAM_MVN_ISO && c.D == h->d + 1);
-    if (lean_fam && c.D <= 32 && c.fuse == 0 && c.schedule == DEMC_SCHED_SYNCHRONOUS &&
-        c.partner_kind == DEMC_PARTNER_HISTORY && c.loglike_mode == DEMC_LOGLIKE_SUFFSTAT && c.Np >= 4 && h->n_seg >= 1 &&
-        (c.Np - c.Np / 2) * 4 <= 512 && h->hist) {
-        bool ref = false;
-        for (const DimTab& t : h->h_tab) ref = ref || t.kind == PR_NORMAL_REF;
-        if (!ref) {
-            const int wgh = (c.Np - c.Np / 2) * 4 > 256 ? 512 : 256;
-            h->lean_hist_ok = true; h->lean_wg = wgh;
-            // cdf | chunk offsets | centred rows | A^-1 fragments [2][8][64]
-            // ... | the first half's held-back rows [wg][8] (+ alignment slack; the snooker instance parks them) | ISO: xbar and
-            // sum_i x~_i [2][32]: demc_resmvn.hpp, pend_l / iso_l
-            h->lean_hist_lds = ((size_t)c.Np + 16 + (size_t)(wgh / 4) * ((size_t)c.D + 2) + 16 * 64 + 2 + (size_t)wgh * 8 + 64) * sizeof(double);
-        }
-        return DEMC_OK;
-    }
-    if (h->family != FAM_MVN_FULL || c.D != h->d || h->d > 32 || c.fuse != 0 || c.schedule != DEMC_SCHED_TWO_COLOUR ||
-        c.partner_kind != DEMC_PARTNER_CURRENT || c.Np < 4)
-        return DEMC_OK;
-    if (h->n_seg < 1) return DEMC_OK;  // (the prior table must fit its run-length form)
-    for (const DimTab& t : h->h_tab)
-        if (t.kind == PR_NORMAL_REF) return DEMC_OK;  // (hierarchical scale priors: the general kernel)
-    const int nact_max = c.Np - c.Np / 2;
-    if (nact_max * 4 > 512) return DEMC_OK;
-    // (DIRECT at D = 8: 512 threads whatever the group's size -- two waves per SIMD for the residual loop, which one wave per SIMD runs
-    // at half the vector pipe's rate: nothing else hides its LDS reads and dependent FP64 pairs)
-    const bool dir8 = c.loglike_mode == DEMC_LOGLIKE_DIRECT && c.D == 8 && nact_max * 4 <= 256;
-    const int wg = (nact_max * 4 > 256 || dir8) ? 512 : 256;
-    const size_t D = (size_t)c.D, Np = (size_t)c.Np;
-    const size_t base = (Np * D + Np + (size_t)nact_max + 16 + (size_t)(wg / 4) * (D + 2)) * sizeof(double);
-    if (c.loglike_mode == DEMC_LOGLIKE_SUFFSTAT) {
-        if (base > kMaxDynLds || !h->res_ok) return DEMC_OK;
-        PICK(h->lean_k1, "k_res_mvn", kResMvn, wg, false, dt, 0, 1);
-        h->lean_ok = true; h->lean_wg = wg; h->lean_lds = base;
-        return DEMC_OK;
-    }
-    // STREAMING: only where the streaming-resident form applies (plan_stream: small populations), and only with one wave per
-    // SIMD (256 threads: what the observation stage needs beyond 256 VGPRs then lives in AGPRs, not scratch)
-    const bool dir = c.loglike_mode == DEMC_LOGLIKE_DIRECT;
-    if (!(dir ? h->st_dir_geo : h->st_ok) || (wg != 256 && !dir8)) return DEMC_OK;
-    // (DIRECT: the instances with the row length compiled in, the chunk of whitened rows in LDS, MvNormal-full)
-    if (dir && !(h->family == FAM_MVN_FULL && h->n_seg == 1 && (c.D == 8 || c.D == 32) && h->dp_direct == c.D && h->dpad == c.D && h->st_x_lds)) return DEMC_OK;
-    size_t bytes = base + ((size_t)(wg / 4) * h->dpad + (size_t)(dir ? wg / 16 : wg / 64) * nact_max) * sizeof(double) + 16;  // (DIRECT: a partial sum per 16-lane row)
-    if (bytes > kMaxDynLds) return DEMC_OK;
-    const size_t xbytes = (size_t)(h->st_chunk_tiles + 1) * (h->dpad / 4) * 64 * sizeof(double);
-    // (the X chunk rides in LDS exactly when plan_stream found room for it; this kernel's other buffers are no larger)
-    if (h->st_x_lds) {
-        if (bytes + xbytes > kMaxDynLds) return DEMC_OK;
-        bytes += xbytes;
-    }
-    PICK(h->lean_k1, "k_res_mvn", kResMvn, wg, true, dt, 0, 1, false, dir);  // (DIRECT: <512, 8> and <256, 32>, what the tests above leave)
-    h->lean_stream_ok = !dir; h->lean_direct_ok = dir; h->lean_wg = wg; h->lean_stream_lds = bytes;
-    return DEMC_OK;
-}
-
-int launch_lean(demc_handle* h, long long iter0, int n_iters, bool stream) {
-    const demc_config& c = h->c;
-    KParams k = base_params(h);
-    k.iter = iter0; k.n_iters = n_iters; k.n_rows = h->hist ? c.n_rows : 0;
-    k.sx = stream ? nullptr : h->sx;
-    k.Ainv = h->Ainv;
-    if (stream) {
-        k.st_C = h->st_C; k.st_nact_max = h->st_nact_max; k.st_x_lds = h->st_x_lds; k.st_chunk_tiles = h->st_chunk_tiles;
-        k.n_tiles = h->n_tiles; k.Xf = h->Xf; k.st_gran = h->st_gran; k.st_err = h->st_err;
-        k.st_rows = 0;
-        if (k.n_groups * h->st_C > h->n_cus) return fail(h, DEMC_EINVAL, "streaming-resident grid exceeds what is resident at once");
-        HIPCHK(hipMemsetAsync(h->st_gran, 0, 2 * (size_t)c.n_groups * h->st_C * h->st_nact_max * 2 * sizeof(unsigned long long), h->stream));
-    }
-    tick(h, 0, true);
-    const unsigned grid = (unsigned)(k.n_groups * (stream ? h->st_C : 1));
-    const size_t lds = stream ? h->lean_stream_lds : h->lean_lds;
-    h->last = demc_handle::LastPlan{h->lean_k1};  // (plan_lean's choice: SUFFSTAT, STREAMING or DIRECT, the row length folded in)
-    LAUNCH_T(h, h->lean_k1->fn, dim3(grid), dim3(h->lean_wg), lds, k);
-    tick(h, 0, false);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(h, DEMC_EHIP, std::string("lean resident launch: ") + hipGetErrorString(e));
-    return DEMC_OK;
-}
-
-// the default sampler on a per-observation family: every iteration up to the next migration in one launch of k_res_obs
-int launch_lean_obs(demc_handle* h, long long iter0, int n_iters) {
-    const demc_config& c = h->c;
-    KParams k = base_params(h);
-    k.iter = iter0; k.n_iters = n_iters; k.n_rows = h->hist ? c.n_rows : 0;
-    h->last = demc_handle::LastPlan{h->lean_obs_k1};
-    tick(h, 0, true);
-    LAUNCH_T(h, h->lean_obs_k1->fn, dim3((unsigned)k.n_groups), dim3(256), h->lean_obs_lds, k);
-    tick(h, 0, false);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(h, DEMC_EHIP, std::string("lean per-observation launch: ") + hipGetErrorString(e));
-    return DEMC_OK;
-}
-
-// DE-MC_Z: ONE iteration of every group (both halves) in the lean body, partner rows from the history
-int launch_lean_hist(demc_handle* h, long long iter, bool snooker) {
-    const demc_config& c = h->c;
-    KParams k = base_params(h);
-    k.iter = iter; k.n_iters = 1; k.n_rows = h->hist ? c.n_rows : 0;
-    k.sx = h->sx;
-    k.Ainv = h->Ainv;
-    const bool iso = h->family == FAM_MVN_ISO;
-    // (ISO: the row length of the reference's own test -- 30 means and sigma -- has an instance with D compiled in)
-    // (... which reads the prior table as [one entry for the 30 means | one for sigma]: any other table takes the general row length)
-    const int dt = iso ? ((c.D == 31 && h->n_seg == 2 && h->seg_start[1] == 30) ? 31 : 0) : (h->n_seg == 1 && (c.D == 32 || c.D == 8)) ? c.D : 0;
-    const bool base = iter <= c.burnin;  // random_gamma reads a base particle (crossover.jl:164): the instance that loads its row
-    const K1Inst* e = nullptr;
-    PICK(e, "k_res_mvn", kResMvn, h->lean_wg, false, dt, snooker ? 3 : base ? 2 : 1, 1, iso);
-    h->last = demc_handle::LastPlan{e};
-    // (the HIST instances hold back the first half's stores for ONE iteration's store_row and form the cdf once per launch: the
-    // precondition is checked here, and again by the kernel -- its phase loop runs no trip for any other count)
-    if (k.n_iters != 1) return fail(h, DEMC_EINVAL, "lean DE-MC_Z kernel: one iteration per launch");
-    tick(h, 0, true);
-    LAUNCH_T(h, e->fn, dim3((unsigned)k.n_groups), dim3(h->lean_wg), h->lean_hist_lds, k);
-    tick(h, 0, false);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return fail(h, DEMC_EHIP, std::string("lean DE-MC_Z launch: ") + hipGetErrorString(err));
-    return DEMC_OK;
-}
-
-// ---- streaming-resident form: resident K1 with the observation stream inside (k_propose<..., STREAM>) ----
+// The observation stream inside a resident kernel: the geometry (h->st) and FORM_STREAM, the general kernel around it.
 // 256-thread form: one wave per SIMD, i.e. the whole register file (512 per lane, AGPRs included) behind each wave -- what does
 // not fit the 256 architectural VGPRs spills to AGPRs instead of scratch memory; 512 threads when a colour needs the lanes.
-// Decides once per model whether the streaming-resident form applies.  It is for populations too small to fill the chip
-// with one K1 -> K2 -> K3 chain per colour phase (launch- and latency-bound): MvNormal family, STREAMING likelihood,
-// two_colour, current-population partners, at most one group per CU, the group and its per-particle scratch in LDS, and a
-// colour phase whose matrix work is in the launch-overhead range.  Large populations keep the per-phase chain, whose
-// k_cross_mfma runs at the matrix peak.
+// It is for populations too small to fill the chip with one K1 -> K2 -> K3 chain per colour phase (launch- and latency-bound):
+// MvNormal family, STREAMING likelihood, two_colour, current-population partners, at most one group per CU, the group and its
+// per-particle scratch in LDS, and a colour phase whose matrix work is in the launch-overhead range.  Large populations keep the
+// per-phase chain, whose k_cross_mfma runs at the matrix peak.
+// (DIRECT: the same geometry -- chunks of the observations per workgroup, hand-over granules -- serves FORM_LEAN_DIRECT only,
+// plan_lean; the general kernel has no such form.)  Nothing is allocated here: alloc_stream follows.
 int plan_stream(demc_handle* h) {
     const demc_config& c = h->c;
-    h->st_ok = false;
-    h->st_dir_geo = false;
-    // (DIRECT: the same geometry -- chunks of the observations per workgroup, hand-over granules -- serves the lean kernel's DIRECT
-    // instance only, plan_lean; the general streaming-resident kernel has no such form, so st_ok stays false)
+    StreamGeo& g = h->st;
+    FormPlan& f = h->form[FORM_STREAM];
+    g.ok = false;
+    f = FormPlan();
     const bool direct = c.loglike_mode == DEMC_LOGLIKE_DIRECT;
     if (!is_mvn(h->family) || (c.loglike_mode != DEMC_LOGLIKE_STREAMING && !direct) || c.fuse != 0 || c.schedule != DEMC_SCHED_TWO_COLOUR ||
         c.partner_kind != DEMC_PARTNER_CURRENT || c.Np < 4 || h->n_cus < 1 || h->geo_groups > h->n_cus || c.n_groups > h->n_cus ||
@@ -1132,11 +1017,9 @@ int plan_stream(demc_handle* h) {
     if (nact_max > 512) return DEMC_OK;
     const double phase_flop = 2.0 * (double)nact_max * gg * (double)h->N * h->dpad;
     if (phase_flop / 78.6e12 > 300e-6) return DEMC_OK;
-    int lpp_max = pow2_ceil((c.D + 1) / 2);
+    const int lpp_max = pow2_ceil((c.D + 1) / 2);
     if (lpp_max > 64) return DEMC_OK;
-    int lpp = 4;
-    while (lpp * 2 <= lpp_max && nact_max * lpp * 2 <= 512) lpp *= 2;
-    if (lpp > lpp_max) lpp = lpp_max;
+    const int lpp = resident_lpp(nact_max, lpp_max, 512);
     const int wg = nact_max * lpp <= 256 ? 256 : 512, ppp = wg / lpp;
     const int rows = ((nact_max + ppp - 1) / ppp) * ppp;
     int C = 1;
@@ -1152,54 +1035,189 @@ int plan_stream(demc_handle* h) {
     const size_t xbytes = (size_t)(chunk + 1) * (h->dpad / 4) * 64 * sizeof(double);  // + the all-zero tail tile
     const int x_lds = (bytes + xbytes <= kMaxDynLds) ? 1 : 0;
     if (x_lds) bytes += xbytes;
-    // hand-over granules [2][n_groups][C][nact_max][2] and the time-out word
-    if (h->st_gran) { hipFree(h->st_gran); h->st_gran = nullptr; }
-    if (hipMalloc((void**)&h->st_gran, 2 * (size_t)c.n_groups * C * nact_max * 2 * sizeof(unsigned long long)) != hipSuccess) return DEMC_OK;
-    if (!h->st_err) {
-        if (hipHostMalloc((void**)&h->st_err, sizeof(unsigned), hipHostMallocMapped) != hipSuccess) return DEMC_OK;
-        *h->st_err = 0u;
-    }
     if (!direct) {  // (k_propose's streaming form has the two tails an MvNormal model can take: PREP_MFMA, else PREP)
         KParams k = base_params(h);
         k.lpp = lpp;
         set_tail_flags(h, k);
         const int tail = tail_of(k) == TAIL_PREP_MFMA ? TAIL_PREP_MFMA : TAIL_PREP;
-        for (int lean = 0; lean < 3; ++lean) PICK(h->st_k1[lean], "k_propose", kPropose, wg, true, tail, true, lean, true);
+        for (int lean = 0; lean < 3; ++lean) PICK(f.k1[lean], "k_propose", kPropose, wg, true, tail, true, lean, true);
+        f.ok = true; f.wg = wg; f.lds = bytes; f.lpp = lpp; f.scr_doubles = (int)scr_doubles;
     }
-    h->st_ok = !direct; h->st_dir_geo = direct;
-    h->st_C = C; h->st_nact_max = nact_max; h->st_rows = rows; h->st_x_lds = x_lds; h->st_chunk_tiles = chunk;
-    h->st_lpp = lpp; h->st_scr_doubles = (int)scr_doubles; h->st_lds = bytes; h->st_wg = wg;
+    g.ok = true; g.C = C; g.nact_max = nact_max; g.rows = rows; g.x_lds = x_lds; g.chunk_tiles = chunk;
     return DEMC_OK;
 }
 
-int launch_stream(demc_handle* h, long long iter0, int n_iters) {
+size_t granule_bytes(const demc_handle* h) { return 2 * (size_t)h->c.n_groups * h->st.C * h->st.nact_max * 2 * sizeof(unsigned long long); }
+
+// The buffers the stream geometry asks for: the hand-over granules and the time-out word.  No memory for them means no streaming
+// form, not an error (the per-phase chain serves).
+void alloc_stream(demc_handle* h) {
+    StreamGeo& g = h->st;
+    if (!g.ok) return;
+    if (g.gran) { hipFree(g.gran); g.gran = nullptr; }
+    g.ok = hipMalloc((void**)&g.gran, granule_bytes(h)) == hipSuccess;
+    if (g.ok && !g.err) {
+        g.ok = hipHostMalloc((void**)&g.err, sizeof(unsigned), hipHostMallocMapped) == hipSuccess;
+        if (g.ok) *g.err = 0u;
+    }
+    if (!g.ok) h->form[FORM_STREAM].ok = false;
+}
+
+// The lean resident kernels of the default sampler -- whether the SAMPLER is the default one is asked per step (choose_form).  They
+// read the prior table in its run-length form and know no Normal(a, theta[ref]) prior, so this plan follows the table
+// (upload_dimtab); it reads plan_resident's and plan_stream's results and touches no device memory.
+int plan_lean(demc_handle* h) {
     const demc_config& c = h->c;
-    KParams k = base_params(h);
-    k.lpp = h->st_lpp;
-    set_tail_flags(h, k);
-    k.sx = nullptr; k.fuse_accept = 1; k.write_prop = k.trace ? 1 : 0;  // STREAMING: the cross term comes from the tiles
-    k.iter = iter0; k.n_iters = n_iters; k.n_sweeps = c.n_blocks > 0 ? c.n_blocks : 1;
-    k.mask = c.n_blocks > 0 ? h->masks : nullptr;
-    k.n_rows = h->hist ? c.n_rows : 0;
-    k.n_split = 1; k.exclude_self = 0; k.own_in_pool = 1; k.tile_rows = c.Np; k.tile_in_lds = 1;
-    k.scr_doubles = h->st_scr_doubles;
-    k.plan = (k.lpp >= 4) ? 1 : 0;
-    k.st_C = h->st_C; k.st_nact_max = h->st_nact_max; k.st_rows = h->st_rows; k.st_x_lds = h->st_x_lds;
-    k.st_chunk_tiles = h->st_chunk_tiles; k.n_tiles = h->n_tiles; k.Xf = h->Xf; k.st_gran = h->st_gran; k.st_err = h->st_err;
-    if (c.n_groups * h->st_C > h->n_cus) return fail(h, DEMC_EINVAL, "streaming-resident grid exceeds the CU count");
-    // epoch tags restart at 1 in every launch: the granules of the previous launch must not match them
-    HIPCHK(hipMemsetAsync(h->st_gran, 0, 2 * (size_t)c.n_groups * h->st_C * h->st_nact_max * 2 * sizeof(unsigned long long), h->stream));
-    tick(h, 0, true);
+    for (Form f : {FORM_LEAN_SUFFSTAT, FORM_LEAN_STREAMING, FORM_LEAN_DIRECT, FORM_LEAN_OBS, FORM_LEAN_Z}) h->form[f] = FormPlan();
+    if (h->n_seg < 1 || has_normal_ref(h)) return DEMC_OK;  // (the table must fit its run-length form; hierarchical scale priors: the general kernel)
+    const int dt = compiled_row_length(h);
+    const int nact_max = c.Np - c.Np / 2;
+    // FORM_LEAN_OBS (demc_resobs.hpp): Gaussian, Binomial and the LNR with a handful of parameters (a lane per scalar of a
+    // sixteen-lane particle) and few enough observations for sixteen lanes to walk them; the group, its scratch rows and -- LNR --
+    // the log Phi(-z) table in LDS
+    if ((h->family == FAM_GAUSSIAN || h->family == FAM_BINOMIAL || h->family == FAM_LNR) && c.D <= 16 && c.fuse == 0 &&
+        c.schedule == DEMC_SCHED_TWO_COLOUR && c.partner_kind == DEMC_PARTNER_CURRENT && c.Np >= 4 && c.Np <= 512 && h->N / 16 <= 512) {
+        const size_t doubles = (size_t)c.Np * c.D + (size_t)c.Np + (size_t)nact_max + (size_t)(256 / 16) * c.D +
+                               (h->family == FAM_LNR ? (size_t)kLogPhiRows * kLogPhiRow : 0);
+        if (doubles * sizeof(double) <= kMaxDynLds) {
+            FormPlan& f = h->form[FORM_LEAN_OBS];
+            PICK(f.k1[0], "k_res_obs", kResObs, 256);
+            f.ok = true; f.wg = 256; f.lds = doubles * sizeof(double);
+        }
+    }
+    // FORM_LEAN_Z: DE-MC_Z (history partners, the synchronous schedule) on MvNormal-full in SUFFSTAT mode: the lean body with
+    // partner rows from the history, one launch per iteration -- all it needs in LDS are select_base's cumulative weights and the
+    // centred rows (... and on MvNormal(mu, sigma^2 I) with sigma a parameter, D = d + 1: the ISO instances of the same body)
+    const bool iso = h->family == FAM_MVN_ISO;
+    if (((h->family == FAM_MVN_FULL && c.D == h->d) || (iso && c.D == h->d + 1)) && c.D <= 32 && c.fuse == 0 &&
+        c.schedule == DEMC_SCHED_SYNCHRONOUS && c.partner_kind == DEMC_PARTNER_HISTORY && c.loglike_mode == DEMC_LOGLIKE_SUFFSTAT &&
+        c.Np >= 4 && nact_max * 4 <= 512 && h->hist) {
+        FormPlan& f = h->form[FORM_LEAN_Z];
+        f.wg = nact_max * 4 > 256 ? 512 : 256;
+        // cdf | chunk offsets | centred rows | A^-1 fragments [2][8][64] | the first half's held-back rows [wg][8] (+ alignment slack;
+        // the snooker instance parks them) | ISO: xbar and sum_i x~_i [2][32]: demc_resmvn.hpp, pend_l / iso_l
+        f.lds = ((size_t)c.Np + 16 + (size_t)(f.wg / 4) * ((size_t)c.D + 2) + 16 * 64 + 2 + (size_t)f.wg * 8 + 64) * sizeof(double);
+        // HIST: 1 past burn-in, 2 inside it (random_gamma reads a base particle, crossover.jl:164: the instance that loads its
+        // row), 3 with snooker updates
+        for (int hist = 1; hist <= 3; ++hist) PICK(f.k1[hist - 1], "k_res_mvn", kResMvn, f.wg, false, dt, hist, 1, iso);
+        f.ok = true;
+        return DEMC_OK;
+    }
+    // the two_colour forms (demc_resmvn.hpp): MvNormal full Sigma, D = d <= 32, one pass per phase
+    if (h->family != FAM_MVN_FULL || c.D != h->d || h->d > 32 || c.fuse != 0 || c.schedule != DEMC_SCHED_TWO_COLOUR ||
+        c.partner_kind != DEMC_PARTNER_CURRENT || c.Np < 4 || nact_max * 4 > 512)
+        return DEMC_OK;
+    // (DIRECT at D = 8: 512 threads whatever the group's size -- two waves per SIMD for the residual loop, which one wave per SIMD runs
+    // at half the vector pipe's rate: nothing else hides its LDS reads and dependent FP64 pairs)
+    const bool dir = c.loglike_mode == DEMC_LOGLIKE_DIRECT;
+    const bool dir8 = dir && c.D == 8 && nact_max * 4 <= 256;
+    const int wg = (nact_max * 4 > 256 || dir8) ? 512 : 256;
+    const size_t D = (size_t)c.D, Np = (size_t)c.Np;
+    const size_t base = (Np * D + Np + (size_t)nact_max + 16 + (size_t)(wg / 4) * (D + 2)) * sizeof(double);
+    if (c.loglike_mode == DEMC_LOGLIKE_SUFFSTAT) {
+        if (base > kMaxDynLds || !h->form[FORM_RESIDENT].ok) return DEMC_OK;
+        FormPlan& f = h->form[FORM_LEAN_SUFFSTAT];
+        PICK(f.k1[0], "k_res_mvn", kResMvn, wg, false, dt, 0, 1);
+        f.ok = true; f.wg = wg; f.lds = base;
+        return DEMC_OK;
+    }
+    // STREAMING / DIRECT: only where the observation stream applies (plan_stream: small populations), and only with one wave per
+    // SIMD (256 threads: what the observation stage needs beyond 256 VGPRs then lives in AGPRs, not scratch)
+    const StreamGeo& g = h->st;
+    if (!g.ok || (wg != 256 && !dir8)) return DEMC_OK;
+    // (DIRECT: the instances with the row length compiled in, the chunk of whitened rows in LDS)
+    if (dir && !(dt != 0 && h->dp_direct == c.D && h->dpad == c.D && g.x_lds)) return DEMC_OK;
+    size_t bytes = base + ((size_t)(wg / 4) * h->dpad + (size_t)(dir ? wg / 16 : wg / 64) * nact_max) * sizeof(double) + 16;  // (DIRECT: a partial sum per 16-lane row)
+    if (bytes > kMaxDynLds) return DEMC_OK;
+    // (the X chunk rides in LDS exactly when plan_stream found room for it; this kernel's other buffers are no larger)
+    if (g.x_lds) bytes += (size_t)(g.chunk_tiles + 1) * (h->dpad / 4) * 64 * sizeof(double);
+    if (bytes > kMaxDynLds) return DEMC_OK;
+    FormPlan& f = h->form[dir ? FORM_LEAN_DIRECT : FORM_LEAN_STREAMING];
+    PICK(f.k1[0], "k_res_mvn", kResMvn, wg, true, dt, 0, 1, false, dir);  // (DIRECT: <512, 8> and <256, 32>, what the tests above leave)
+    f.ok = true; f.wg = wg; f.lds = bytes;
+    return DEMC_OK;
+}
+
+// ---- choosing and launching a form ----
+
+// Which form carries the updates of a step call: the ONE place where the plans meet what is known only when a step is asked for --
+// a replay, an update of a subset of the groups (cur_glist), and the sampler around the kernels (lean_level: a trace, snooker
+// updates, blocks).  None of it changes inside a call, and no rule depends on the iteration: inside burn-in FORM_LEAN_Z takes
+// another instance (launch_form), not another form.  First match wins.
+Form choose_form(const demc_handle* h) {
+    const FormPlan* f = h->form;
+    // a replay hands over the caller's draws, which only the per-phase kernels read: no multi-iteration form, no lean DE-MC_Z body
+    if (h->rp_active) return FORM_PHASE;
+    const bool whole = h->cur_glist == nullptr;  // a subset of the groups never takes a spin_waiting form; it may take the others
+    const bool plain = lean_level(h, DEMC_PARTNER_CURRENT) == 1;  // the lean two_colour kernels: no trace, snooker updates or blocks
+    if (f[FORM_LEAN_DIRECT].ok && plain && whole) return FORM_LEAN_DIRECT;  // DIRECT: the one whole-update form it has
+    // STREAMING: the observation stream inside the resident kernel, the lean one where it serves
+    if (f[FORM_STREAM].ok && whole) return (plain && f[FORM_LEAN_STREAMING].ok) ? FORM_LEAN_STREAMING : FORM_STREAM;
+    // SUFFSTAT on MvNormal-full, then the per-observation families: their lean kernel before the general resident one
+    if (f[FORM_LEAN_SUFFSTAT].ok && plain) return FORM_LEAN_SUFFSTAT;
+    if (f[FORM_LEAN_OBS].ok && plain) return FORM_LEAN_OBS;
+    if (f[FORM_RESIDENT].ok) return FORM_RESIDENT;
+    // DE-MC_Z: the lean body has a snooker instance but no block sweeps -- snooker with blocks goes to the per-phase chain
+    const int lean_z = f[FORM_LEAN_Z].ok ? lean_level(h, DEMC_PARTNER_HISTORY) : 0;
+    if (lean_z == 1 || (lean_z == 2 && h->c.n_blocks == 0)) return FORM_LEAN_Z;
+    return FORM_PHASE;
+}
+
+// Iterations one launch carries at most: it stays in the millisecond range whatever the caller asks for, shorter where the grid
+// spins.  (FORM_LEAN_Z: cells of history row t - 1 come from every group, so a launch cannot span iterations.)
+int iterations_per_launch(Form f) { return (f == FORM_PHASE || f == FORM_LEAN_Z) ? 1 : spin_waiting(f) ? 64 : 1024; }
+
+// the kernarg fields of the observation stream (st_rows, the general kernel's scratch rows, apart), and its granules reset
+int stream_fields(demc_handle* h, KParams& k) {
+    const StreamGeo& g = h->st;
+    k.st_C = g.C; k.st_nact_max = g.nact_max; k.st_x_lds = g.x_lds; k.st_chunk_tiles = g.chunk_tiles;
+    k.n_tiles = h->n_tiles; k.Xf = h->Xf; k.st_gran = g.gran; k.st_err = g.err;
     // Every workgroup of this grid must be resident at once (the workgroups of a group spin on each other's progress).  The
     // grid is sized for that by construction -- at most one workgroup per CU (plan_stream: n_groups * C <= CUs, and each
     // takes most of a CU's LDS) -- so a plain launch has the same residency as a cooperative one, without its launch-time
     // cost (+15-19 us, MI355X_MICROARCH.md "coop-launch"); every spin in the kernel is bounded regardless.
-    const K1Inst* e = h->st_k1[lean_level(h, k)];
-    h->last = demc_handle::LastPlan{e};
-    LAUNCH_T(h, e->fn, dim3(c.n_groups * h->st_C), dim3(h->st_wg), h->st_lds, k);
+    if (k.n_groups * g.C > h->n_cus) return fail(h, DEMC_EINVAL, "streaming-resident grid exceeds what is resident at once");
+    // epoch tags restart at 1 in every launch: the granules of the previous launch must not match them
+    HIPCHK(hipMemsetAsync(g.gran, 0, granule_bytes(h), h->stream));
+    return DEMC_OK;
+}
+
+// iterations [iter0, iter0 + n_iters) of every group (of the subset in force) in ONE launch of `form` (any but FORM_PHASE)
+int launch_form(demc_handle* h, Form form, long long iter0, int n_iters) {
+    const demc_config& c = h->c;
+    const FormPlan& f = h->form[form];
+    KParams k = base_params(h);
+    k.iter = iter0; k.n_iters = n_iters; k.n_rows = h->hist ? c.n_rows : 0;
+    const K1Inst* e = f.k1[0];
+    if (form == FORM_RESIDENT || form == FORM_STREAM) {  // the general kernel: K1's own parameters, the tile being the whole group
+        k.lpp = f.lpp;
+        set_tail_flags(h, k);
+        k.n_sweeps = c.n_blocks > 0 ? c.n_blocks : 1;
+        k.mask = c.n_blocks > 0 ? h->masks : nullptr;
+        k.n_split = 1; k.exclude_self = 0; k.own_in_pool = 1; k.tile_rows = c.Np; k.tile_in_lds = 1;
+        k.scr_doubles = f.scr_doubles;
+        k.plan = (k.lpp >= 4) ? 1 : 0;
+        if (form == FORM_STREAM) {  // STREAMING: the cross term comes from the tiles
+            k.sx = nullptr; k.fuse_accept = 1; k.write_prop = k.trace ? 1 : 0;
+            k.st_rows = h->st.rows;
+        }
+        e = f.k1[lean_level(h, DEMC_PARTNER_CURRENT)];
+    } else if (form == FORM_LEAN_SUFFSTAT || form == FORM_LEAN_Z)
+        k.sx = h->sx;
+    if (form == FORM_LEAN_Z) {
+        // (the HIST instances hold back the first half's stores for ONE iteration's store_row and form the cdf once per launch: the
+        // precondition is checked here, and again by the kernel -- its phase loop runs no trip for any other count)
+        if (n_iters != 1) return fail(h, DEMC_EINVAL, "lean DE-MC_Z kernel: one iteration per launch");
+        e = f.k1[lean_level(h, DEMC_PARTNER_HISTORY) == 2 ? 2 : iter0 <= c.burnin ? 1 : 0];
+    }
+    unsigned grid = (unsigned)k.n_groups;
+    if (spin_waiting(form)) {
+        if (int rc = stream_fields(h, k)) return rc;
+        grid *= (unsigned)h->st.C;
+    }
+    launch_k1(h, e, grid, f.wg, f.lds, k);
     const hipError_t err = hipGetLastError();
-    tick(h, 0, false);
-    if (err != hipSuccess) return fail(h, DEMC_EHIP, std::string("streaming-resident launch: ") + hipGetErrorString(err));
+    if (err != hipSuccess) return fail(h, DEMC_EHIP, e->name(e->key) + " launch: " + hipGetErrorString(err));
     return DEMC_OK;
 }
 
@@ -1268,10 +1286,8 @@ int evaluate_rows(demc_handle* h, double* theta_dev, double* weight_dev) {
 // memory is not an error (the sweeps copy the population instead); demc_last_error then says so.
 int plan_snap2(demc_handle* h) {
     const demc_config& c = h->c;
-    const bool hier = h->family == FAM_HIER_BINOMIAL || h->family == FAM_HIER_GAUSSIAN;
-    const bool want = hier && h->hier_scr && h->lpp > 64 && c.n_blocks > 1 && c.schedule == DEMC_SCHED_SYNCHRONOUS &&
-                      c.partner_kind == DEMC_PARTNER_HISTORY && c.proposal_kind == 0 && c.burnin >= 1 && c.fuse == 0 && !c.trace &&
-                      c.kappa == 1.0 && (long long)h->geo_groups * c.Np >= 2LL * h->n_cus;
+    const bool want = frozen_possible(h) && c.n_blocks > 1 && c.schedule == DEMC_SCHED_SYNCHRONOUS &&
+                      c.partner_kind == DEMC_PARTNER_HISTORY && c.proposal_kind == 0 && c.burnin >= 1;
     if (!want) {
         if (h->snap2 || h->snap2_w) {
             HIPCHK(hipStreamSynchronize(h->stream));
@@ -1328,8 +1344,10 @@ int size_k1_lds(demc_handle* h) {
     if (int rc = raise_dyn_lds(h, kResObs)) return rc;
     if (int rc = raise_dyn_lds(h, kSim)) return rc;
     if (int rc = raise_dyn_lds(h, kOde)) return rc;
+    // the whole-update forms.  Decide, then allocate: the plans compute geometry only, the stream's buffers follow once it is known
     if (int rc = plan_resident(h)) return rc;
     if (int rc = plan_stream(h)) return rc;
+    alloc_stream(h);
     if (int rc = plan_lean(h)) return rc;
     HIPCHK(hipFuncSetAttribute((const void*)k_mig_pack, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynLds));
     return plan_snap2(h);
@@ -1520,14 +1538,14 @@ int32_t demc_destroy(demc_handle* h) {
         if (h->glist_pin[i]) hipHostFree(h->glist_pin[i]);
         if (h->glist_ev[i]) hipEventDestroy(h->glist_ev[i]);
     }
-    if (h->st_gran) hipFree(h->st_gran);
+    if (h->st.gran) hipFree(h->st.gran);
     if (h->frozen_order_d) hipFree(h->frozen_order_d);
     if (h->frozen_order_pin) hipHostFree(h->frozen_order_pin);
     if (h->frozen_order_ev) hipEventDestroy(h->frozen_order_ev);
     if (h->snap2) hipFree(h->snap2);
     if (h->snap2_w) hipFree(h->snap2_w);
     if (h->clk_dev) hipFree(h->clk_dev);
-    if (h->st_err) hipHostFree(h->st_err);
+    if (h->st.err) hipHostFree(h->st.err);
     if (h->side) hipStreamSynchronize(h->side);
     if (h->comm && h->own_comm) ncclCommDestroy(h->comm);
     if (h->ev_pack) hipEventDestroy(h->ev_pack);
@@ -2354,20 +2372,14 @@ static int exchange_overlapped(demc_handle* h, int64_t iter, int run) {
 static void plan_frozen_order(demc_handle* h, int64_t iter0, int32_t n_iters) {
     const demc_config& c = h->c;
     h->frozen_iters = 0;
-    const bool hier = h->family == FAM_HIER_BINOMIAL || h->family == FAM_HIER_GAUSSIAN;
-    if (!hier || c.n_blocks < 1 || h->lpp <= 64 || h->cur_glist || c.beta <= 0.0 || h->rp_active || n_iters < 1) return;
-    // nothing to plan where launch_phase cannot take the frozen form at all: too few moving particles for two workgroups per CU,
-    // recombination, a pool beyond the kernel's, the unfused / per-phase forms, a trace
-    const int n_act = c.schedule == DEMC_SCHED_TWO_COLOUR ? c.Np - c.Np / 2 : c.schedule == DEMC_SCHED_SEQUENTIAL ? 1 : c.Np;
-    if ((long long)h->geo_groups * n_act < 2LL * h->n_cus || c.kappa != 1.0 || c.Np > 512 || c.fuse != 0 || c.trace || !h->hier_scr) return;
+    // nothing to plan where launch_phase cannot take the frozen form at all (frozen_possible; a pool beyond the kernel's), for a
+    // subset of the groups (its own list), without mutation, or under a replay
+    if (!frozen_possible(h) || c.Np > 512 || h->cur_glist || c.beta <= 0.0 || h->rp_active || n_iters < 1) return;
     bool any = false;
     std::vector<char> frozen((size_t)c.n_blocks, 0);
     for (int b = 0; b < c.n_blocks && (size_t)b < h->mask_runs.size(); ++b) {
         const auto& mr = h->mask_runs[(size_t)b];
-        int inside = 0;
-        for (int r = 0; r < mr.n; ++r)
-            if ((mr.in >> r) & 1u) inside += (r + 1 < mr.n ? mr.start[r + 1] : c.D) - mr.start[r];
-        frozen[(size_t)b] = mr.n > 0 && inside >= 1;
+        frozen[(size_t)b] = block_span(mr.n, mr.in, mr.start, c.D).inside >= 1;
         any = any || frozen[(size_t)b];
     }
     const size_t need = (size_t)n_iters * c.n_blocks * c.n_groups;
@@ -2418,6 +2430,8 @@ static int step_body(demc_handle* h, int64_t iter0, int32_t n_iters, bool with_m
     const int n_sweeps = c.n_blocks > 0 ? c.n_blocks : 1;  // block_update! main.jl:174-179
     plan_frozen_order(h, iter0, n_iters);
     h->snap2_iter = -1;  // (a by-product snapshot lives inside one call)
+    const Form form = choose_form(h);
+    const int cap = iterations_per_launch(form);
     for (int64_t iter = iter0; iter < iter0 + n_iters; ++iter) {
         if (with_migration && migration_due_h(h, iter)) {  // main.jl:85
             if (c.n_groups_total != c.n_groups || (h->comm && h->own_comm)) {  // (a communicator of one rank takes the same path)
@@ -2440,36 +2454,13 @@ static int step_body(demc_handle* h, int64_t iter0, int32_t n_iters, bool with_m
             } else
                 migration_enqueue(h, iter, h->mig_rows, h->mig_rows, true, true);
         }
-        const bool st_ok = h->st_ok && !h->cur_glist;  // (a subset update never uses the form whose workgroups wait on each other)
-        // the default sampler has lean kernels of its own on MvNormal-full and on the per-observation families (same draws, same decisions)
-        KParams kp0 = base_params(h);
-        kp0.mode = MODE_STEP;
-        const bool plain = is_plain(h, kp0);
-        const bool obs_lean = h->lean_obs_ok && plain;
-        const bool dir_lean = h->lean_direct_ok && plain && !h->cur_glist;  // (its workgroups wait on each other: never on a subset)
-        if ((h->res_ok || st_ok || obs_lean || dir_lean) && !h->rp_active) {  // every iteration up to the next migration in one launch
-            int run = 1;  // capped so that a single launch stays in the millisecond range whatever the caller asks for
-            const int cap = (st_ok || dir_lean) ? 64 : 1024;
+        if (form != FORM_PHASE) {  // every iteration up to the next migration, or to the form's cap, in one launch
+            int run = 1;
             while (run < cap && iter + run < iter0 + n_iters && !(with_migration && migration_due_h(h, iter + run))) ++run;
-            int rc;
-            if (dir_lean) rc = launch_lean(h, iter, run, true);
-            else if (st_ok && plain && h->lean_stream_ok) rc = launch_lean(h, iter, run, true);
-            else if (!st_ok && plain && h->lean_ok) rc = launch_lean(h, iter, run, false);
-            else if (obs_lean) rc = launch_lean_obs(h, iter, run);
-            else rc = st_ok ? launch_stream(h, iter, run) : launch_resident(h, iter, run);
+            int rc = launch_form(h, form, iter, run);
             if (rc != DEMC_OK) return rc;
             iter += run - 1;
             continue;
-        }
-        if (h->lean_hist_ok && !h->rp_active) {  // DE-MC_Z, the default sampler: the lean body
-            KParams kp = base_params(h);
-            kp.mode = MODE_STEP;
-            const int lh = lean_hist(h, kp);  // 1: the default sampler; 2 with theta_snooker > 0 and no blocks: + snooker updates
-            if (lh == 1 || (lh == 2 && c.n_blocks == 0)) {
-                int rc = launch_lean_hist(h, iter, lh == 2);
-                if (rc != DEMC_OK) return rc;
-                continue;
-            }
         }
         for (int b = 0; b < n_sweeps; ++b) {
             const unsigned char* mask = c.n_blocks > 0 ? h->masks + (size_t)b * c.D : nullptr;
@@ -2498,8 +2489,8 @@ static int step_checks(demc_handle* h, int64_t iter0, int32_t n_iters) {
 static int drain(demc_handle* h) {
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipGetLastError());
-    if (h->st_err && *h->st_err) {
-        *h->st_err = 0u;
+    if (h->st.err && *h->st.err) {
+        *h->st.err = 0u;
         return fail(h, DEMC_EHIP, "streaming-resident kernel: a hand-over between the workgroups of a group timed out");
     }
     if (h->comm) {  // a collective that failed after it was enqueued shows up here

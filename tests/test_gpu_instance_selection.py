@@ -18,22 +18,37 @@ from conftest import make_problem, setup_engine
 pytestmark = pytest.mark.gpu
 
 
-def names_of(demc, fam, Np, history=False, **cfg):
-    """the names after each of two single-iteration steps (with history partners: iterations 3 and 4 behind two prior rows, and
-    burnin = 3, so that the first lies inside burn-in and the second past it)"""
+def tiny_engine(demc, fam, Np, history=False, blocks=None, **cfg):
+    """2 groups of Np particles on 64 observations, ready to step (with history partners: behind two prior rows, burnin = 3)"""
     prob = make_problem(fam[0], np.random.default_rng(17), **fam[1])
     P = 2 * Np
     if history:
         cfg = dict(schedule=1, partner_kind=1, n_initial=2, burnin=3, **cfg)
     eng = demc.HipEngine(n_groups=2, Np=Np, D=prob["D"], n_rows=8, seed=11, alpha=0.0, **cfg)
     setup_engine(eng, prob)
+    if blocks is not None:
+        eng.set_blocks(blocks)
     if history:
         eng.set_history_rows(0, np.stack([prob["init"](P) for _ in range(2)]))
     eng.set_state(prob["init"](P))
+    return eng
+
+
+def names_of(demc, fam, Np, history=False, blocks=None, replay=None, groups=None, **cfg):
+    """the names after each of two single-iteration steps (with history partners: iterations 3 and 4 behind two prior rows, and
+    burnin = 3, so that the first lies inside burn-in and the second past it); `replay`: draws handed to set_replay first;
+    `groups`: the steps are subset updates of these groups"""
+    eng = tiny_engine(demc, fam, Np, history, blocks, **cfg)
+    if replay:
+        eng.set_replay(**replay)
     first = 3 if history else 1
     out = []
     for it in (first, first + 1):
-        eng.step(it, 1)
+        if groups is None:
+            eng.step(it, 1)
+        else:
+            eng.update_groups_enqueue(it, 1, groups)
+            eng.synchronize()
         out.append(eng.last_kernels())
     eng.close()
     return out
@@ -95,3 +110,66 @@ def test_per_phase_instance_of_512_threads(demc):
     """a particle of D = 4096 scalars takes a whole 512-thread workgroup (hierarchical Binomial, 4094 subjects, their terms summed in
     K1: TAIL_OBS); fuse = 2 keeps the per-phase kernel where the long-row kernel would take over"""
     assert names_of(demc, ("hier_binomial", dict(S=4094)), 8, fuse=2, trace=1) == ["k_propose<512,false,TAIL_OBS,false,false>"] * 2
+
+
+# ---- the rules that depend on what is known only when a step is asked for: a replay, a subset of the groups, a trace, snooker
+# updates with blocks, and how many iterations one launch may carry ----
+
+PHASE_MVN8 = "k_propose<256,true,TAIL_PREP_MFMA,false,{lean}>"  # the per-phase K1 of MvNormal-full, d = 8, over the LDS tile
+
+
+def test_replay_takes_the_per_phase_chain(demc):
+    """a replay disables every kernel that carries several iterations (and the lean bodies: their draws are Philox only).  MvNormal-full
+    d = 8, SUFFSTAT takes k_res_mvn<256,false,8>; under a replay each colour phase is one per-phase K1 (SUFFSTAT on two_colour fuses
+    the whole update into it: no likelihood or accept kernel follows), the general instance (LEAN = 0)"""
+    assert names_of(demc, mvn(8), 8, loglike_mode=1) == ["k_res_mvn<256,false,8>"] * 2
+    assert names_of(demc, mvn(8), 8, loglike_mode=1, replay=dict(u_step=[0.9])) == [PHASE_MVN8.format(lean="false")] * 2
+
+
+def test_subset_update_leaves_the_streaming_forms(demc):
+    """an update of a subset of the groups never takes a form whose workgroups wait on each other: MvNormal-full d = 8, STREAMING
+    takes k_res_mvn<256,true,8> for the whole handle and the per-phase chain (lean K1 over the tile, d = 8: two k-steps per pass)
+    for one group of the two -- STREAMING has no other resident form to fall back on"""
+    chain = PHASE_MVN8.format(lean="true") + " + k_cross_mfma<2,4> + k_accept_store"
+    assert names_of(demc, mvn(8), 8, loglike_mode=0) == ["k_res_mvn<256,true,8>"] * 2
+    got = names_of(demc, mvn(8), 8, loglike_mode=0, groups=[1])
+    assert got == [chain] * 2 and not any("k_res_mvn" in g or g.endswith(",true>") for g in got)
+
+
+def test_subset_update_keeps_the_lean_suffstat_kernel(demc):
+    """... while the forms with one independent workgroup per group serve a subset as they serve the handle: SUFFSTAT keeps
+    k_res_mvn<256,false,8>"""
+    assert names_of(demc, mvn(8), 8, loglike_mode=1, groups=[1]) == ["k_res_mvn<256,false,8>"] * 2
+
+
+def test_de_mc_z_with_snooker_and_blocks_takes_the_per_phase_chain(demc):
+    """the lean DE-MC_Z body has a snooker instance (HIST = 3) but no block sweeps: with snooker updates AND a block mask every sweep
+    is a per-phase K1 without a tile, LEAN = 2 -- one kernel inside burn-in too (SUFFSTAT: the sweep-start snapshot keeps the update
+    fused), never k_res_mvn<...,3>"""
+    blocks = np.array([[1, 1, 1, 0, 0], [0, 0, 0, 1, 1]], np.uint8)
+    assert names_of(demc, mvn(5), 8, history=True, loglike_mode=1, theta_snooker=0.1) == ["k_res_mvn<256,false,0,3>"] * 2
+    assert names_of(demc, mvn(5), 8, history=True, loglike_mode=1, theta_snooker=0.1, blocks=blocks) == \
+        ["k_propose<256,false,TAIL_PREP_MFMA,false,2>"] * 2
+
+
+def test_trace_on_a_per_observation_family_takes_the_general_resident_kernel(demc):
+    """k_res_obs serves the default sampler only; a trace is not part of it: the Gaussian model keeps the resident form (its
+    per-observation terms summed in K1: TAIL_OBS) with the general instance, LEAN = 0"""
+    gauss = ("gaussian", dict(N=64))
+    assert names_of(demc, gauss, 8) == ["k_res_obs<256>"] * 2
+    assert names_of(demc, gauss, 8, trace=1) == ["k_propose<256,true,TAIL_OBS,true,false>"] * 2
+
+
+@pytest.mark.parametrize("cfg,n,cap,kernel", [(dict(loglike_mode=1), 1100, 1024, "k_res_mvn<256,false,8>"),
+                                              (dict(loglike_mode=0, theta_snooker=0.1), 200, 64, "k_propose<256,true,TAIL_PREP_MFMA,true,2,true>")])
+def test_iterations_per_launch_follow_the_form(demc, cfg, n, cap, kernel):
+    """one launch carries at most 1024 iterations, 64 where the workgroups of a group wait on each other (the streaming-resident
+    forms): n iterations without a migration are ceil(n / cap) launches"""
+    eng = tiny_engine(demc, mvn(8), 8, **cfg)
+    eng.timing_enable()
+    eng.update(1, n)
+    launches = eng.timing_read()["propose"]["launches"]
+    name = eng.last_kernels()
+    eng.close()
+    assert name == kernel
+    assert launches == -(-n // cap)

@@ -13,7 +13,7 @@ span loop over a non-plain segment, or turned -Inf - (-Inf) into an accepted mov
 
 Every case is a free run of both engines through test_gpu_production.free_run with that helper's bars: particle ids and accept
 flags bit for bit, theta bit for bit at beta = 0 and to 1e-10 otherwise, log-posteriors to rtol 1e-9 in every
-case.  The instance each case ran is asserted by name; the names were derived by hand from plan_lean / launch_phase / launch_lean_hist (csrc/demc_hip.cpp) and are written into the case list.
+case.  The instance each case ran is asserted by name; the names were derived by hand from plan_lean / launch_phase / choose_form (csrc/demc_hip.cpp) and are written into the case list.
 
 The cases, their tables and shapes live in tests/test_prior_tables_host.py (CASES), which shows on the CPU that each of them
 is evidence: the prior under test changes decisions, the run accepts, the bounds said to bite do.
@@ -159,7 +159,7 @@ def test_res_mvn_other_forms_under_non_normal_priors(demc, orc, c):
     instances: MvNormal(mu, sigma^2 I) with d = 5 and sigma ~ Gamma / LogNormal / Exponential (the general row length: sigma's
     entry through the nibble decode), and workloads.mvn30 with the 30 means Cauchy(0, 1) and sigma ~ LogNormal(0, 0.5) in place
     of the reference's Cauchy+: that table is still [one entry for the 30 means | one for sigma] (n_seg = 2, the second segment
-    starting at scalar 30), which is all launch_lean_hist asks before it takes the D = 31 instance -- the kinds of the two
+    starting at scalar 30), which is all compiled_row_length asks before it takes the D = 31 instance -- the kinds of the two
     entries are not part of the rule -- so the instance with the fixed sigma slot runs a non-Normal entry for the means through
     the one-segment arm and a LogNormal through the slot."""
     run_case(demc, orc, c)
