@@ -43,6 +43,7 @@
 #include "demc_ode.hpp"
 #include "demc_summary.hpp"  // demc_summarize: its kernels and their launches live in demc_summary.cpp
 #include "demc_quantile.hpp"  // demc_quantiles: likewise, demc_quantile.cpp
+#include "demc_devmem.hpp"  // owners of the device memory, pinned memory, events and modules the handle holds
 #include "demc_instances.hpp"  // one table per templated kernel, built from the lists above: every choice of an instance goes through them
 
 using namespace demc;
@@ -92,8 +93,49 @@ struct FormPlan {
 struct StreamGeo {
     bool ok = false;
     int C = 0, nact_max = 0, rows = 0, x_lds = 0, chunk_tiles = 0;  // chunks per group, moving particles, scratch rows, X chunk in LDS, tiles per chunk
-    unsigned long long* gran = nullptr;  // hand-over granules (device), [2][n_groups][C][nact_max][2]
-    unsigned* err = nullptr;             // time-out flag (host-mapped, zero-copy)
+    DevBuf<unsigned long long> gran;  // hand-over granules (device), [2][n_groups][C][nact_max][2]
+    PinnedBuf<unsigned> err;          // time-out flag (host-mapped, zero-copy)
+};
+
+// Everything a set-model call defines.  The default state is "no model"; clear_model is the one place a model is released.
+struct Model {
+    int family = -1;
+    long long N = 0;
+    int d = 0, n_acc = 0, dpad = 0;
+    int n_tiles = 0;
+    int ks_t = 0, n_kpass = 0;  // MFMA k-steps per pass (template) and passes over the dimensions
+    int dp_direct = 0;          // DIRECT mode: padded length of a whitened observation row (8 / 16 / 32 / 64)
+    int direct_wgs_per_cu = 0;  // ... resident workgroups of its kernel per CU (wgs_per_cu: asked once per model)
+    DevBuf<double> data, Ainv, Ypad, Xf, sx, xbar;
+    size_t data2_off = 0;
+    double c0 = 0, c1 = 0, c2 = 0;
+    // user plug-in (demc_set_model_source): JIT-compiled module, kernel and its hyper-parameters
+    Module user_module;
+    hipFunction_t user_kernel = nullptr;
+    DevBuf<double> user_hyper;
+    int user_nhyper = 0;
+    bool user_row = false;        // whole-row plug-in (demc_set_model_source_row): one workgroup per proposal
+    bool user_has_prior = false;  // ... whose source also defines demc_user_prior_row
+    DevBuf<long long> user_dims;
+    int user_ndims = 0;
+    // simulation-based likelihood (demc_set_model_sim, demc_simlike.hpp); a user simulator's module lives in user_module / user_kernel
+    int sim_kind = -1, sim_est = 0, sim_n = 0;
+    int sim_kmax = 0;              // KDE_CHOICE: the largest observed choice
+    double sim_bw = 0.0;
+    DevBuf<double> sim_logtab;     // [n_sim + 1] log(c / n_sim): the frequency estimator's terms
+    // ODE-trajectory likelihood (DEMC_FAM_ODE_LV, demc_ode.hpp): N = the observation times T, data = Y[T][DIM]
+    int ode_substeps = 0;
+    double ode_u0[4] = {0, 0, 0, 0}, ode_h = 0.0;
+};
+
+// demc_set_replay: device copies of the caller's draws.  Cleared by assigning Replay{}.
+struct Replay {
+    DevBuf<double> group, part, noise, znoise, recomb;
+    DevBuf<long long> partner, mig_particle;
+    DevBuf<int> mig_groups;
+    int n_mig = 0;
+    bool active = false, has_step = false;
+    double u_step = 0.0;
 };
 
 }  // namespace
@@ -104,54 +146,26 @@ struct demc_handle {
     hipStream_t stream = nullptr;
     bool own_stream = false;
     // state
-    double *theta = nullptr, *weight = nullptr, *prop = nullptr, *prop_prior = nullptr, *prop_adj = nullptr;
-    double *tr_w = nullptr, *partial = nullptr, *aux = nullptr;
-    DimTab* dimtab = nullptr;
+    DevBuf<double> theta, weight, prop, prop_prior, prop_adj, tr_w, partial, aux;
+    DevBuf<DimTab> dimtab;
     std::vector<DimTab> h_tab;  // host copy: bounds and priors arrive in separate calls
-    DimSeg* dimseg = nullptr;   // run-length form of the table (kMaxDimSeg entries)
+    DevBuf<DimSeg> dimseg;      // run-length form of the table (kMaxDimSeg entries)
     int n_seg = 0;              // 0: more segments than kMaxDimSeg, the kernels read dimtab
     int seg_start[kMaxDimSeg] = {0};
     unsigned seg_plain = 0;     // segments with a flat / Normal / Normal(a, theta[ref]) prior
     struct MaskRuns { int n = 0; unsigned in = 0; int start[kMaxMaskRun] = {0}; };
     std::vector<MaskRuns> mask_runs;  // per block sweep: the mask run-length encoded (n = 0: too many runs)
-    double *hist = nullptr, *lp_hist = nullptr, *mig_rows = nullptr, *scratch_theta = nullptr, *scratch_w = nullptr;
-    long long* id = nullptr;
-    unsigned char *prop_oob = nullptr, *tr_acc = nullptr, *masks = nullptr, *acc_hist = nullptr;
-    int *tr_idx = nullptr, *id_hist = nullptr;
-    // model
-    int family = -1;
-    long long N = 0;
-    int d = 0, n_acc = 0, dpad = 0;
-    int n_tiles = 0;
-    int ks_t = 0, n_kpass = 0;  // MFMA k-steps per pass (template) and passes over the dimensions
-    int dp_direct = 0;          // DIRECT mode: padded length of a whitened observation row (8 / 16 / 32 / 64)
-    int direct_wgs_per_cu = 0;  // ... resident workgroups of its kernel per CU (wgs_per_cu: asked once)
-    int obs_wgs_per_cu = 0;     // the same for k_obs_loglike
-    int lba_wave_wgs_per_cu = 0;  // ... and k_lba_wave
-    double *data = nullptr, *Ainv = nullptr, *Ypad = nullptr, *Xf = nullptr, *sx = nullptr, *xbar = nullptr;
-    size_t data2_off = 0;
-    // user plug-in (demc_set_model_source): JIT-compiled module, kernel and its hyper-parameters
-    hipModule_t user_module = nullptr;
-    hipFunction_t user_kernel = nullptr;
-    double* user_hyper = nullptr;
-    int user_nhyper = 0;
-    bool user_row = false;        // whole-row plug-in (demc_set_model_source_row): one workgroup per proposal
-    bool user_has_prior = false;  // ... whose source also defines demc_user_prior_row
-    long long* user_dims = nullptr;
-    int user_ndims = 0;
-    // simulation-based likelihood (demc_set_model_sim, demc_simlike.hpp); a user simulator's module lives in user_module / user_kernel
-    int sim_kind = -1, sim_est = 0, sim_n = 0;
-    int sim_kmax = 0;               // KDE_CHOICE: the largest observed choice
-    double sim_bw = 0.0;
-    double* sim_logtab = nullptr;   // [n_sim + 1] log(c / n_sim): the frequency estimator's terms
-    unsigned sim_entity_base = 0;   // demc_logpost: row r of a call is evaluated at entity r
-    // ODE-trajectory likelihood (DEMC_FAM_ODE_LV, demc_ode.hpp): N = the observation times T, data = Y[T][DIM]
-    int ode_substeps = 0;
-    double ode_u0[4] = {0, 0, 0, 0}, ode_h = 0.0;
+    DevBuf<double> hist, lp_hist, mig_rows, scratch_theta, scratch_w;
+    DevBuf<long long> id;
+    DevBuf<unsigned char> prop_oob, tr_acc, masks, acc_hist;
+    DevBuf<int> tr_idx, id_hist;
+    Model m;                      // the model currently set (family -1: none)
+    int obs_wgs_per_cu = 0;       // resident workgroups of k_obs_loglike per CU (wgs_per_cu: asked once) ...
+    int lba_wave_wgs_per_cu = 0;  // ... and of k_lba_wave: whatever the model
+    unsigned sim_entity_base = 0;  // demc_logpost on a simulated likelihood: row r of a call is evaluated at entity r
     // DEMC_PRIOR_TRUNCNORMAL: the device's table holds a Normal entry whose constant carries the mass between the bounds; the scale
     // the caller gave (0: the scalar's prior is not a truncated Normal) is kept here so that the constant follows the bounds
     std::vector<double> trunc_sd;
-    double c0 = 0, c1 = 0, c2 = 0;
     int partial_cap = 64;
     int lpp = 1;
     int tile_in_lds = 0;
@@ -165,14 +179,14 @@ struct demc_handle {
     // workgroup that starts last ends the launch.  A hint only: any order gives the same results.
     // by-product snapshot (KParams::snap_theta / snap_weight): the rows and weights a frozen sweep over the whole population ended
     // with, valid as the sweep-start snapshot of sweep `snap2_sweep` of iteration `snap2_iter` (and of nothing else)
-    double *snap2 = nullptr, *snap2_w = nullptr;
+    DevBuf<double> snap2, snap2_w;
     int64_t snap2_iter = -1;
     int snap2_sweep = -1;
-    int* frozen_order_d = nullptr;
+    DevBuf<int> frozen_order_d;
     size_t frozen_order_cap = 0;
-    int* frozen_order_pin = nullptr;        // pinned staging of the table (a truly asynchronous copy: nothing is drained)
+    PinnedBuf<int> frozen_order_pin;        // pinned staging of the table (a truly asynchronous copy: nothing is drained)
     size_t frozen_order_pin_cap = 0;
-    hipEvent_t frozen_order_ev = nullptr;   // the last copy out of the staging buffer has been consumed
+    Event frozen_order_ev;                  // the last copy out of the staging buffer has been consumed
     long long frozen_iter0 = 0;
     int frozen_iters = 0;
     int n_cus = 0;
@@ -185,20 +199,14 @@ struct demc_handle {
     // the host copy as consumed.  The device copy is refilled by a copy ON THE HANDLE'S STREAM, i.e. behind every kernel that
     // still reads its previous content.
     static constexpr int kGlistRing = 8;
-    int* glist_buf[kGlistRing] = {};
-    int* glist_pin[kGlistRing] = {};
-    hipEvent_t glist_ev[kGlistRing] = {};
+    DevBuf<int> glist_buf[kGlistRing];
+    PinnedBuf<int> glist_pin[kGlistRing];
+    Event glist_ev[kGlistRing];
     int glist_next = 0;
     const int* cur_glist = nullptr;
     int cur_ng = 0;
     std::string err;
-    // replay (demc_set_replay): device copies of the caller's draws
-    double *rp_group = nullptr, *rp_part = nullptr, *rp_noise = nullptr, *rp_znoise = nullptr, *rp_recomb = nullptr;
-    long long *rp_partner = nullptr, *rp_mig_particle = nullptr;
-    int* rp_mig_groups = nullptr;
-    int rp_n_mig = 0;
-    bool rp_active = false, rp_has_step = false;
-    double rp_u_step = 0.0;
+    Replay rp;
     int geo_groups = 0;  // groups the lane geometry is sized for (demc_config.geometry_groups, else n_groups)
     int hist_ld = 0;     // doubles between consecutive history cells (KParams::hist_ld)
     // the one collective of the path: an RCCL communicator owned by the handle (demc_comm_init), or lent by the
@@ -208,8 +216,8 @@ struct demc_handle {
     int comm_rank = 0, comm_world = 1;
     bool comm_overlap = false;        // demc_comm_set_overlap: unselected groups update while the all-gather is in flight
     hipStream_t side = nullptr;       // ... on this stream
-    hipEvent_t ev_pack = nullptr, ev_gath = nullptr;
-    double* red_dev = nullptr;        // demc_comm_allreduce staging
+    Event ev_pack, ev_gath;
+    DevBuf<double> red_dev;           // demc_comm_allreduce staging
     size_t red_cap = 0;
     long long n_exchanges = 0;        // all-gathers issued (diagnostic, demc_comm_stats)
     struct demc_multi* multi = nullptr;
@@ -229,7 +237,7 @@ struct demc_handle {
     double t_ms[5] = {0, 0, 0, 0, 0};
     long long t_n[5] = {0, 0, 0, 0, 0};
     // clock probe of the DIRECT likelihood kernel (demc_timing_clock): per workgroup {s_memtime, s_memrealtime, XCD} at its end
-    unsigned long long* clk_dev = nullptr;
+    DevBuf<unsigned long long> clk_dev;
     size_t clk_cap = 0, clk_n = 0;  // workgroups the buffer holds / the last timed launch wrote
 };
 
@@ -270,21 +278,21 @@ int32_t guarded(demc_handle* h, F&& body) noexcept {
 #define USE_DEVICE(h) HIPCHK(hipSetDevice((h)->c.device_id))
 
 template <typename T>
-int dev_alloc(demc_handle* h, T** p, size_t n) {
+int dev_alloc(demc_handle* h, DevBuf<T>& p, size_t n) {
     if (n == 0) n = 1;
-    hipError_t e = hipMalloc((void**)p, n * sizeof(T));
+    hipError_t e = p.alloc(n);
     if (e != hipSuccess) return fail(h, DEMC_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
     // hipMemset runs on the null stream and may return before the fill has happened; the handle's own stream is
     // non-blocking, i.e. NOT ordered behind the null stream -- without the wait a kernel launched right after an
     // allocation (demc_export_chains) could have its output zeroed underneath it.
-    e = hipMemset(*p, 0, n * sizeof(T));
+    e = hipMemset(p.get(), 0, n * sizeof(T));
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
     if (e != hipSuccess) return fail(h, DEMC_EHIP, std::string("hipMemset: ") + hipGetErrorString(e));
     return DEMC_OK;
 }
 #define ALLOC(ptr, n)                          \
     do {                                       \
-        int rc_ = dev_alloc(h, &(ptr), (n));   \
+        int rc_ = dev_alloc(h, (ptr), (n));    \
         if (rc_ != DEMC_OK) return rc_;        \
     } while (0)
 
@@ -390,16 +398,16 @@ KParams base_params(demc_handle* h) {
     k.n_mrun = 1; k.mrun_in = 1u;  // no block mask: one run, inside
     k.hist = h->hist; k.acc_hist = h->acc_hist; k.lp_hist = h->lp_hist; k.id_hist = h->id_hist; k.hist_ld = h->hist_ld;
     k.P = h->P; k.store_row = -1; k.tile_in_lds = h->tile_in_lds;
-    k.family = h->family; k.N = h->N; k.d = h->d; k.n_acc = h->n_acc; k.n_partials = 1;
-    k.partial = h->partial; k.aux = h->aux; k.data = h->data; k.data2 = h->data ? h->data + h->data2_off : nullptr;
-    k.c0 = h->c0; k.c1 = h->c1; k.c2 = h->c2;
-    k.direct = (is_mvn(h->family) && c.loglike_mode == DEMC_LOGLIKE_DIRECT) ? 1 : 0;
+    k.family = h->m.family; k.N = h->m.N; k.d = h->m.d; k.n_acc = h->m.n_acc; k.n_partials = 1;
+    k.partial = h->partial; k.aux = h->aux; k.data = h->m.data; k.data2 = h->m.data ? h->m.data + h->m.data2_off : nullptr;
+    k.c0 = h->m.c0; k.c1 = h->m.c1; k.c2 = h->m.c2;
+    k.direct = (is_mvn(h->m.family) && c.loglike_mode == DEMC_LOGLIKE_DIRECT) ? 1 : 0;
     k.n_split = 1; k.fuse_prep = 0; k.prep_mfma = 0; k.fuse_obs = 0; k.fuse_accept = 0; k.plan = 0;
     k.scr_doubles = (int)(h->k1_scr_bytes / sizeof(double)); k.write_prop = 1; k.trace = c.trace;
-    k.Ainv = h->Ainv; k.sx = nullptr; k.xbar = h->xbar; k.Ypad = h->Ypad; k.dpad = h->dpad;
-    k.rp_group = h->rp_group; k.rp_part = h->rp_part; k.rp_partner = h->rp_partner; k.rp_noise = h->rp_noise;
-    k.rp_znoise = h->rp_znoise; k.rp_recomb = h->rp_recomb; k.rp_mig_groups = h->rp_mig_groups;
-    k.rp_mig_particle = h->rp_mig_particle; k.rp_n_mig = h->rp_n_mig;
+    k.Ainv = h->m.Ainv; k.sx = nullptr; k.xbar = h->m.xbar; k.Ypad = h->m.Ypad; k.dpad = h->m.dpad;
+    k.rp_group = h->rp.group; k.rp_part = h->rp.part; k.rp_partner = h->rp.partner; k.rp_noise = h->rp.noise;
+    k.rp_znoise = h->rp.znoise; k.rp_recomb = h->rp.recomb; k.rp_mig_groups = h->rp.mig_groups;
+    k.rp_mig_particle = h->rp.mig_particle; k.rp_n_mig = h->rp.n_mig;
     k.glist = h->cur_glist;
     if (h->cur_glist) k.n_groups = h->cur_ng;
     return k;
@@ -498,8 +506,8 @@ int clock_buffer(demc_handle* h, size_t wgs, unsigned long long** out) {
     *out = nullptr;
     if (!h->timing) return DEMC_OK;
     if (wgs > h->clk_cap) {
-        if (h->clk_dev) { HIPCHK(hipStreamSynchronize(h->stream)); hipFree(h->clk_dev); h->clk_dev = nullptr; h->clk_cap = 0; }
-        ALLOC(h->clk_dev, 3 * wgs);
+        if (h->clk_dev) { HIPCHK(hipStreamSynchronize(h->stream)); h->clk_cap = 0; }
+        ALLOC(h->clk_dev, 3 * wgs);  // (the old buffer goes as the new one comes)
         h->clk_cap = wgs;
     }
     HIPCHK(hipMemsetAsync(h->clk_dev, 0, 3 * wgs * sizeof(unsigned long long), h->stream));
@@ -518,24 +526,24 @@ int launch_sim_loglike(demc_handle* h, KParams& k, long long n_prop) {
     SimKParams s;
     std::memset(&s, 0, sizeof s);
     s.n_groups = k.n_groups; s.Np = k.Np; s.D = k.D; s.a_lo = k.a_lo; s.n_act = k.n_act; s.group_offset = k.group_offset;
-    s.n_sim = h->sim_n; s.nhyper = h->user_nhyper > 0 ? h->user_nhyper - 1 : 0;
-    s.n_obs = h->N; s.iter = k.iter; s.seed = k.seed; s.sweep = k.sweep; s.entity_base = h->sim_entity_base;
-    s.bandwidth = h->sim_bw; s.n_pow = std::pow((double)h->sim_n, -0.2);
-    s.prop = k.prop; s.partial = k.partial; s.obs = h->data; s.hyper = h->user_hyper ? h->user_hyper + 1 : nullptr;
-    s.logtab = h->sim_logtab; s.glist = k.glist; s.k_max = h->sim_kmax;
-    const size_t lds = h->sim_est == EST_KDE_CHOICE ? sim_choice_lds(h->sim_n) : (size_t)h->sim_n * sizeof(double);
-    h->last.k2 = demc_handle::K2_SIM; h->last.k2_key = InstKey{{h->sim_kind, h->sim_est}};
-    if (h->sim_kind == SIM_USER) {
+    s.n_sim = h->m.sim_n; s.nhyper = h->m.user_nhyper > 0 ? h->m.user_nhyper - 1 : 0;
+    s.n_obs = h->m.N; s.iter = k.iter; s.seed = k.seed; s.sweep = k.sweep; s.entity_base = h->sim_entity_base;
+    s.bandwidth = h->m.sim_bw; s.n_pow = std::pow((double)h->m.sim_n, -0.2);
+    s.prop = k.prop; s.partial = k.partial; s.obs = h->m.data; s.hyper = h->m.user_hyper ? h->m.user_hyper + 1 : nullptr;
+    s.logtab = h->m.sim_logtab; s.glist = k.glist; s.k_max = h->m.sim_kmax;
+    const size_t lds = h->m.sim_est == EST_KDE_CHOICE ? sim_choice_lds(h->m.sim_n) : (size_t)h->m.sim_n * sizeof(double);
+    h->last.k2 = demc_handle::K2_SIM; h->last.k2_key = InstKey{{h->m.sim_kind, h->m.sim_est}};
+    if (h->m.sim_kind == SIM_USER) {
         size_t sz = sizeof s;
         void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &s, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
         tick(h, 2, true, true);
-        const hipError_t e = hipModuleLaunchKernel(h->user_kernel, (unsigned)n_prop, 1, 1, 256, 1, 1, 0, h->stream, nullptr, cfg);
+        const hipError_t e = hipModuleLaunchKernel(h->m.user_kernel, (unsigned)n_prop, 1, 1, 256, 1, 1, 0, h->stream, nullptr, cfg);
         tick(h, 2, false, true);
         if (e != hipSuccess) return fail(h, DEMC_EHIP, std::string("hipModuleLaunchKernel: ") + hipGetErrorString(e));
         return DEMC_OK;
     }
     const Inst<SimFn>* e = nullptr;
-    PICK(e, "k_sim_loglike", kSim, h->sim_kind, h->sim_est);
+    PICK(e, "k_sim_loglike", kSim, h->m.sim_kind, h->m.sim_est);
     tick(h, 2, true);
     LAUNCH_T(h, e->fn, dim3((unsigned)n_prop), dim3(256), lds, s);
     tick(h, 2, false);
@@ -547,14 +555,14 @@ int launch_ode_loglike(demc_handle* h, KParams& k) {
     OdeKParams o;
     std::memset(&o, 0, sizeof o);
     o.n_groups = k.n_groups; o.Np = k.Np; o.D = k.D; o.a_lo = k.a_lo; o.n_act = k.n_act;
-    o.T = (int)h->N; o.substeps = h->ode_substeps;
-    std::memcpy(o.u0, h->ode_u0, sizeof o.u0);
-    o.h = h->ode_h; o.h2 = 0.5 * h->ode_h; o.h6 = h->ode_h / 6.0;
-    o.prop = k.prop; o.partial = k.partial; o.obs = h->data; o.glist = k.glist;
+    o.T = (int)h->m.N; o.substeps = h->m.ode_substeps;
+    std::memcpy(o.u0, h->m.ode_u0, sizeof o.u0);
+    o.h = h->m.ode_h; o.h2 = 0.5 * h->m.ode_h; o.h6 = h->m.ode_h / 6.0;
+    o.prop = k.prop; o.partial = k.partial; o.obs = h->m.data; o.glist = k.glist;
     const Inst<OdeFn>* e = nullptr;
     PICK(e, "k_ode_loglike", kOde, ODE_LV);
     h->last.k2 = demc_handle::K2_ODE; h->last.k2_key = e->key;
-    const size_t lds = (size_t)h->N * 2 * sizeof(double);
+    const size_t lds = (size_t)h->m.N * 2 * sizeof(double);
     tick(h, 2, true);
     LAUNCH_T(h, e->fn, dim3((unsigned)k.n_groups, (unsigned)((k.n_act + 255) / 256)), dim3(256), lds, o);
     tick(h, 2, false);
@@ -565,7 +573,7 @@ int launch_ode_loglike(demc_handle* h, KParams& k) {
 int launch_loglike(demc_handle* h, KParams& k) {
     const long long n_prop = (long long)k.n_groups * k.n_act;
     if (n_prop == 0) return DEMC_OK;
-    switch (h->family) {
+    switch (h->m.family) {
         case FAM_MVN_FULL:
         case FAM_MVN_ISO: {
             const bool suff = h->c.loglike_mode == DEMC_LOGLIKE_SUFFSTAT;  // then K1 already formed S
@@ -574,16 +582,16 @@ int launch_loglike(demc_handle* h, KParams& k) {
                 // proposal blocks of 256 x observation chunks: enough workgroups for 8 waves per SIMD, chunks no shorter
                 // than 64 observations, at most the partial-sum workspace
                 const long long blocks = (n_prop + 255) / 256;
-                long long cap = h->N / 64;
+                long long cap = h->m.N / 64;
                 if (cap > h->partial_cap) cap = h->partial_cap;
                 if (cap < 1) cap = 1;
                 // The kernel is one long uniform loop per workgroup: the launch takes ceil(workgroups / resident workgroups)
                 // rounds of equal length, so the chunk count is chosen to fill the last round (cfg3: 128 blocks x 48 chunks =
                 // 4 full rounds of 1536 resident workgroups; 32 chunks would leave a third of the chip idle in round 3).
                 const Inst<ChunkFn>* e = nullptr;
-                PICK(e, "k_direct_mvn", kDirect, h->dp_direct);
-                if (int rc = wgs_per_cu(h, (const void*)e->fn, &h->direct_wgs_per_cu)) return rc;
-                const int n_chunks = chunks_filling_rounds(blocks, cap, (double)h->direct_wgs_per_cu * h->n_cus);
+                PICK(e, "k_direct_mvn", kDirect, h->m.dp_direct);
+                if (int rc = wgs_per_cu(h, (const void*)e->fn, &h->m.direct_wgs_per_cu)) return rc;
+                const int n_chunks = chunks_filling_rounds(blocks, cap, (double)h->m.direct_wgs_per_cu * h->n_cus);
                 h->last.k2 = demc_handle::K2_DIRECT_MVN; h->last.k2_key = e->key;
                 // timing on: every workgroup also leaves its shader-clock / reference-clock ticks (demc_timing_clock)
                 unsigned long long* clk = nullptr;
@@ -594,22 +602,22 @@ int launch_loglike(demc_handle* h, KParams& k) {
                 k.n_partials = n_chunks;
             } else if (!suff) {
                 const Inst<CrossFn>* e = nullptr;  // (k-steps per pass: the next instance up, demc_set_model keeps them a power of two <= 16)
-                PICK(e, "k_cross_mfma", kCross, h->ks_t <= 1 ? 1 : h->ks_t <= 2 ? 2 : h->ks_t <= 4 ? 4 : h->ks_t <= 8 ? 8 : 16, 4);
+                PICK(e, "k_cross_mfma", kCross, h->m.ks_t <= 1 ? 1 : h->m.ks_t <= 2 ? 2 : h->m.ks_t <= 4 ? 4 : h->m.ks_t <= 8 ? 8 : 16, 4);
                 h->last.k2 = demc_handle::K2_CROSS_MFMA; h->last.k2_key = e->key;
                 tick(h, 2, true);
                 // particle tiles of 256 (4 waves x MT=4 x 16) x observation chunks; chunks in multiples of 8 so that
                 // blockIdx % 8 (the XCD a block lands on) selects the chunk it streams
                 const long long n_ptiles = (n_prop + 255) / 256;
                 int n_chunks = 8;
-                while (n_ptiles * n_chunks < 1024 && n_chunks * 2 <= 32 && h->n_tiles / (n_chunks * 2) >= 16) n_chunks *= 2;
-                if (h->n_tiles < n_chunks) n_chunks = (int)(h->n_tiles > 0 ? h->n_tiles : 1);
-                const int n_kpass = h->n_kpass;
+                while (n_ptiles * n_chunks < 1024 && n_chunks * 2 <= 32 && h->m.n_tiles / (n_chunks * 2) >= 16) n_chunks *= 2;
+                if (h->m.n_tiles < n_chunks) n_chunks = (int)(h->m.n_tiles > 0 ? h->m.n_tiles : 1);
+                const int n_kpass = h->m.n_kpass;
                 if (n_chunks * n_kpass > h->partial_cap) n_chunks = h->partial_cap / n_kpass;
                 if (n_chunks < 1) return fail(h, DEMC_EINVAL, "data dimension too large for the partial-sum workspace");
                 const int grid2 = (int)(n_ptiles * n_chunks);
                 for (int kp = 0; kp < n_kpass; ++kp) {
-                    const int k0 = kp * 4 * h->ks_t, part0 = kp * n_chunks;
-                    LAUNCH_T(h, e->fn, dim3(grid2), dim3(256), 0, k, h->Ypad, h->dpad, k0, h->Xf, h->n_tiles, n_chunks, part0);
+                    const int k0 = kp * 4 * h->m.ks_t, part0 = kp * n_chunks;
+                    LAUNCH_T(h, e->fn, dim3(grid2), dim3(256), 0, k, h->m.Ypad.get(), h->m.dpad, k0, h->m.Xf.get(), h->m.n_tiles, n_chunks, part0);
                 }
                 tick(h, 2, false);
                 k.n_partials = n_chunks * n_kpass;
@@ -620,18 +628,18 @@ int launch_loglike(demc_handle* h, KParams& k) {
         case FAM_LBA:
         case FAM_LNR:
         case FAM_RASTRIGIN: {
-            long long cap = h->N / 32;
+            long long cap = h->m.N / 32;
             if (cap > h->partial_cap) cap = h->partial_cap;
-            if (cap < 1 || h->family == FAM_RASTRIGIN) cap = 1;
+            if (cap < 1 || h->m.family == FAM_RASTRIGIN) cap = 1;
             if (int rc = wgs_per_cu(h, (const void*)k_obs_loglike, &h->obs_wgs_per_cu)) return rc;
             int n_chunks = chunks_filling_rounds((n_prop + 255) / 256, cap, (double)h->obs_wgs_per_cu * h->n_cus);
-            if (h->family == FAM_LBA) {
+            if (h->m.family == FAM_LBA) {
                 // a wave per proposal, lanes across the (sorted) trials: k_lba_wave.  Chunks of whole batches (512 trials), at least two a chunk.
                 const Inst<ChunkFn>*e = nullptr, *e3 = nullptr;
-                PICK(e, "k_lba_wave", kLbaWave, h->n_acc == 3 ? 3 : h->n_acc == 2 ? 2 : 0);
+                PICK(e, "k_lba_wave", kLbaWave, h->m.n_acc == 3 ? 3 : h->m.n_acc == 2 ? 2 : 0);
                 PICK(e3, "k_lba_wave", kLbaWave, 3);  // (the occupancy that sizes the chunks is the three-accumulator instance's, whichever runs)
                 if (int rc = wgs_per_cu(h, (const void*)e3->fn, &h->lba_wave_wgs_per_cu)) return rc;
-                long long capw = h->N / 1024;
+                long long capw = h->m.N / 1024;
                 if (capw > h->partial_cap) capw = h->partial_cap;
                 if (capw < 1) capw = 1;
                 int nc = chunks_filling_rounds((n_prop + 3) / 4, capw, (double)h->lba_wave_wgs_per_cu * h->n_cus);
@@ -653,23 +661,23 @@ int launch_loglike(demc_handle* h, KParams& k) {
         } break;
         case FAM_USER: {
             long long want = (262144 + n_prop - 1) / n_prop;
-            long long cap = h->N / 32;
+            long long cap = h->m.N / 32;
             if (cap < 1) cap = 1;
             if (want > cap) want = cap;
             if (want > h->partial_cap) want = h->partial_cap;
-            if (h->user_row) want = 1;
+            if (h->m.user_row) want = 1;
             UserKParams u;
             u.n_groups = k.n_groups; u.Np = k.Np; u.D = k.D; u.a_lo = k.a_lo; u.n_act = k.n_act; u.n_chunks = (int)want;
-            u.nhyper = h->user_nhyper; u.with_prior = h->c.fitness_kind == DEMC_FITNESS_POSTERIOR ? 1 : 0;
-            u.N = h->N; u.P = h->P; u.prop = k.prop; u.partial = k.partial;
-            u.data = h->data; u.hyper = h->user_hyper; u.dims = h->user_dims; u.glist = k.glist; u.ndims = h->user_ndims; u.pad = 0;
+            u.nhyper = h->m.user_nhyper; u.with_prior = h->c.fitness_kind == DEMC_FITNESS_POSTERIOR ? 1 : 0;
+            u.N = h->m.N; u.P = h->P; u.prop = k.prop; u.partial = k.partial;
+            u.data = h->m.data; u.hyper = h->m.user_hyper; u.dims = h->m.user_dims; u.glist = k.glist; u.ndims = h->m.user_ndims; u.pad = 0;
             size_t sz = sizeof u;
             void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &u, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
-            h->last.k2 = h->user_row ? demc_handle::K2_USER_ROW : demc_handle::K2_USER;
+            h->last.k2 = h->m.user_row ? demc_handle::K2_USER_ROW : demc_handle::K2_USER;
             tick(h, 2, true, true);
-            hipError_t e = h->user_row
-                ? hipModuleLaunchKernel(h->user_kernel, (unsigned)n_prop, 1, 1, 256, 1, 1, 0, h->stream, nullptr, cfg)
-                : hipModuleLaunchKernel(h->user_kernel, (unsigned)((n_prop + 255) / 256), (unsigned)want, 1, 256, 1, 1, 0,
+            hipError_t e = h->m.user_row
+                ? hipModuleLaunchKernel(h->m.user_kernel, (unsigned)n_prop, 1, 1, 256, 1, 1, 0, h->stream, nullptr, cfg)
+                : hipModuleLaunchKernel(h->m.user_kernel, (unsigned)((n_prop + 255) / 256), (unsigned)want, 1, 256, 1, 1, 0,
                                         h->stream, nullptr, cfg);
             tick(h, 2, false, true);
             if (e != hipSuccess) return fail(h, DEMC_EHIP, std::string("hipModuleLaunchKernel: ") + hipGetErrorString(e));
@@ -705,16 +713,16 @@ void set_tail_flags(demc_handle* h, KParams& k) {
     const bool suff = c.loglike_mode == DEMC_LOGLIKE_SUFFSTAT;
     // K1 tails: MvNormal preparation always; the whole update when the likelihood is O(D^2) given data-only
     // statistics and a phase writes only rows that no other workgroup reads (two_colour, or the identity pass)
-    k.fuse_prep = is_mvn(h->family) ? 1 : 0;
-    k.prep_mfma = (h->family == FAM_MVN_FULL && k.lpp >= 4 && k.lpp <= 16 && h->d <= 32) ? 1 : 0;
-    k.sx = (k.fuse_prep && suff) ? h->sx : nullptr;
-    k.Ainv = (h->family == FAM_MVN_FULL) ? h->Ainv : nullptr;
+    k.fuse_prep = is_mvn(h->m.family) ? 1 : 0;
+    k.prep_mfma = (h->m.family == FAM_MVN_FULL && k.lpp >= 4 && k.lpp <= 16 && h->m.d <= 32) ? 1 : 0;
+    k.sx = (k.fuse_prep && suff) ? h->m.sx : nullptr;
+    k.Ainv = (h->m.family == FAM_MVN_FULL) ? h->m.Ainv : nullptr;
     // small-N scalar-data families: the sub-group of a particle sums the per-observation terms itself
     // (hierarchical families: one term per subject, i.e. O(D) like the proposal itself; their Gaussian form has p.d
     // observations behind every subject)
-    const long long obs_work = (h->family == FAM_HIER_GAUSSIAN) ? h->N * (h->d > 0 ? h->d : 1) : h->N;
-    const bool cheap_obs = ((h->family == FAM_GAUSSIAN || h->family == FAM_BINOMIAL || h->family == FAM_RASTRIGIN) &&
-                            h->N / k.lpp <= 512) ||
+    const long long obs_work = (h->m.family == FAM_HIER_GAUSSIAN) ? h->m.N * (h->m.d > 0 ? h->m.d : 1) : h->m.N;
+    const bool cheap_obs = ((h->m.family == FAM_GAUSSIAN || h->m.family == FAM_BINOMIAL || h->m.family == FAM_RASTRIGIN) &&
+                            h->m.N / k.lpp <= 512) ||
                            (h->hier_scr && obs_work / k.lpp <= 4096);
     // nothing a moving particle reads can move in the same launch: two_colour (partners rest), the identity pass, and the
     // sequential schedule (one particle per group and launch, handled by that group's only workgroup)
@@ -738,7 +746,7 @@ void set_tail_flags(demc_handle* h, KParams& k) {
 int lean_level(const demc_handle* h, int partner_kind, int mode = MODE_STEP) {
     const demc_config& c = h->c;
     const bool base = mode == MODE_STEP && c.proposal_kind == 0 && c.partner_kind == partner_kind && c.update_kind == 0 &&
-                      c.fitness_kind == 0 && c.kappa == 1.0 && !c.trace && !h->rp_active;
+                      c.fitness_kind == 0 && c.kappa == 1.0 && !c.trace && !h->rp.active;
     return !base ? 0 : (c.theta_snooker == 0.0 && c.n_blocks == 0) ? 1 : 2;
 }
 int tail_of(const KParams& k) { return k.prep_mfma ? TAIL_PREP_MFMA : k.fuse_prep ? TAIL_PREP : k.fuse_obs ? TAIL_OBS : TAIL_NONE; }
@@ -771,7 +779,7 @@ BlockSpan block_span(int n_run, unsigned in, const int* start, int D) {
 bool frozen_possible(const demc_handle* h) {
     const demc_config& c = h->c;
     const int n_act = c.schedule == DEMC_SCHED_TWO_COLOUR ? c.Np - c.Np / 2 : c.schedule == DEMC_SCHED_SEQUENTIAL ? 1 : c.Np;
-    return (h->family == FAM_HIER_BINOMIAL || h->family == FAM_HIER_GAUSSIAN) && h->hier_scr && h->lpp > 64 && c.n_blocks >= 1 &&
+    return (h->m.family == FAM_HIER_BINOMIAL || h->m.family == FAM_HIER_GAUSSIAN) && h->hier_scr && h->lpp > 64 && c.n_blocks >= 1 &&
            c.fuse == 0 && !c.trace && c.kappa == 1.0 && (long long)h->geo_groups * n_act >= 2LL * h->n_cus;
 }
 
@@ -798,11 +806,11 @@ int launch_phase(demc_handle* h, KParams k) {
     k.own_in_pool = (k.a_lo >= k.pool_lo && k.a_lo + k.n_act <= k.pool_lo + k.pool_n) ? 1 : 0;
     k.tile_rows = k.pool_n + (k.own_in_pool ? 0 : (int)per_split);
     const size_t lds_tile = h->k1_lds - h->k1_tile_bytes + (size_t)k.tile_rows * c.D * sizeof(double);  // <= k1_lds
-    k.plan = (tile && k.mode == MODE_STEP && k.lpp >= 4 && k.lpp <= 64 && lds_tile + plan_bytes <= kMaxDynLds && !h->rp_active) ? 1 : 0;
+    k.plan = (tile && k.mode == MODE_STEP && k.lpp >= 4 && k.lpp <= 64 && lds_tile + plan_bytes <= kMaxDynLds && !h->rp.active) ? 1 : 0;
     // long rows of a hierarchical family, whole update fused: the dedicated one-pass kernel (demc_longrow.hpp)
     const size_t cdf_doubles = k.pool_n > 256 ? (size_t)k.pool_n + ((size_t)k.pool_n + 15) / 16 : 0;
     const size_t lr_lds = ((((size_t)c.D + 1) & ~(size_t)1) + cdf_doubles) * sizeof(double);
-    const bool lr_shape = k.lpp > 64 && h->hier_scr && k.mode == MODE_STEP && !h->rp_active && c.fuse != 2 && h->n_seg > 0 && lr_lds <= kMaxDynLds;
+    const bool lr_shape = k.lpp > 64 && h->hier_scr && k.mode == MODE_STEP && !h->rp.active && c.fuse != 2 && h->n_seg > 0 && lr_lds <= kMaxDynLds;
     // DE-MC_Z INSIDE burn-in (Examples/Hierarchical_Example.jl:103-114 spends half its run there): random_gamma's base particle
     // (crossover.jl:156-164) is a row of the current population, which another workgroup of this synchronous launch may be writing,
     // so set_tail_flags left the sweep unfused (K1 -> k_hier_loglike -> K3 through the proposal buffer: 2.3x the time).  The rows
@@ -814,7 +822,7 @@ int launch_phase(demc_handle* h, KParams k) {
     const bool suff_mvn = k.fuse_prep && c.loglike_mode == DEMC_LOGLIKE_SUFFSTAT;
     bool snapshot = false, have_snap2 = false;
     if (!k.fuse_accept && k.mode == MODE_STEP && c.schedule == DEMC_SCHED_SYNCHRONOUS && c.partner_kind == DEMC_PARTNER_HISTORY &&
-        c.proposal_kind == 0 && k.iter <= c.burnin && (h->tf_cheap_obs || suff_mvn) && c.fuse == 0 && !k.trace && !h->rp_active &&
+        c.proposal_kind == 0 && k.iter <= c.burnin && (h->tf_cheap_obs || suff_mvn) && c.fuse == 0 && !k.trace && !h->rp.active &&
         k.theta == h->theta) {
         // (the copies follow the choice of the kernel: a frozen sweep reads its base row at the block's scalars only)
         snapshot = true;
@@ -857,7 +865,7 @@ int launch_phase(demc_handle* h, KParams k) {
         // per thread and round behind 16-byte loads, which the hierarchical Binomial family's even rows allow)
         const bool big = blk.longest > 256;
         const bool on = blk.inside >= 1 && (long long)h->geo_groups * k.n_act >= 2LL * h->n_cus &&
-                        (big ? h->family == FAM_HIER_BINOMIAL && (c.D & 1) == 0 : blk.inside <= kFrozenMax);
+                        (big ? h->m.family == FAM_HIER_BINOMIAL && (c.D & 1) == 0 : blk.inside <= kFrozenMax);
         if (on) {
             if (snapshot)
                 if (int rc = take_snapshot(true)) return rc;
@@ -944,7 +952,7 @@ bool has_normal_ref(const demc_handle* h) {
 // as [one entry for the 30 means | one for sigma]: any other table takes the general row length
 int compiled_row_length(const demc_handle* h) {
     const int D = h->c.D;
-    if (h->family == FAM_MVN_ISO) return (D == 31 && h->n_seg == 2 && h->seg_start[1] == 30) ? 31 : 0;
+    if (h->m.family == FAM_MVN_ISO) return (D == 31 && h->n_seg == 2 && h->seg_start[1] == 30) ? 31 : 0;
     return (h->n_seg == 1 && (D == 32 || D == 8)) ? D : 0;
 }
 
@@ -959,8 +967,8 @@ int plan_resident(demc_handle* h) {
     const int lpp_max = pow2_ceil((c.D + 1) / 2);
     if (lpp_max > 64) return DEMC_OK;
     const int n_act = c.Np - c.Np / 2;
-    const size_t D = (size_t)c.D, Np = (size_t)c.Np, d = (size_t)h->d;
-    const bool mvn = is_mvn(h->family);
+    const size_t D = (size_t)c.D, Np = (size_t)c.Np, d = (size_t)h->m.d;
+    const bool mvn = is_mvn(h->m.family);
     // geometry for a thread budget: lanes per particle, workgroup size, LDS bytes; false when the update cannot be fused or the
     // group does not fit
     int lpp = 0, wg = 0, tail = TAIL_NONE;
@@ -976,7 +984,7 @@ int plan_resident(demc_handle* h) {
         tail = tail_of(k);
         scr_doubles = (k.fuse_prep || k.fuse_obs) ? (size_t)(wg / lpp) * (D + 2) : 0;
         const size_t doubles =
-            Np * D + Np + (Np + (Np + 15) / 16) + ((h->family == FAM_MVN_FULL && h->ainv_lds) ? d * d : 0) + (mvn ? d : 0) + scr_doubles;
+            Np * D + Np + (Np + (Np + 15) / 16) + ((h->m.family == FAM_MVN_FULL && h->ainv_lds) ? d * d : 0) + (mvn ? d : 0) + scr_doubles;
         bytes = doubles * sizeof(double) + (size_t)n_act * (4 * sizeof(double) + 4 * sizeof(int));
         return bytes <= kMaxDynLds;
     };
@@ -1005,9 +1013,9 @@ int plan_stream(demc_handle* h) {
     g.ok = false;
     f = FormPlan();
     const bool direct = c.loglike_mode == DEMC_LOGLIKE_DIRECT;
-    if (!is_mvn(h->family) || (c.loglike_mode != DEMC_LOGLIKE_STREAMING && !direct) || c.fuse != 0 || c.schedule != DEMC_SCHED_TWO_COLOUR ||
+    if (!is_mvn(h->m.family) || (c.loglike_mode != DEMC_LOGLIKE_STREAMING && !direct) || c.fuse != 0 || c.schedule != DEMC_SCHED_TWO_COLOUR ||
         c.partner_kind != DEMC_PARTNER_CURRENT || c.Np < 4 || h->n_cus < 1 || h->geo_groups > h->n_cus || c.n_groups > h->n_cus ||
-        h->dpad > 64 || h->n_kpass != 1)
+        h->m.dpad > 64 || h->m.n_kpass != 1)
         return DEMC_OK;
     // Whether the form applies and into how many chunks C a group's observation tiles are cut is decided from the groups of
     // the WHOLE population (geometry_groups), not from this shard's: C fixes the summation order of the cross terms, and a
@@ -1015,7 +1023,7 @@ int plan_stream(demc_handle* h) {
     const int gg = h->geo_groups > c.n_groups ? h->geo_groups : c.n_groups;
     const int nact_max = c.Np - c.Np / 2;
     if (nact_max > 512) return DEMC_OK;
-    const double phase_flop = 2.0 * (double)nact_max * gg * (double)h->N * h->dpad;
+    const double phase_flop = 2.0 * (double)nact_max * gg * (double)h->m.N * h->m.dpad;
     if (phase_flop / 78.6e12 > 300e-6) return DEMC_OK;
     const int lpp_max = pow2_ceil((c.D + 1) / 2);
     if (lpp_max > 64) return DEMC_OK;
@@ -1023,16 +1031,16 @@ int plan_stream(demc_handle* h) {
     const int wg = nact_max * lpp <= 256 ? 256 : 512, ppp = wg / lpp;
     const int rows = ((nact_max + ppp - 1) / ppp) * ppp;
     int C = 1;
-    while (2 * C * gg <= h->n_cus && h->n_tiles / (2 * C) >= 8 && 2 * C <= 32) C *= 2;
-    const int chunk = (h->n_tiles + C - 1) / C;
-    const size_t D = (size_t)c.D, Np = (size_t)c.Np, d = (size_t)h->d;
+    while (2 * C * gg <= h->n_cus && h->m.n_tiles / (2 * C) >= 8 && 2 * C <= 32) C *= 2;
+    const int chunk = (h->m.n_tiles + C - 1) / C;
+    const size_t D = (size_t)c.D, Np = (size_t)c.Np, d = (size_t)h->m.d;
     const size_t scr_doubles = (size_t)rows * (D + 6);
-    const size_t doubles = Np * D + Np + (Np + (Np + 15) / 16) + ((h->family == FAM_MVN_FULL && h->ainv_lds) ? d * d : 0) + d + scr_doubles +
-                           (size_t)rows * h->dpad + (size_t)(wg / 64) * nact_max;
+    const size_t doubles = Np * D + Np + (Np + (Np + 15) / 16) + ((h->m.family == FAM_MVN_FULL && h->ainv_lds) ? d * d : 0) + d + scr_doubles +
+                           (size_t)rows * h->m.dpad + (size_t)(wg / 64) * nact_max;
     size_t bytes = doubles * sizeof(double) + (size_t)nact_max * (4 * sizeof(double) + 4 * sizeof(int)) +
                    2 * sizeof(unsigned) * (size_t)C * nact_max + 16;
     if (bytes > kMaxDynLds) return DEMC_OK;
-    const size_t xbytes = (size_t)(chunk + 1) * (h->dpad / 4) * 64 * sizeof(double);  // + the all-zero tail tile
+    const size_t xbytes = (size_t)(chunk + 1) * (h->m.dpad / 4) * 64 * sizeof(double);  // + the all-zero tail tile
     const int x_lds = (bytes + xbytes <= kMaxDynLds) ? 1 : 0;
     if (x_lds) bytes += xbytes;
     if (!direct) {  // (k_propose's streaming form has the two tails an MvNormal model can take: PREP_MFMA, else PREP)
@@ -1054,11 +1062,10 @@ size_t granule_bytes(const demc_handle* h) { return 2 * (size_t)h->c.n_groups * 
 void alloc_stream(demc_handle* h) {
     StreamGeo& g = h->st;
     if (!g.ok) return;
-    if (g.gran) { hipFree(g.gran); g.gran = nullptr; }
-    g.ok = hipMalloc((void**)&g.gran, granule_bytes(h)) == hipSuccess;
+    g.ok = g.gran.alloc(granule_bytes(h) / sizeof(unsigned long long)) == hipSuccess;
     if (g.ok && !g.err) {
-        g.ok = hipHostMalloc((void**)&g.err, sizeof(unsigned), hipHostMallocMapped) == hipSuccess;
-        if (g.ok) *g.err = 0u;
+        g.ok = g.err.alloc(1, hipHostMallocMapped) == hipSuccess;
+        if (g.ok) *g.err.get() = 0u;
     }
     if (!g.ok) h->form[FORM_STREAM].ok = false;
 }
@@ -1075,10 +1082,10 @@ int plan_lean(demc_handle* h) {
     // FORM_LEAN_OBS (demc_resobs.hpp): Gaussian, Binomial and the LNR with a handful of parameters (a lane per scalar of a
     // sixteen-lane particle) and few enough observations for sixteen lanes to walk them; the group, its scratch rows and -- LNR --
     // the log Phi(-z) table in LDS
-    if ((h->family == FAM_GAUSSIAN || h->family == FAM_BINOMIAL || h->family == FAM_LNR) && c.D <= 16 && c.fuse == 0 &&
-        c.schedule == DEMC_SCHED_TWO_COLOUR && c.partner_kind == DEMC_PARTNER_CURRENT && c.Np >= 4 && c.Np <= 512 && h->N / 16 <= 512) {
+    if ((h->m.family == FAM_GAUSSIAN || h->m.family == FAM_BINOMIAL || h->m.family == FAM_LNR) && c.D <= 16 && c.fuse == 0 &&
+        c.schedule == DEMC_SCHED_TWO_COLOUR && c.partner_kind == DEMC_PARTNER_CURRENT && c.Np >= 4 && c.Np <= 512 && h->m.N / 16 <= 512) {
         const size_t doubles = (size_t)c.Np * c.D + (size_t)c.Np + (size_t)nact_max + (size_t)(256 / 16) * c.D +
-                               (h->family == FAM_LNR ? (size_t)kLogPhiRows * kLogPhiRow : 0);
+                               (h->m.family == FAM_LNR ? (size_t)kLogPhiRows * kLogPhiRow : 0);
         if (doubles * sizeof(double) <= kMaxDynLds) {
             FormPlan& f = h->form[FORM_LEAN_OBS];
             PICK(f.k1[0], "k_res_obs", kResObs, 256);
@@ -1088,8 +1095,8 @@ int plan_lean(demc_handle* h) {
     // FORM_LEAN_Z: DE-MC_Z (history partners, the synchronous schedule) on MvNormal-full in SUFFSTAT mode: the lean body with
     // partner rows from the history, one launch per iteration -- all it needs in LDS are select_base's cumulative weights and the
     // centred rows (... and on MvNormal(mu, sigma^2 I) with sigma a parameter, D = d + 1: the ISO instances of the same body)
-    const bool iso = h->family == FAM_MVN_ISO;
-    if (((h->family == FAM_MVN_FULL && c.D == h->d) || (iso && c.D == h->d + 1)) && c.D <= 32 && c.fuse == 0 &&
+    const bool iso = h->m.family == FAM_MVN_ISO;
+    if (((h->m.family == FAM_MVN_FULL && c.D == h->m.d) || (iso && c.D == h->m.d + 1)) && c.D <= 32 && c.fuse == 0 &&
         c.schedule == DEMC_SCHED_SYNCHRONOUS && c.partner_kind == DEMC_PARTNER_HISTORY && c.loglike_mode == DEMC_LOGLIKE_SUFFSTAT &&
         c.Np >= 4 && nact_max * 4 <= 512 && h->hist) {
         FormPlan& f = h->form[FORM_LEAN_Z];
@@ -1104,7 +1111,7 @@ int plan_lean(demc_handle* h) {
         return DEMC_OK;
     }
     // the two_colour forms (demc_resmvn.hpp): MvNormal full Sigma, D = d <= 32, one pass per phase
-    if (h->family != FAM_MVN_FULL || c.D != h->d || h->d > 32 || c.fuse != 0 || c.schedule != DEMC_SCHED_TWO_COLOUR ||
+    if (h->m.family != FAM_MVN_FULL || c.D != h->m.d || h->m.d > 32 || c.fuse != 0 || c.schedule != DEMC_SCHED_TWO_COLOUR ||
         c.partner_kind != DEMC_PARTNER_CURRENT || c.Np < 4 || nact_max * 4 > 512)
         return DEMC_OK;
     // (DIRECT at D = 8: 512 threads whatever the group's size -- two waves per SIMD for the residual loop, which one wave per SIMD runs
@@ -1126,11 +1133,11 @@ int plan_lean(demc_handle* h) {
     const StreamGeo& g = h->st;
     if (!g.ok || (wg != 256 && !dir8)) return DEMC_OK;
     // (DIRECT: the instances with the row length compiled in, the chunk of whitened rows in LDS)
-    if (dir && !(dt != 0 && h->dp_direct == c.D && h->dpad == c.D && g.x_lds)) return DEMC_OK;
-    size_t bytes = base + ((size_t)(wg / 4) * h->dpad + (size_t)(dir ? wg / 16 : wg / 64) * nact_max) * sizeof(double) + 16;  // (DIRECT: a partial sum per 16-lane row)
+    if (dir && !(dt != 0 && h->m.dp_direct == c.D && h->m.dpad == c.D && g.x_lds)) return DEMC_OK;
+    size_t bytes = base + ((size_t)(wg / 4) * h->m.dpad + (size_t)(dir ? wg / 16 : wg / 64) * nact_max) * sizeof(double) + 16;  // (DIRECT: a partial sum per 16-lane row)
     if (bytes > kMaxDynLds) return DEMC_OK;
     // (the X chunk rides in LDS exactly when plan_stream found room for it; this kernel's other buffers are no larger)
-    if (g.x_lds) bytes += (size_t)(g.chunk_tiles + 1) * (h->dpad / 4) * 64 * sizeof(double);
+    if (g.x_lds) bytes += (size_t)(g.chunk_tiles + 1) * (h->m.dpad / 4) * 64 * sizeof(double);
     if (bytes > kMaxDynLds) return DEMC_OK;
     FormPlan& f = h->form[dir ? FORM_LEAN_DIRECT : FORM_LEAN_STREAMING];
     PICK(f.k1[0], "k_res_mvn", kResMvn, wg, true, dt, 0, 1, false, dir);  // (DIRECT: <512, 8> and <256, 32>, what the tests above leave)
@@ -1147,7 +1154,7 @@ int plan_lean(demc_handle* h) {
 Form choose_form(const demc_handle* h) {
     const FormPlan* f = h->form;
     // a replay hands over the caller's draws, which only the per-phase kernels read: no multi-iteration form, no lean DE-MC_Z body
-    if (h->rp_active) return FORM_PHASE;
+    if (h->rp.active) return FORM_PHASE;
     const bool whole = h->cur_glist == nullptr;  // a subset of the groups never takes a spin_waiting form; it may take the others
     const bool plain = lean_level(h, DEMC_PARTNER_CURRENT) == 1;  // the lean two_colour kernels: no trace, snooker updates or blocks
     if (f[FORM_LEAN_DIRECT].ok && plain && whole) return FORM_LEAN_DIRECT;  // DIRECT: the one whole-update form it has
@@ -1171,7 +1178,7 @@ int iterations_per_launch(Form f) { return (f == FORM_PHASE || f == FORM_LEAN_Z)
 int stream_fields(demc_handle* h, KParams& k) {
     const StreamGeo& g = h->st;
     k.st_C = g.C; k.st_nact_max = g.nact_max; k.st_x_lds = g.x_lds; k.st_chunk_tiles = g.chunk_tiles;
-    k.n_tiles = h->n_tiles; k.Xf = h->Xf; k.st_gran = g.gran; k.st_err = g.err;
+    k.n_tiles = h->m.n_tiles; k.Xf = h->m.Xf; k.st_gran = g.gran; k.st_err = g.err;
     // Every workgroup of this grid must be resident at once (the workgroups of a group spin on each other's progress).  The
     // grid is sized for that by construction -- at most one workgroup per CU (plan_stream: n_groups * C <= CUs, and each
     // takes most of a CU's LDS) -- so a plain launch has the same residency as a cooperative one, without its launch-time
@@ -1203,7 +1210,7 @@ int launch_form(demc_handle* h, Form form, long long iter0, int n_iters) {
         }
         e = f.k1[lean_level(h, DEMC_PARTNER_CURRENT)];
     } else if (form == FORM_LEAN_SUFFSTAT || form == FORM_LEAN_Z)
-        k.sx = h->sx;
+        k.sx = h->m.sx;
     if (form == FORM_LEAN_Z) {
         // (the HIST instances hold back the first half's stores for ONE iteration's store_row and form the cdf once per launch: the
         // precondition is checked here, and again by the kernel -- its phase loop runs no trip for any other count)
@@ -1291,17 +1298,15 @@ int plan_snap2(demc_handle* h) {
     if (!want) {
         if (h->snap2 || h->snap2_w) {
             HIPCHK(hipStreamSynchronize(h->stream));
-            if (h->snap2) hipFree(h->snap2);
-            if (h->snap2_w) hipFree(h->snap2_w);
-            h->snap2 = nullptr; h->snap2_w = nullptr; h->snap2_iter = -1;
+            h->snap2.reset(); h->snap2_w.reset(); h->snap2_iter = -1;
         }
         return DEMC_OK;
     }
     if (h->snap2) return DEMC_OK;
     const size_t bytes = sizeof(double) * (size_t)h->P * c.D;
-    if (hipMalloc((void**)&h->snap2, bytes) != hipSuccess) { h->snap2 = nullptr; (void)hipGetLastError(); }
-    if (h->snap2 && hipMalloc((void**)&h->snap2_w, sizeof(double) * (size_t)h->P) != hipSuccess) {
-        hipFree(h->snap2); h->snap2 = nullptr; h->snap2_w = nullptr; (void)hipGetLastError();
+    if (h->snap2.alloc((size_t)h->P * c.D) != hipSuccess) (void)hipGetLastError();
+    if (h->snap2 && h->snap2_w.alloc((size_t)h->P) != hipSuccess) {
+        h->snap2.reset(); (void)hipGetLastError();
     }
     if (!h->snap2)
         h->err = "note: no memory for the by-product snapshot (" + std::to_string(bytes) + " bytes): DE-MC_Z sweeps inside burn-in copy the population instead";
@@ -1320,15 +1325,15 @@ int size_k1_lds(demc_handle* h) {
     const demc_config& c = h->c;
     const size_t D = (size_t)c.D;
     const size_t cdf = ((size_t)c.Np + ((size_t)c.Np + 15) / 16) * sizeof(double);
-    size_t ainv = (h->family == FAM_MVN_FULL) ? (size_t)h->d * h->d * sizeof(double) : 0;
+    size_t ainv = (h->m.family == FAM_MVN_FULL) ? (size_t)h->m.d * h->m.d * sizeof(double) : 0;
     h->ainv_lds = ainv <= 40 * 1024 ? 1 : 0;  // d <= 71: beside the tile; wider data read A^-1 from L2
     if (!h->ainv_lds) ainv = 0;
-    const size_t xb = is_mvn(h->family) ? (size_t)h->d * sizeof(double) : 0;
+    const size_t xb = is_mvn(h->m.family) ? (size_t)h->m.d * sizeof(double) : 0;
     const size_t scr_rows = (size_t)(h->lpp >= 256 ? 1 : 256 / h->lpp) * (D + 2) * sizeof(double);
-    const bool hier = h->family == FAM_HIER_BINOMIAL || h->family == FAM_HIER_GAUSSIAN;
+    const bool hier = h->m.family == FAM_HIER_BINOMIAL || h->m.family == FAM_HIER_GAUSSIAN;
     h->hier_scr = hier && scr_rows <= 96 * 1024;  // theta' of the pass fits in LDS: the subjects can be summed in K1
-    const bool scr_fam = is_mvn(h->family) || h->family == FAM_GAUSSIAN || h->family == FAM_BINOMIAL ||
-                         h->family == FAM_RASTRIGIN || h->hier_scr;
+    const bool scr_fam = is_mvn(h->m.family) || h->m.family == FAM_GAUSSIAN || h->m.family == FAM_BINOMIAL ||
+                         h->m.family == FAM_RASTRIGIN || h->hier_scr;
     const size_t scr = scr_fam ? scr_rows : 0;
     const size_t tile = (size_t)c.Np * D * sizeof(double);
     h->tile_in_lds = (tile + cdf + ainv + xb + scr <= 96 * 1024) ? 1 : 0;
@@ -1353,15 +1358,41 @@ int size_k1_lds(demc_handle* h) {
     return plan_snap2(h);
 }
 
-void free_replay(demc_handle* h) {
-    void* ptrs[] = {h->rp_group, h->rp_part, h->rp_noise, h->rp_znoise, h->rp_recomb, h->rp_partner, h->rp_mig_particle, h->rp_mig_groups};
-    for (void* p : ptrs)
-        if (p) hipFree(p);
-    h->rp_group = h->rp_part = h->rp_noise = h->rp_znoise = h->rp_recomb = nullptr;
-    h->rp_partner = h->rp_mig_particle = nullptr;
-    h->rp_mig_groups = nullptr;
-    h->rp_n_mig = 0;
-    h->rp_active = h->rp_has_step = false;
+// The one place a model is released: nothing on the stream may still read it, then every buffer, the JIT module and every
+// field go with the record.  What a REFUSED set-model call leaves behind differs by entry point and is kept as it was:
+// demc_set_model_sim validates everything first, so a refusal leaves the previous model in force; demc_set_model and the source
+// entry points release first (after their checks of the call's shape), so a refusal past that point leaves no model.
+int clear_model(demc_handle* h) {
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->m = Model{};
+    return DEMC_OK;
+}
+
+// hiprtc: `src` compiled for the library's architecture, loaded, and its kernel `entry` looked up.  `what` names the text in the
+// message of a source that does not compile (the log follows it).
+template <size_t NOPT>
+int compile_module(demc_handle* h, const std::string& src, const char* file, const char* (&opts)[NOPT], const char* what,
+                   const char* entry, Module& mod, hipFunction_t* fn) {
+    hiprtcProgram prog;
+    if (hiprtcCreateProgram(&prog, src.c_str(), file, 0, nullptr, nullptr) != HIPRTC_SUCCESS)
+        return fail(h, DEMC_EHIP, "hiprtcCreateProgram failed");
+    const hiprtcResult cr = hiprtcCompileProgram(prog, (int)NOPT, opts);
+    if (cr != HIPRTC_SUCCESS) {
+        size_t ls = 0;
+        hiprtcGetProgramLogSize(prog, &ls);
+        std::string log(ls, '\0');
+        if (ls) hiprtcGetProgramLog(prog, &log[0]);
+        hiprtcDestroyProgram(&prog);
+        return fail(h, DEMC_EINVAL, std::string(what) + " does not compile: " + hiprtcGetErrorString(cr) + "\n" + log);
+    }
+    size_t cs = 0;
+    hiprtcGetCodeSize(prog, &cs);
+    std::vector<char> code(cs);
+    hiprtcGetCode(prog, code.data());
+    hiprtcDestroyProgram(&prog);
+    HIPCHK(mod.load(code.data()));
+    HIPCHK(hipModuleGetFunction(fn, mod, entry));
+    return DEMC_OK;
 }
 
 bool chol_inv(const double* S, int d, std::vector<double>& Ainv, double& logdet, std::vector<double>* Linv = nullptr) {
@@ -1449,8 +1480,8 @@ int32_t demc_create(const demc_config* cfg, demc_handle** out) {
     ALLOC(h->dimseg, (size_t)kMaxDimSeg);
     for (int i = 0; i < demc_handle::kGlistRing; ++i) {
         ALLOC(h->glist_buf[i], (size_t)c.n_groups);
-        HIPCHK(hipHostMalloc((void**)&h->glist_pin[i], (size_t)c.n_groups * sizeof(int), hipHostMallocDefault));
-        HIPCHK(hipEventCreateWithFlags(&h->glist_ev[i], hipEventDisableTiming));
+        HIPCHK(h->glist_pin[i].alloc((size_t)c.n_groups, hipHostMallocDefault));
+        HIPCHK(h->glist_ev[i].create(hipEventDisableTiming));
     }
     ALLOC(h->mig_rows, (size_t)c.n_groups_total * (D + 3));
     ALLOC(h->scratch_theta, P * D); ALLOC(h->scratch_w, P);
@@ -1522,38 +1553,11 @@ int32_t demc_destroy(demc_handle* h) {
     drain_events(h);
     for (hipEvent_t e : h->event_pool) hipEventDestroy(e);
     h->event_pool.clear();
-    void* ptrs[] = {h->theta, h->weight, h->prop, h->prop_prior, h->prop_adj, h->tr_w, h->partial, h->aux,
-                    h->dimtab, h->dimseg, h->hist, h->lp_hist, h->mig_rows, h->scratch_theta, h->scratch_w, h->id, h->prop_oob,
-                    h->tr_acc, h->masks, h->acc_hist, h->tr_idx, h->id_hist, h->data, h->Ainv, h->Ypad,
-                    h->Xf, h->sx, h->xbar};
-    for (void* p : ptrs)
-        if (p) hipFree(p);
-    if (h->user_module) hipModuleUnload(h->user_module);
-    if (h->user_hyper) hipFree(h->user_hyper);
-    if (h->user_dims) hipFree(h->user_dims);
-    if (h->sim_logtab) hipFree(h->sim_logtab);
-    free_replay(h);
-    for (int i = 0; i < demc_handle::kGlistRing; ++i) {
-        if (h->glist_buf[i]) hipFree(h->glist_buf[i]);
-        if (h->glist_pin[i]) hipHostFree(h->glist_pin[i]);
-        if (h->glist_ev[i]) hipEventDestroy(h->glist_ev[i]);
-    }
-    if (h->st.gran) hipFree(h->st.gran);
-    if (h->frozen_order_d) hipFree(h->frozen_order_d);
-    if (h->frozen_order_pin) hipHostFree(h->frozen_order_pin);
-    if (h->frozen_order_ev) hipEventDestroy(h->frozen_order_ev);
-    if (h->snap2) hipFree(h->snap2);
-    if (h->snap2_w) hipFree(h->snap2_w);
-    if (h->clk_dev) hipFree(h->clk_dev);
-    if (h->st.err) hipHostFree(h->st.err);
     if (h->side) hipStreamSynchronize(h->side);
     if (h->comm && h->own_comm) ncclCommDestroy(h->comm);
-    if (h->ev_pack) hipEventDestroy(h->ev_pack);
-    if (h->ev_gath) hipEventDestroy(h->ev_gath);
     if (h->side) hipStreamDestroy(h->side);
-    if (h->red_dev) hipFree(h->red_dev);
     if (h->own_stream && h->stream) hipStreamDestroy(h->stream);
-    delete h;
+    delete h;  // every buffer, event and module goes with its owner (demc_devmem.hpp)
     return DEMC_OK;
     });
 }
@@ -1587,34 +1591,31 @@ int32_t demc_set_model(demc_handle* h, int32_t family, const double* data, const
     long long dm[4] = {0, 0, 0, 0};
     for (int i = 0; i < ndims; ++i) dm[i] = dims[i];
     const int D = h->c.D;
-    for (double** p : {&h->data, &h->Ainv, &h->Ypad, &h->Xf, &h->sx, &h->xbar})
-        if (*p) { hipFree(*p); *p = nullptr; }
-    h->family = -1; h->N = 0; h->d = 0; h->n_acc = 0; h->dpad = 0; h->n_tiles = 0; h->c0 = h->c1 = h->c2 = 0; h->data2_off = 0;
-    h->dp_direct = 0; h->direct_wgs_per_cu = 0; h->sim_kind = -1;
-    std::vector<double> dev;  // what goes to h->data
+    if (int rc = clear_model(h)) return rc;
+    std::vector<double> dev;  // what goes to h->m.data
     switch (family) {
         case DEMC_FAM_GAUSSIAN:
             if (D != 2 || dm[0] < 1) return fail(h, DEMC_EINVAL, "GAUSSIAN: theta=(mu,sigma), dims=[N]");
-            h->N = dm[0];
+            h->m.N = dm[0];
             dev.assign(data, data + dm[0]);
             break;
         case DEMC_FAM_BINOMIAL: {
             if (D != 1 || dm[0] < 1) return fail(h, DEMC_EINVAL, "BINOMIAL: theta=p, dims=[N], data=[n[N],k[N]]");
             const long long N = dm[0];
-            h->N = N;
+            h->m.N = N;
             dev.assign(data, data + 2 * N);
             dev.resize(3 * N);
             for (long long i = 0; i < N; ++i) {
                 const double n = data[i], k = data[N + i];
                 dev[2 * N + i] = std::lgamma(n + 1.0) - std::lgamma(k + 1.0) - std::lgamma(n - k + 1.0);
             }
-            h->data2_off = (size_t)N;
+            h->m.data2_off = (size_t)N;
         } break;
         case DEMC_FAM_HIER_BINOMIAL: {
             if (D != dm[0] + 2 || nhyper < 1) return fail(h, DEMC_EINVAL, "HIER_BINOMIAL: D=S+2, dims=[S], hyper=[n]");
             const long long S = dm[0];
-            h->N = S;
-            h->c0 = hyper[0];
+            h->m.N = S;
+            h->m.c0 = hyper[0];
             dev.assign(data, data + S);
             dev.resize(2 * S);
             double lgc_sum = 0.0;
@@ -1623,12 +1624,12 @@ int32_t demc_set_model(demc_handle* h, int32_t family, const double* data, const
                 dev[S + s] = std::lgamma(n + 1.0) - std::lgamma(k + 1.0) - std::lgamma(n - k + 1.0);
                 lgc_sum += dev[S + s];
             }
-            h->c2 = lgc_sum;  // the long-row kernel adds the coefficients as one data-only constant
+            h->m.c2 = lgc_sum;  // the long-row kernel adds the coefficients as one data-only constant
         } break;
         case DEMC_FAM_HIER_GAUSSIAN:
             if (D != dm[0] + 3 || dm[1] < 1) return fail(h, DEMC_EINVAL, "HIER_GAUSSIAN: D=S+3, dims=[S,n]");
-            h->N = dm[0];
-            h->d = (int)dm[1];
+            h->m.N = dm[0];
+            h->m.d = (int)dm[1];
             dev.assign(data, data + dm[0] * dm[1]);
             break;
         case DEMC_FAM_LBA:
@@ -1644,11 +1645,11 @@ int32_t demc_set_model(demc_handle* h, int32_t family, const double* data, const
                     return fail(h, DEMC_EINVAL, "LBA/LNR: choice of trial " + std::to_string(i) + " is not an integer in [1, n_acc]");
                 if (!std::isfinite(rt)) return fail(h, DEMC_EINVAL, "LBA/LNR: decision time of trial " + std::to_string(i) + " is not finite");
             }
-            h->N = dm[0];
-            h->n_acc = (int)dm[1];
-            h->c0 = (family == DEMC_FAM_LNR) ? (nhyper > 0 ? hyper[0] : 1.0) : 0.0;
+            h->m.N = dm[0];
+            h->m.n_acc = (int)dm[1];
+            h->m.c0 = (family == DEMC_FAM_LNR) ? (nhyper > 0 ? hyper[0] : 1.0) : 0.0;
             dev.assign(data, data + 2 * dm[0]);
-            h->data2_off = (size_t)dm[0];
+            h->m.data2_off = (size_t)dm[0];
             if (family == DEMC_FAM_LBA) {
                 // The log-likelihood is a sum over trials: their order is the library's to choose.  Sorted by (choice, decision time)
                 // the 64 lanes of k_lba_wave -- 64 consecutive trials of one proposal -- read the same row or two of the Phi table and
@@ -1663,7 +1664,7 @@ int32_t demc_set_model(demc_handle* h, int32_t family, const double* data, const
             }
         } break;
         case DEMC_FAM_RASTRIGIN:
-            h->N = 1;
+            h->m.N = 1;
             break;
         case DEMC_FAM_ODE_LV: {
             if (D != 5) return fail(h, DEMC_EINVAL, "ODE_LV: D = 5 required, theta=(alpha,beta,gamma,delta,sigma)");
@@ -1679,10 +1680,10 @@ int32_t demc_set_model(demc_handle* h, int32_t family, const double* data, const
             for (long long i = 0; i < 2 * dm[0]; ++i)
                 if (!std::isfinite(data[i]))
                     return fail(h, DEMC_EINVAL, "ODE_LV: data value " + std::to_string(i) + " (time " + std::to_string(i / 2) + ") is not finite");
-            h->N = dm[0];
-            h->ode_substeps = (int)hyper[3];
-            h->ode_u0[0] = hyper[0]; h->ode_u0[1] = hyper[1]; h->ode_u0[2] = h->ode_u0[3] = 0.0;
-            h->ode_h = hyper[2] / hyper[3];
+            h->m.N = dm[0];
+            h->m.ode_substeps = (int)hyper[3];
+            h->m.ode_u0[0] = hyper[0]; h->m.ode_u0[1] = hyper[1]; h->m.ode_u0[2] = h->m.ode_u0[3] = 0.0;
+            h->m.ode_h = hyper[2] / hyper[3];
             dev.assign(data, data + 2 * dm[0]);
         } break;
         case DEMC_FAM_MVN_ISO:
@@ -1693,29 +1694,29 @@ int32_t demc_set_model(demc_handle* h, int32_t family, const double* data, const
             if (d > 1024) return fail(h, DEMC_EUNSUPPORTED, "MVN families: data dimension d <= 1024");
             if (family == DEMC_FAM_MVN_ISO && D != d + 1) return fail(h, DEMC_EINVAL, "MVN_ISO: D=d+1");
             if (family == DEMC_FAM_MVN_FULL && (D != d || nhyper != d * d)) return fail(h, DEMC_EINVAL, "MVN_FULL: D=d, hyper=Sigma[d][d]");
-            h->N = N;
-            h->d = d;
+            h->m.N = N;
+            h->m.d = d;
             // k-steps of 4 dims: one pass of KS in {1,2,4,8,16} steps for d <= 64, else passes of 16 steps
-            if (d <= 64) { h->ks_t = pow2_ceil((d + 3) / 4); h->n_kpass = 1; }
-            else { h->ks_t = 16; h->n_kpass = (d + 63) / 64; }
-            h->dpad = 4 * h->ks_t * h->n_kpass;
+            if (d <= 64) { h->m.ks_t = pow2_ceil((d + 3) / 4); h->m.n_kpass = 1; }
+            else { h->m.ks_t = 16; h->m.n_kpass = (d + 63) / 64; }
+            h->m.dpad = 4 * h->m.ks_t * h->m.n_kpass;
             if ((N + 15) / 16 > 0x3fffffff) return fail(h, DEMC_EINVAL, "too many observations");
-            h->n_tiles = (int)((N + 15) / 16);
+            h->m.n_tiles = (int)((N + 15) / 16);
             const bool direct = h->c.loglike_mode == DEMC_LOGLIKE_DIRECT;
             if (direct && d > 64) return fail(h, DEMC_EUNSUPPORTED, "DIRECT likelihood: data dimension d <= 64 (the whitened proposal lives in registers)");
             std::vector<double> Ainv, Linv;
             double logdet = 0.0;
             if (family == DEMC_FAM_MVN_FULL) {
                 if (!chol_inv(hyper, d, Ainv, logdet, &Linv)) return fail(h, DEMC_EINVAL, "Sigma is not positive definite");
-                h->c0 = -0.5 * (double)N * (d * kLog2Pi + logdet);
-                ALLOC(h->Ainv, (size_t)d * d);
+                h->m.c0 = -0.5 * (double)N * (d * kLog2Pi + logdet);
+                ALLOC(h->m.Ainv, (size_t)d * d);
                 // K1's preparation forms y_c = sum_k M[k][c] (theta' - xbar)_k.  M = Sigma^-1 (symmetric) gives y = Sigma^-1 mu~;
                 // in DIRECT mode M = (L^-1)' gives the whitened proposal m = L^-1 mu~ instead.
                 std::vector<double> M = Ainv;
                 if (direct)
                     for (int r = 0; r < d; ++r)
                         for (int cc = 0; cc < d; ++cc) M[(size_t)r * d + cc] = Linv[(size_t)cc * d + r];
-                HIPCHK(hipMemcpy(h->Ainv, M.data(), sizeof(double) * d * d, hipMemcpyHostToDevice));
+                HIPCHK(hipMemcpy(h->m.Ainv, M.data(), sizeof(double) * d * d, hipMemcpyHostToDevice));
             }
             // The data are CENTRED once (x~_i = x_i - xbar) and proposals are shifted the same way in K1
             // (mu~ = theta' - xbar): (x_i - mu) = (x~_i - mu~), but every term of the expanded quadratic form
@@ -1746,29 +1747,29 @@ int32_t demc_set_model(demc_handle* h, int32_t family, const double* data, const
                 c1 += q;
                 for (int k = 0; k < d; ++k) sx[k] += x[k];
             }
-            h->c1 = c1;
-            ALLOC(h->sx, (size_t)d);
-            HIPCHK(hipMemcpy(h->sx, sx.data(), sizeof(double) * d, hipMemcpyHostToDevice));
-            ALLOC(h->xbar, (size_t)d);
-            HIPCHK(hipMemcpy(h->xbar, xbar.data(), sizeof(double) * d, hipMemcpyHostToDevice));
-            ALLOC(h->Ypad, (size_t)h->P * h->dpad);
+            h->m.c1 = c1;
+            ALLOC(h->m.sx, (size_t)d);
+            HIPCHK(hipMemcpy(h->m.sx, sx.data(), sizeof(double) * d, hipMemcpyHostToDevice));
+            ALLOC(h->m.xbar, (size_t)d);
+            HIPCHK(hipMemcpy(h->m.xbar, xbar.data(), sizeof(double) * d, hipMemcpyHostToDevice));
+            ALLOC(h->m.Ypad, (size_t)h->P * h->m.dpad);
             // fragment-ordered copy of X for v_mfma_f64_16x16x4_f64's B operand:
             //   Xf[tile][kstep][lane] = X[16*tile + (lane&15)][4*kstep + (lane>>4)], zero padded
-            const int ksx = h->dpad / 4;
-            std::vector<double> xf(((size_t)h->n_tiles + 1) * ksx * 64, 0.0);  // +1: the all-zero tail tile
-            for (long long tI = 0; tI < h->n_tiles; ++tI)
+            const int ksx = h->m.dpad / 4;
+            std::vector<double> xf(((size_t)h->m.n_tiles + 1) * ksx * 64, 0.0);  // +1: the all-zero tail tile
+            for (long long tI = 0; tI < h->m.n_tiles; ++tI)
                 for (int ks = 0; ks < ksx; ++ks)
                     for (int l = 0; l < 64; ++l) {
                         const long long i = 16 * tI + (l & 15);
                         const int k = 4 * ks + (l >> 4);
                         if (i < N && k < d) xf[((size_t)tI * ksx + ks) * 64 + l] = data[i * d + k];
                     }
-            ALLOC(h->Xf, xf.size());
-            HIPCHK(hipMemcpy(h->Xf, xf.data(), sizeof(double) * xf.size(), hipMemcpyHostToDevice));
+            ALLOC(h->m.Xf, xf.size());
+            HIPCHK(hipMemcpy(h->m.Xf, xf.data(), sizeof(double) * xf.size(), hipMemcpyHostToDevice));
             if (direct) {
                 // whitened, centred observations z_i = L^-1 x~_i (ISO: x~_i), rows padded with zeros to DP scalars
-                h->dp_direct = d <= 8 ? 8 : d <= 16 ? 16 : d <= 32 ? 32 : 64;
-                const int DP = h->dp_direct;
+                h->m.dp_direct = d <= 8 ? 8 : d <= 16 ? 16 : d <= 32 ? 32 : 64;
+                const int DP = h->m.dp_direct;
                 dev.assign((size_t)N * DP, 0.0);
                 for (long long i = 0; i < N; ++i) {
                     const double* x = data + i * d;
@@ -1788,10 +1789,10 @@ int32_t demc_set_model(demc_handle* h, int32_t family, const double* data, const
             return fail(h, DEMC_EUNSUPPORTED, "model family is not registered; arbitrary closures cannot run on the device");
     }
     if (!dev.empty()) {
-        ALLOC(h->data, dev.size());
-        HIPCHK(hipMemcpy(h->data, dev.data(), sizeof(double) * dev.size(), hipMemcpyHostToDevice));
+        ALLOC(h->m.data, dev.size());
+        HIPCHK(hipMemcpy(h->m.data, dev.data(), sizeof(double) * dev.size(), hipMemcpyHostToDevice));
     }
-    h->family = family;
+    h->m.family = family;
     return size_k1_lds(h);
     });
 }
@@ -1805,52 +1806,30 @@ static int32_t set_model_source_impl(demc_handle* h, const char* hip_source, con
     long long n_data = 1;
     for (int i = 0; i < ndims; ++i) n_data *= dims[i];
     if (n_data < 1) return fail(h, DEMC_EINVAL, "user model: empty data");
-    HIPCHK(hipStreamSynchronize(h->stream));
-    for (double** p : {&h->data, &h->Ainv, &h->Ypad, &h->Xf, &h->sx, &h->xbar, &h->user_hyper})
-        if (*p) { hipFree(*p); *p = nullptr; }
-    if (h->user_dims) { hipFree(h->user_dims); h->user_dims = nullptr; }
-    if (h->user_module) { hipModuleUnload(h->user_module); h->user_module = nullptr; h->user_kernel = nullptr; }
-    h->family = -1; h->d = 0; h->n_acc = 0; h->dpad = 0; h->n_tiles = 0; h->c0 = h->c1 = h->c2 = 0; h->data2_off = 0;
-    h->user_row = row; h->user_has_prior = row && has_prior; h->user_ndims = ndims; h->sim_kind = -1;
+    if (int rc = clear_model(h)) return rc;
+    h->m.user_row = row; h->m.user_has_prior = row && has_prior; h->m.user_ndims = ndims;
     // compile: kernarg struct + declarations + user source + kernel, for gfx950
     const std::string src = std::string(row && has_prior ? "#define DEMC_USER_HAS_PRIOR 1\n" : "") + kUserStruct +
                             (row ? kUserRowPrologue : kUserPrologue) + hip_source + (row ? kUserRowKernel : kUserKernel);
-    hiprtcProgram prog;
-    if (hiprtcCreateProgram(&prog, src.c_str(), "demc_user_model.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS)
-        return fail(h, DEMC_EHIP, "hiprtcCreateProgram failed");
     const char* opts[] = {"--offload-arch=" DEMC_ARCH_STR, "-O3", "-std=c++17"};
-    const hiprtcResult cr = hiprtcCompileProgram(prog, 3, opts);
-    if (cr != HIPRTC_SUCCESS) {
-        size_t ls = 0;
-        hiprtcGetProgramLogSize(prog, &ls);
-        std::string log(ls, '\0');
-        if (ls) hiprtcGetProgramLog(prog, &log[0]);
-        hiprtcDestroyProgram(&prog);
-        return fail(h, DEMC_EINVAL, std::string("user model does not compile: ") + hiprtcGetErrorString(cr) + "\n" + log);
-    }
-    size_t cs = 0;
-    hiprtcGetCodeSize(prog, &cs);
-    std::vector<char> code(cs);
-    hiprtcGetCode(prog, code.data());
-    hiprtcDestroyProgram(&prog);
-    HIPCHK(hipModuleLoadData(&h->user_module, code.data()));
-    HIPCHK(hipModuleGetFunction(&h->user_kernel, h->user_module, row ? "k_user_row" : "k_user_loglike"));
-    h->N = dims[0];
-    ALLOC(h->data, (size_t)n_data);
-    HIPCHK(hipMemcpy(h->data, data, sizeof(double) * (size_t)n_data, hipMemcpyHostToDevice));
+    if (int rc = compile_module(h, src, "demc_user_model.hip", opts, "user model", row ? "k_user_row" : "k_user_loglike", h->m.user_module, &h->m.user_kernel))
+        return rc;
+    h->m.N = dims[0];
+    ALLOC(h->m.data, (size_t)n_data);
+    HIPCHK(hipMemcpy(h->m.data, data, sizeof(double) * (size_t)n_data, hipMemcpyHostToDevice));
     {
         long long dm[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         for (int i = 0; i < ndims; ++i) dm[i] = dims[i];
-        ALLOC(h->user_dims, (size_t)8);
-        HIPCHK(hipMemcpy(h->user_dims, dm, sizeof dm, hipMemcpyHostToDevice));
+        ALLOC(h->m.user_dims, (size_t)8);
+        HIPCHK(hipMemcpy(h->m.user_dims, dm, sizeof dm, hipMemcpyHostToDevice));
     }
-    h->user_nhyper = nhyper > 0 ? nhyper : 0;
-    if (h->user_nhyper) {
+    h->m.user_nhyper = nhyper > 0 ? nhyper : 0;
+    if (h->m.user_nhyper) {
         if (!hyper) return fail(h, DEMC_EINVAL, "user model: nhyper > 0 without hyper");
-        ALLOC(h->user_hyper, (size_t)h->user_nhyper);
-        HIPCHK(hipMemcpy(h->user_hyper, hyper, sizeof(double) * (size_t)h->user_nhyper, hipMemcpyHostToDevice));
+        ALLOC(h->m.user_hyper, (size_t)h->m.user_nhyper);
+        HIPCHK(hipMemcpy(h->m.user_hyper, hyper, sizeof(double) * (size_t)h->m.user_nhyper, hipMemcpyHostToDevice));
     }
-    h->family = FAM_USER;
+    h->m.family = FAM_USER;
     return size_k1_lds(h);
     });
 }
@@ -1923,60 +1902,37 @@ int32_t demc_set_model_sim(demc_handle* h, int32_t simulator, int32_t estimator,
         for (int64_t j = 0; j < n_obs; ++j)
             if (!(data[j] == std::floor(data[j])))
                 return fail(h, DEMC_EINVAL, "demc_set_model_sim: the FREQUENCY estimator needs integer-valued data (observation " + std::to_string(j) + " is not)");
-    HIPCHK(hipStreamSynchronize(h->stream));
-    for (double** p : {&h->data, &h->Ainv, &h->Ypad, &h->Xf, &h->sx, &h->xbar, &h->user_hyper, &h->sim_logtab})
-        if (*p) { hipFree(*p); *p = nullptr; }
-    if (h->user_dims) { hipFree(h->user_dims); h->user_dims = nullptr; }
-    if (h->user_module) { hipModuleUnload(h->user_module); h->user_module = nullptr; h->user_kernel = nullptr; }
-    h->family = -1; h->N = 0; h->d = 0; h->n_acc = 0; h->dpad = 0; h->n_tiles = 0; h->c0 = h->c1 = h->c2 = 0; h->data2_off = 0;
-    h->user_row = false; h->user_has_prior = false; h->user_ndims = 0; h->user_nhyper = 0; h->sim_kind = -1;
+    if (int rc = clear_model(h)) return rc;
     if (simulator == DEMC_SIM_USER) {
         // the one kernel text (demc_simlike.hpp) with n_sim and the estimator compiled in, the user's function behind it
         const std::string src = "#define DEMC_SIM_JIT 1\n#define DEMC_SIM_JIT_N " + std::to_string(n_sim) + "\n#define DEMC_SIM_JIT_EST " +
                                 std::to_string(estimator) + "\n" + kSimKernelSource + "\n" + hip_source + "\n";
-        hiprtcProgram prog;
-        if (hiprtcCreateProgram(&prog, src.c_str(), "demc_user_sim.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS)
-            return fail(h, DEMC_EHIP, "hiprtcCreateProgram failed");
         const char* opts[] = {"--offload-arch=" DEMC_ARCH_STR, "-O3", "-std=c++17", "-ffp-contract=off"};
-        const hiprtcResult cr = hiprtcCompileProgram(prog, 4, opts);
-        if (cr != HIPRTC_SUCCESS) {
-            size_t ls = 0;
-            hiprtcGetProgramLogSize(prog, &ls);
-            std::string log(ls, '\0');
-            if (ls) hiprtcGetProgramLog(prog, &log[0]);
-            hiprtcDestroyProgram(&prog);
-            return fail(h, DEMC_EINVAL, std::string("user simulator does not compile: ") + hiprtcGetErrorString(cr) + "\n" + log);
-        }
-        size_t cs = 0;
-        hiprtcGetCodeSize(prog, &cs);
-        std::vector<char> code(cs);
-        hiprtcGetCode(prog, code.data());
-        hiprtcDestroyProgram(&prog);
-        HIPCHK(hipModuleLoadData(&h->user_module, code.data()));
-        HIPCHK(hipModuleGetFunction(&h->user_kernel, h->user_module, "k_sim_loglike_user"));
+        if (int rc = compile_module(h, src, "demc_user_sim.hip", opts, "user simulator", "k_sim_loglike_user", h->m.user_module, &h->m.user_kernel))
+            return rc;
     }
-    h->N = n_obs;
+    h->m.N = n_obs;
     const size_t n_data = (size_t)n_obs * (pairs ? 2 : 1);
-    ALLOC(h->data, n_data);
-    HIPCHK(hipMemcpy(h->data, data, sizeof(double) * n_data, hipMemcpyHostToDevice));
-    h->sim_kmax = kmax;
+    ALLOC(h->m.data, n_data);
+    HIPCHK(hipMemcpy(h->m.data, data, sizeof(double) * n_data, hipMemcpyHostToDevice));
+    h->m.sim_kmax = kmax;
     // hyper as the kernels see it: [bandwidth, the simulator's own ...]
-    h->user_nhyper = nhyper > 0 ? nhyper : 1;
+    h->m.user_nhyper = nhyper > 0 ? nhyper : 1;
     {
-        std::vector<double> hy((size_t)h->user_nhyper, 0.0);
+        std::vector<double> hy((size_t)h->m.user_nhyper, 0.0);
         for (int i = 0; i < nhyper; ++i) hy[(size_t)i] = hyper[i];
-        ALLOC(h->user_hyper, hy.size());
-        HIPCHK(hipMemcpy(h->user_hyper, hy.data(), sizeof(double) * hy.size(), hipMemcpyHostToDevice));
-        h->sim_bw = hy[0] > 0.0 ? hy[0] : 0.0;
+        ALLOC(h->m.user_hyper, hy.size());
+        HIPCHK(hipMemcpy(h->m.user_hyper, hy.data(), sizeof(double) * hy.size(), hipMemcpyHostToDevice));
+        h->m.sim_bw = hy[0] > 0.0 ? hy[0] : 0.0;
     }
     if (estimator == DEMC_SIMEST_FREQUENCY) {
         std::vector<double> lt((size_t)n_sim + 1);
         for (int64_t c = 0; c <= n_sim; ++c) lt[(size_t)c] = std::log((double)c / (double)n_sim);  // (log 0 = -Inf: a count of zero)
-        ALLOC(h->sim_logtab, lt.size());
-        HIPCHK(hipMemcpy(h->sim_logtab, lt.data(), sizeof(double) * lt.size(), hipMemcpyHostToDevice));
+        ALLOC(h->m.sim_logtab, lt.size());
+        HIPCHK(hipMemcpy(h->m.sim_logtab, lt.data(), sizeof(double) * lt.size(), hipMemcpyHostToDevice));
     }
-    h->sim_kind = simulator; h->sim_est = estimator; h->sim_n = (int)n_sim;
-    h->family = FAM_SIM;
+    h->m.sim_kind = simulator; h->m.sim_est = estimator; h->m.sim_n = (int)n_sim;
+    h->m.family = FAM_SIM;
     return size_k1_lds(h);
     });
 }
@@ -2022,7 +1978,7 @@ static int upload_dimtab(demc_handle* h) {
     HIPCHK(hipMemcpy(h->dimseg, segs, sizeof segs, hipMemcpyHostToDevice));
     // the lean resident kernel reads the table in its run-length form and knows no Normal(a, theta[ref]) prior: priors and
     // bounds arrive AFTER demc_set_model in every caller, so its plan is taken again whenever the table changes
-    return h->family >= 0 ? plan_lean(h) : DEMC_OK;
+    return h->m.family >= 0 ? plan_lean(h) : DEMC_OK;
 }
 
 int32_t demc_set_priors(demc_handle* h, const int32_t* kind, const double* a, const double* b, const int32_t* ref) {
@@ -2092,7 +2048,7 @@ int32_t demc_set_blocks(demc_handle* h, const uint8_t* masks, int32_t n_blocks) 
     return guarded(h, [&]() -> int32_t {
     if (!h || n_blocks < 0 || (n_blocks > 0 && !masks)) return DEMC_EINVAL;
     USE_DEVICE(h);
-    if (h->masks) { hipFree(h->masks); h->masks = nullptr; }
+    h->masks.reset();
     h->c.n_blocks = n_blocks;
     if (n_blocks > 0) {
         ALLOC(h->masks, (size_t)n_blocks * h->c.D);
@@ -2126,7 +2082,7 @@ int32_t demc_set_state(demc_handle* h, const double* theta, const double* weight
     if (weight)
         HIPCHK(hipMemcpy(h->weight, weight, P * sizeof(double), hipMemcpyHostToDevice));
     else {
-        if (h->family < 0) return fail(h, DEMC_EINVAL, "demc_set_model before demc_set_state(weight = NULL)");
+        if (h->m.family < 0) return fail(h, DEMC_EINVAL, "demc_set_model before demc_set_state(weight = NULL)");
         int rc = evaluate_rows(h, h->theta, h->weight);
         if (rc != DEMC_OK) return rc;
         HIPCHK(hipStreamSynchronize(h->stream));
@@ -2163,18 +2119,16 @@ int32_t demc_set_history_rows(demc_handle* h, int64_t row0, int64_t nrows, const
     }
     // padded cells: the caller's dense rows go through a device staging buffer, a few rows at a time
     const size_t chunk = std::max<size_t>(1, ((size_t)64 << 20) / (P * D * sizeof(double)));
-    double* stage = nullptr;
+    DevBuf<double> stage;
     ALLOC(stage, std::min<size_t>(chunk, (size_t)nrows) * P * D);
-    int rc = DEMC_OK;
-    for (size_t r = 0; r < (size_t)nrows && rc == DEMC_OK; r += chunk) {
+    for (size_t r = 0; r < (size_t)nrows; r += chunk) {
         const size_t n = std::min(chunk, (size_t)nrows - r);
-        if (hipMemcpy(stage, rows + r * P * D, n * P * D * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) { rc = fail(h, DEMC_EHIP, "history upload"); break; }
-        hipLaunchKernelGGL(k_hist_repack, dim3(1024), dim3(256), 0, h->stream, h->hist + ((size_t)row0 + r) * P * ld, stage, (long long)(n * P), (int)D,
+        if (hipMemcpy(stage, rows + r * P * D, n * P * D * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(h, DEMC_EHIP, "history upload");
+        hipLaunchKernelGGL(k_hist_repack, dim3(1024), dim3(256), 0, h->stream, h->hist + ((size_t)row0 + r) * P * ld, stage.get(), (long long)(n * P), (int)D,
                            (int)ld, (int)D);
-        if (hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(h, DEMC_EHIP, "history repack");
+        if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(h, DEMC_EHIP, "history repack");
     }
-    hipFree(stage);
-    return rc;
+    return DEMC_OK;
     });
 }
 
@@ -2190,18 +2144,15 @@ int32_t demc_get_history(demc_handle* h, int64_t row0, int64_t row1, double* th,
     if (th && ld == D) HIPCHK(hipMemcpy(th, h->hist + (size_t)row0 * P * D, n * P * D * sizeof(double), hipMemcpyDeviceToHost));
     else if (th && n > 0) {  // padded cells: packed into a dense staging buffer on the device, a few rows at a time
         const size_t chunk = std::max<size_t>(1, ((size_t)64 << 20) / (P * D * sizeof(double)));
-        double* stage = nullptr;
+        DevBuf<double> stage;
         ALLOC(stage, std::min(chunk, n) * P * D);
-        int rc = DEMC_OK;
-        for (size_t r = 0; r < n && rc == DEMC_OK; r += chunk) {
+        for (size_t r = 0; r < n; r += chunk) {
             const size_t m = std::min(chunk, n - r);
-            hipLaunchKernelGGL(k_hist_repack, dim3(1024), dim3(256), 0, h->stream, stage, h->hist + ((size_t)row0 + r) * P * ld, (long long)(m * P), (int)D,
+            hipLaunchKernelGGL(k_hist_repack, dim3(1024), dim3(256), 0, h->stream, stage.get(), h->hist + ((size_t)row0 + r) * P * ld, (long long)(m * P), (int)D,
                                (int)D, (int)ld);
-            if (hipStreamSynchronize(h->stream) != hipSuccess) { rc = fail(h, DEMC_EHIP, "history repack"); break; }
-            if (hipMemcpy(th + r * P * D, stage, m * P * D * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(h, DEMC_EHIP, "history download");
+            if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(h, DEMC_EHIP, "history repack");
+            if (hipMemcpy(th + r * P * D, stage, m * P * D * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(h, DEMC_EHIP, "history download");
         }
-        hipFree(stage);
-        if (rc != DEMC_OK) return rc;
     }
     if (acc) HIPCHK(hipMemcpy(acc, h->acc_hist + (size_t)row0 * P, n * P, hipMemcpyDeviceToHost));
     if (lp) HIPCHK(hipMemcpy(lp, h->lp_hist + (size_t)row0 * P, n * P * sizeof(double), hipMemcpyDeviceToHost));
@@ -2225,16 +2176,15 @@ int32_t demc_export_chains(demc_handle* h, int64_t row0, int64_t row1, int32_t l
     const long long n = row1 - row0;
     if (n == 0) return DEMC_OK;
     const size_t elems = (size_t)n * (size_t)h->P * (size_t)(h->c.D + 2);
-    double* dev = nullptr;
+    DevBuf<double> dev;
     ALLOC(dev, elems);
     KParams k = base_params(h);
     const long long blocks = (long long)((elems + 255) / 256);
     hipLaunchKernelGGL(k_export_chains, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, h->stream, k, (long long)row0, n,
-                       (int)layout, (long long)h->c.group_offset * h->c.Np, dev);
+                       (int)layout, (long long)h->c.group_offset * h->c.Np, dev.get());
     hipError_t e = hipStreamSynchronize(h->stream);
     if (e == hipSuccess) e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpy(out, dev, elems * sizeof(double), hipMemcpyDeviceToHost);
-    hipFree(dev);
     if (e != hipSuccess) return fail(h, DEMC_EHIP, std::string("demc_export_chains: ") + hipGetErrorString(e));
     return DEMC_OK;
     });
@@ -2276,9 +2226,9 @@ int32_t demc_quantiles(demc_handle* h, int64_t row0, int64_t row1, const double*
 
 // the alpha coin of iteration `iter` as this handle sees it: the replayed uniform while one is set (main.jl:85)
 static bool migration_due_h(demc_handle* h, int64_t iter) {
-    if (h->rp_active && h->rp_has_step) {
+    if (h->rp.active && h->rp.has_step) {
         const int ngt = h->c.n_groups_total > 0 ? h->c.n_groups_total : h->c.n_groups;
-        return h->rp_u_step <= (ngt == 1 ? 0.0 : h->c.alpha);
+        return h->rp.u_step <= (ngt == 1 ? 0.0 : h->c.alpha);
     }
     return demc_migration_due(&h->c, iter) != 0;
 }
@@ -2318,7 +2268,7 @@ static int step_body(demc_handle* h, int64_t iter0, int32_t n_iters, bool with_m
 // THE HANDLE'S STREAM, i.e. behind every kernel that still reads its previous content.
 static int update_subset(demc_handle* h, int64_t iter0, int32_t n_iters, const int32_t* groups, int32_t n) {
     if (n == 0) return DEMC_OK;
-    if (h->rp_active && h->rp_n_mig > 0)
+    if (h->rp.active && h->rp.n_mig > 0)
         return fail(h, DEMC_EINVAL, "subset updates follow demc_migration_groups, which does not see a replayed migration sub-group");
     const int G = h->c.n_groups;
     for (int i = 0; i < n; ++i)
@@ -2374,7 +2324,7 @@ static void plan_frozen_order(demc_handle* h, int64_t iter0, int32_t n_iters) {
     h->frozen_iters = 0;
     // nothing to plan where launch_phase cannot take the frozen form at all (frozen_possible; a pool beyond the kernel's), for a
     // subset of the groups (its own list), without mutation, or under a replay
-    if (!frozen_possible(h) || c.Np > 512 || h->cur_glist || c.beta <= 0.0 || h->rp_active || n_iters < 1) return;
+    if (!frozen_possible(h) || c.Np > 512 || h->cur_glist || c.beta <= 0.0 || h->rp.active || n_iters < 1) return;
     bool any = false;
     std::vector<char> frozen((size_t)c.n_blocks, 0);
     for (int b = 0; b < c.n_blocks && (size_t)b < h->mask_runs.size(); ++b) {
@@ -2385,20 +2335,19 @@ static void plan_frozen_order(demc_handle* h, int64_t iter0, int32_t n_iters) {
     const size_t need = (size_t)n_iters * c.n_blocks * c.n_groups;
     if (!any || need > ((size_t)1 << 24)) return;
     if (need > h->frozen_order_cap) {
-        if (h->frozen_order_d) { if (hipStreamSynchronize(h->stream) != hipSuccess) return; hipFree(h->frozen_order_d); }
-        h->frozen_order_d = nullptr; h->frozen_order_cap = 0;
-        if (hipMalloc((void**)&h->frozen_order_d, need * sizeof(int)) != hipSuccess) { (void)hipGetLastError(); return; }
+        if (h->frozen_order_d && hipStreamSynchronize(h->stream) != hipSuccess) return;
+        h->frozen_order_cap = 0;
+        if (h->frozen_order_d.alloc(need) != hipSuccess) { (void)hipGetLastError(); return; }
         h->frozen_order_cap = need;
     }
     // PINNED staging owned by the handle, guarded by an event: the copy below is asynchronous for the host too (a pageable source
     // made it wait for everything already queued on the stream -- step_body's "nothing is drained" was not true for blocked
     // hierarchical models), and the buffer outlives the call
-    if (!h->frozen_order_ev && hipEventCreateWithFlags(&h->frozen_order_ev, hipEventDisableTiming) != hipSuccess) { h->frozen_order_ev = nullptr; return; }
+    if (!h->frozen_order_ev && h->frozen_order_ev.create(hipEventDisableTiming) != hipSuccess) return;
     if (h->frozen_order_pin && hipEventSynchronize(h->frozen_order_ev) != hipSuccess) return;  // (the previous table has left the buffer)
     if (need > h->frozen_order_pin_cap) {
-        if (h->frozen_order_pin) hipHostFree(h->frozen_order_pin);
-        h->frozen_order_pin = nullptr; h->frozen_order_pin_cap = 0;
-        if (hipHostMalloc((void**)&h->frozen_order_pin, need * sizeof(int), hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return; }
+        h->frozen_order_pin_cap = 0;
+        if (h->frozen_order_pin.alloc(need, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return; }
         h->frozen_order_pin_cap = need;
     }
     int* order = h->frozen_order_pin;
@@ -2441,7 +2390,7 @@ static int step_body(demc_handle* h, int64_t iter0, int32_t n_iters, bool with_m
                                                 "demc_migration_pack/apply + demc_update");
                 // (history partners: the cells of row t - 1 come from EVERY group, so no subset of the groups may run ahead of the
                 // others by an iteration -- the overlapped form, which lets the unselected groups do exactly that, is not taken)
-                if (h->comm_overlap && !h->rp_active && c.partner_kind != DEMC_PARTNER_HISTORY) {
+                if (h->comm_overlap && !h->rp.active && c.partner_kind != DEMC_PARTNER_HISTORY) {
                     int run = 1;
                     while (iter + run < iter0 + n_iters && !migration_due_h(h, iter + run)) ++run;
                     int rc = exchange_overlapped(h, iter, run);
@@ -2475,7 +2424,7 @@ static int step_body(demc_handle* h, int64_t iter0, int32_t n_iters, bool with_m
 }
 
 static int step_checks(demc_handle* h, int64_t iter0, int32_t n_iters) {
-    if (h->family < 0) return fail(h, DEMC_EINVAL, "demc_set_model has not been called");
+    if (h->m.family < 0) return fail(h, DEMC_EINVAL, "demc_set_model has not been called");
     if (iter0 < 1 || n_iters < 0) return fail(h, DEMC_EINVAL, "iter0 is 1-based (de.iter, main.jl:34)");
     if (h->c.partner_kind == DEMC_PARTNER_HISTORY && iter0 < 2)
         return fail(h, DEMC_EINVAL, "history partners need at least one stored row (n_initial > 0)");
@@ -2489,8 +2438,8 @@ static int step_checks(demc_handle* h, int64_t iter0, int32_t n_iters) {
 static int drain(demc_handle* h) {
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipGetLastError());
-    if (h->st.err && *h->st.err) {
-        *h->st.err = 0u;
+    if (h->st.err && *h->st.err.get()) {
+        *h->st.err.get() = 0u;
         return fail(h, DEMC_EHIP, "streaming-resident kernel: a hand-over between the workgroups of a group timed out");
     }
     if (h->comm) {  // a collective that failed after it was enqueued shows up here
@@ -2630,8 +2579,8 @@ int32_t demc_comm_unique_id(void* id_out, int32_t nbytes) {
 
 static int comm_side_objects(demc_handle* h) {
     if (!h->side) HIPCHK(hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking));
-    if (!h->ev_pack) HIPCHK(hipEventCreateWithFlags(&h->ev_pack, hipEventDisableTiming));
-    if (!h->ev_gath) HIPCHK(hipEventCreateWithFlags(&h->ev_gath, hipEventDisableTiming));
+    if (!h->ev_pack) HIPCHK(h->ev_pack.create(hipEventDisableTiming));
+    if (!h->ev_gath) HIPCHK(h->ev_gath.create(hipEventDisableTiming));
     return DEMC_OK;
 }
 
@@ -2702,7 +2651,7 @@ int32_t demc_comm_allreduce(demc_handle* h, double* host_inout, int32_t n, int32
     if (!h->comm || h->comm_world == 1) return DEMC_OK;  // one rank: the values are the result
     const size_t m = n > 0 ? (size_t)n : 1;              // n == 0: a barrier (one dummy element goes round)
     if (h->red_cap < m) {
-        if (h->red_dev) { hipFree(h->red_dev); h->red_dev = nullptr; h->red_cap = 0; }
+        h->red_cap = 0;
         ALLOC(h->red_dev, m);
         h->red_cap = m;
     }
@@ -2729,7 +2678,7 @@ int32_t demc_comm_stats(demc_handle* h, int64_t* out3) {
 struct demc_multi {
     std::vector<demc_handle*> shard;
     bool rccl = false;              // distinct devices: one communicator per shard from ncclCommInitAll
-    std::vector<hipEvent_t> packed, copied;  // shared-device transport: rows packed / peers' rows copied
+    std::vector<Event> packed, copied;  // shared-device transport: rows packed / peers' rows copied
     bool copied_valid = false;
     std::string err;
 };
@@ -2763,8 +2712,8 @@ int32_t demc_destroy_multi(demc_multi* m) {
     }
     for (size_t r = m->shard.size(); r-- > 0;) {  // (last first: shards that share a device borrow an earlier shard's stream)
         if (m->shard[r]) hipSetDevice(m->shard[r]->c.device_id);
-        if (r < m->packed.size() && m->packed[r]) hipEventDestroy(m->packed[r]);
-        if (r < m->copied.size() && m->copied[r]) hipEventDestroy(m->copied[r]);
+        if (r < m->packed.size()) m->packed[r].reset();
+        if (r < m->copied.size()) m->copied[r].reset();
         if (m->shard[r]) demc_destroy(m->shard[r]);
     }
     delete m;
@@ -2820,8 +2769,8 @@ int32_t demc_create_multi(const demc_config* cfg, int32_t n_shards, const int32_
     } else if (n_shards > 1) {
         // shards that share a device (several shards per GPU): the rows change hands by device-to-device copies ordered by
         // events -- RCCL refuses two ranks on one device
-        m->packed.assign((size_t)n_shards, nullptr);
-        m->copied.assign((size_t)n_shards, nullptr);
+        m->packed.resize((size_t)n_shards);
+        m->copied.resize((size_t)n_shards);
         // Shards on ONE device run on one stream (the first such shard's): the streaming-resident kernels size their grid
         // for the whole chip and their workgroups spin on each other, so two of them in flight at once on a device would not
         // be co-resident (a 2 x 40-group set: 2 x 160 workgroups on 256 CUs).  In stream order the set is what one handle
@@ -2835,8 +2784,8 @@ int32_t demc_create_multi(const demc_config* cfg, int32_t n_shards, const int32_
                 }
         for (int r = 0; r < n_shards; ++r) {
             if (hipSetDevice(devs[(size_t)r]) != hipSuccess ||
-                hipEventCreateWithFlags(&m->packed[(size_t)r], hipEventDisableTiming) != hipSuccess ||
-                hipEventCreateWithFlags(&m->copied[(size_t)r], hipEventDisableTiming) != hipSuccess)
+                m->packed[(size_t)r].create(hipEventDisableTiming) != hipSuccess ||
+                m->copied[(size_t)r].create(hipEventDisableTiming) != hipSuccess)
                 return mfail(m, DEMC_EHIP, "creating the exchange events");
         }
     }
@@ -2948,28 +2897,21 @@ int32_t demc_apply_migration(demc_handle* h, const int32_t* src_slot, const int3
         seen[(size_t)dst_slot[k]] = 1;
     }
     const size_t W = (size_t)h->c.D + 2;
-    int* d_slots = nullptr;
-    double* d_stage = nullptr;
-    HIPCHK(hipMalloc(&d_slots, 2 * (size_t)n * sizeof(int)));
-    if (hipMalloc(&d_stage, (size_t)n * W * sizeof(double)) != hipSuccess) {
-        hipFree(d_slots);
-        return fail(h, DEMC_ENOMEM, "out of device memory for the migration staging rows");
-    }
-    int rc = DEMC_OK;
+    DevBuf<int> d_slots;
+    DevBuf<double> d_stage;
+    HIPCHK(d_slots.alloc(2 * (size_t)n));
+    if (d_stage.alloc((size_t)n * W) != hipSuccess) return fail(h, DEMC_ENOMEM, "out of device memory for the migration staging rows");
     hipError_t e = hipMemcpyAsync(d_slots, src_slot, (size_t)n * sizeof(int), hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_slots + n, dst_slot, (size_t)n * sizeof(int), hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) {
         KParams k = base_params(h);
         const unsigned wgs = (unsigned)(((size_t)n * W + 255) / 256);
-        hipLaunchKernelGGL(k_slot_moves, dim3(wgs), dim3(256), 0, h->stream, k, d_slots, d_stage, n, 0);
-        hipLaunchKernelGGL(k_slot_moves, dim3(wgs), dim3(256), 0, h->stream, k, d_slots + n, d_stage, n, 1);
+        hipLaunchKernelGGL(k_slot_moves, dim3(wgs), dim3(256), 0, h->stream, k, d_slots.get(), d_stage.get(), n, 0);
+        hipLaunchKernelGGL(k_slot_moves, dim3(wgs), dim3(256), 0, h->stream, k, d_slots + n, d_stage.get(), n, 1);
         e = hipStreamSynchronize(h->stream);
         if (e == hipSuccess) e = hipGetLastError();
     }
-    if (e != hipSuccess) rc = fail(h, DEMC_EHIP, hipGetErrorString(e));
-    hipFree(d_slots);
-    hipFree(d_stage);
-    return rc;
+    return e == hipSuccess ? DEMC_OK : fail(h, DEMC_EHIP, hipGetErrorString(e));
     });
 }
 
@@ -2982,7 +2924,7 @@ int32_t demc_logpost(demc_handle* h, const double* theta, int64_t n, double* out
     return guarded(h, [&]() -> int32_t {
     if (!h || !theta || !out || n < 0) return DEMC_EINVAL;
     USE_DEVICE(h);
-    if (h->family < 0) return fail(h, DEMC_EINVAL, "demc_set_model has not been called");
+    if (h->m.family < 0) return fail(h, DEMC_EINVAL, "demc_set_model has not been called");
     const size_t P = (size_t)h->P, D = (size_t)h->c.D;
     std::vector<double> w(P);
     for (int64_t off = 0; off < n; off += (int64_t)P) {
@@ -3008,7 +2950,7 @@ int32_t demc_set_replay(demc_handle* h, const demc_replay* r) {
     if (!h) return DEMC_EINVAL;
     USE_DEVICE(h);
     HIPCHK(hipStreamSynchronize(h->stream));
-    free_replay(h);
+    h->rp = Replay{};
     if (!r) return DEMC_OK;
     const demc_config& c = h->c;
     const size_t P = (size_t)h->P, D = (size_t)c.D, G = (size_t)c.n_groups;
@@ -3028,32 +2970,30 @@ int32_t demc_set_replay(demc_handle* h, const demc_replay* r) {
             seen[(size_t)g] = 1;
         }
     }
-    auto up = [&](auto** dst, const auto* src, size_t n) -> int {
+    auto up = [&](auto& dst, const auto* src, size_t n) -> int {
         if (!src || n == 0) return DEMC_OK;
         int rc = dev_alloc(h, dst, n);
         if (rc != DEMC_OK) return rc;
-        HIPCHK(hipMemcpy(*dst, src, n * sizeof(**dst), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(dst, src, n * sizeof(*src), hipMemcpyHostToDevice));
         return DEMC_OK;
     };
-    int rc = DEMC_OK;
-    if (rc == DEMC_OK) rc = up(&h->rp_group, r->u_group, G);
-    if (rc == DEMC_OK) rc = up(&h->rp_part, r->u_part, 5 * P);
-    if (rc == DEMC_OK) rc = up(&h->rp_partner, reinterpret_cast<const long long*>(r->partner), 3 * P);
-    if (rc == DEMC_OK) rc = up(&h->rp_noise, r->u_noise, P * D);
-    if (rc == DEMC_OK) rc = up(&h->rp_znoise, r->z_noise, P * D);
-    if (rc == DEMC_OK) rc = up(&h->rp_recomb, r->u_recomb, P * D);
-    if (rc == DEMC_OK) rc = up(&h->rp_mig_particle, reinterpret_cast<const long long*>(r->mig_particle), G);
-    if (rc == DEMC_OK) rc = up(&h->rp_mig_groups, r->mig_groups, (size_t)r->n_mig_groups);
-    if (rc != DEMC_OK) {
-        free_replay(h);
-        return rc;
-    }
-    h->rp_n_mig = r->n_mig_groups;
+    Replay rp;  // filled aside: a failure on the way leaves the handle without a replay
+    int rc = up(rp.group, r->u_group, G);
+    if (rc == DEMC_OK) rc = up(rp.part, r->u_part, 5 * P);
+    if (rc == DEMC_OK) rc = up(rp.partner, reinterpret_cast<const long long*>(r->partner), 3 * P);
+    if (rc == DEMC_OK) rc = up(rp.noise, r->u_noise, P * D);
+    if (rc == DEMC_OK) rc = up(rp.znoise, r->z_noise, P * D);
+    if (rc == DEMC_OK) rc = up(rp.recomb, r->u_recomb, P * D);
+    if (rc == DEMC_OK) rc = up(rp.mig_particle, reinterpret_cast<const long long*>(r->mig_particle), G);
+    if (rc == DEMC_OK) rc = up(rp.mig_groups, r->mig_groups, (size_t)r->n_mig_groups);
+    if (rc != DEMC_OK) return rc;
+    rp.n_mig = r->n_mig_groups;
     if (r->u_step && r->u_step[0] == r->u_step[0]) {
-        h->rp_has_step = true;
-        h->rp_u_step = r->u_step[0];
+        rp.has_step = true;
+        rp.u_step = r->u_step[0];
     }
-    h->rp_active = true;
+    rp.active = true;
+    h->rp = std::move(rp);
     return DEMC_OK;
     });
 }

@@ -10,36 +10,19 @@
 #include <vector>
 
 #include "../../include/demc.h"
+#include "demc_devmem.hpp"  // Scratch, Event
 
 namespace demc {
 
 namespace {
 
-struct Scratch {  // device allocations of one call, freed however it ends
-    std::vector<void*> ptrs;
-    ~Scratch() {
-        for (void* q : ptrs) (void)hipFree(q);
-    }
-    template <typename T>
-    bool get(T** out, size_t n) {
-        void* q = nullptr;
-        if (hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) return false;
-        ptrs.push_back(q);
-        *out = (T*)q;
-        return true;
-    }
-};
-
 struct Events {  // DEMC_QUANTILE_TRACE=1: device time of every histogram pass, printed to stderr (tools/quantile_bench.py)
-    std::vector<hipEvent_t> ev;
-    ~Events() {
-        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-    }
+    std::vector<Event> ev;
     bool mark(hipStream_t st) {
-        hipEvent_t e;
-        if (hipEventCreate(&e) != hipSuccess) return false;
-        ev.push_back(e);
-        return hipEventRecord(e, st) == hipSuccess;
+        Event e;
+        if (e.create(hipEventDefault) != hipSuccess) return false;
+        ev.push_back(std::move(e));
+        return hipEventRecord(ev.back(), st) == hipSuccess;
     }
 };
 

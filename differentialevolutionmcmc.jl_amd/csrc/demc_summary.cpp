@@ -9,25 +9,11 @@
 #include <vector>
 
 #include "../../include/demc.h"
+#include "demc_devmem.hpp"  // Scratch
 
 namespace demc {
 
 namespace {
-
-struct Scratch {  // device allocations of one call, freed however it ends
-    std::vector<void*> ptrs;
-    ~Scratch() {
-        for (void* q : ptrs) (void)hipFree(q);
-    }
-    template <typename T>
-    bool get(T** out, size_t n) {
-        void* q = nullptr;
-        if (hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) return false;
-        ptrs.push_back(q);
-        *out = (T*)q;
-        return true;
-    }
-};
 
 template <bool LDS>
 int launch_all(SumKParams& p, int workers, int n_jt, size_t lds, int n_blocks, hipStream_t st, std::string& err) {
