@@ -14,15 +14,13 @@
 
 #include <cmath>
 
+#include "demc_dimtab.hpp"  // kLog2Pi / kLogPi / kPi, the PR_* kinds, prior_const: shared with the host-only preparation
 #include "demc_logphi_table.hpp"
 #include "demc_phi_table.hpp"
 #include "demc_softplus_table.hpp"
 
 namespace demc {
 
-constexpr double kLog2Pi = 1.8378770664093454835606594728112;
-constexpr double kLogPi = 1.1447298858494001741434273513531;
-constexpr double kPi = 3.14159265358979323846264338327950288;
 constexpr double kInvSqrt2 = 0.70710678118654752440;
 constexpr double kInvSqrt2Pi = 0.39894228040143267794;
 
@@ -201,35 +199,6 @@ __device__ __forceinline__ double softplus_tab(double x, const SoftplusTab& c) {
     double q = fma(c.q7, f, c.q6);
     q = fma(q, f, c.q5); q = fma(q, f, c.q4); q = fma(q, f, c.q3); q = fma(q, f, -0.5); q = fma(q, f, 1.0);
     return fmax(x, 0.0) + fma(f, q, row.x);
-}
-
-enum Prior : int {
-    PR_FLAT = 0, PR_NORMAL = 1, PR_HALFCAUCHY = 2, PR_UNIFORM = 3, PR_BETA = 4, PR_NORMAL_REF = 5, PR_GAMMA = 6,
-    PR_EXPONENTIAL = 7, PR_LOGNORMAL = 8, PR_CAUCHY = 9
-};
-
-// x-independent part of a scalar's log-prior, computed on the host (keeps lgamma / atan out of the kernels)
-inline double prior_const(int kind, double a, double b) {
-    switch (kind) {
-        case PR_NORMAL:
-            return -0.5 * kLog2Pi - std::log(b);
-        case PR_HALFCAUCHY:
-            return -kLogPi - std::log(b) - std::log(1.0 - (std::atan((0.0 - a) / b) / kPi + 0.5));
-        case PR_UNIFORM:
-            return -std::log(b - a);
-        case PR_BETA:
-            return -(std::lgamma(a) + std::lgamma(b) - std::lgamma(a + b));
-        case PR_GAMMA:
-            return -a * std::log(b) - std::lgamma(a);
-        case PR_EXPONENTIAL:
-            return -std::log(b);
-        case PR_LOGNORMAL:
-            return -std::log(b) - 0.5 * kLog2Pi;
-        case PR_CAUCHY:
-            return -kLogPi - std::log(b);
-        default:
-            return 0.0;
-    }
 }
 
 // Phi(z) and phi(z)/S from the generated piecewise polynomial of Phi (tools/gen_phi_table.py: absolute error 1.1e-16 for Phi

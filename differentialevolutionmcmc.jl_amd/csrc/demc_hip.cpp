@@ -44,6 +44,7 @@
 #include "demc_summary.hpp"  // demc_summarize: its kernels and their launches live in demc_summary.cpp
 #include "demc_quantile.hpp"  // demc_quantiles: likewise, demc_quantile.cpp
 #include "demc_devmem.hpp"  // owners of the device memory, pinned memory, events and modules the handle holds
+#include "demc_prep.hpp"  // host-only: a model's data and constants, the prior table and its run-length forms, every refusal of those
 #include "demc_instances.hpp"  // one table per templated kernel, built from the lists above: every choice of an instance goes through them
 
 using namespace demc;
@@ -52,6 +53,8 @@ using namespace demc;
 #define DEMC_ARCH_STR "gfx950"  // the Makefile passes its ARCH, so that the JIT-compiled plug-in matches the library
 #endif
 constexpr size_t kMaxDynLds = 150 * 1024;  // of the 160 KB per CU; the rest covers the kernels' static __shared__
+static_assert(kPrepOdeMaxT == kOdeMaxT && kPrepOdeMaxSubsteps == kOdeMaxSubsteps && kPrepSimMaxN == kSimMaxN && kPrepSimChoiceMaxN == kSimChoiceMaxN,
+              "demc_prep.hpp refuses by the kernels' caps");
 
 namespace {
 
@@ -97,18 +100,12 @@ struct StreamGeo {
     PinnedBuf<unsigned> err;          // time-out flag (host-mapped, zero-copy)
 };
 
-// Everything a set-model call defines.  The default state is "no model"; clear_model is the one place a model is released.
-struct Model {
+// Everything a set-model call defines: the sizes and constants prepare_model works out (ModelShape, demc_prep.hpp) and what lives
+// on the device.  The default state is "no model"; clear_model is the one place a model is released.
+struct Model : ModelShape {
     int family = -1;
-    long long N = 0;
-    int d = 0, n_acc = 0, dpad = 0;
-    int n_tiles = 0;
-    int ks_t = 0, n_kpass = 0;  // MFMA k-steps per pass (template) and passes over the dimensions
-    int dp_direct = 0;          // DIRECT mode: padded length of a whitened observation row (8 / 16 / 32 / 64)
-    int direct_wgs_per_cu = 0;  // ... resident workgroups of its kernel per CU (wgs_per_cu: asked once per model)
+    int direct_wgs_per_cu = 0;  // DIRECT mode: resident workgroups of its kernel per CU (wgs_per_cu: asked once per model)
     DevBuf<double> data, Ainv, Ypad, Xf, sx, xbar;
-    size_t data2_off = 0;
-    double c0 = 0, c1 = 0, c2 = 0;
     // user plug-in (demc_set_model_source): JIT-compiled module, kernel and its hyper-parameters
     Module user_module;
     hipFunction_t user_kernel = nullptr;
@@ -123,9 +120,6 @@ struct Model {
     int sim_kmax = 0;              // KDE_CHOICE: the largest observed choice
     double sim_bw = 0.0;
     DevBuf<double> sim_logtab;     // [n_sim + 1] log(c / n_sim): the frequency estimator's terms
-    // ODE-trajectory likelihood (DEMC_FAM_ODE_LV, demc_ode.hpp): N = the observation times T, data = Y[T][DIM]
-    int ode_substeps = 0;
-    double ode_u0[4] = {0, 0, 0, 0}, ode_h = 0.0;
 };
 
 // demc_set_replay: device copies of the caller's draws.  Cleared by assigning Replay{}.
@@ -153,7 +147,6 @@ struct demc_handle {
     int n_seg = 0;              // 0: more segments than kMaxDimSeg, the kernels read dimtab
     int seg_start[kMaxDimSeg] = {0};
     unsigned seg_plain = 0;     // segments with a flat / Normal / Normal(a, theta[ref]) prior
-    struct MaskRuns { int n = 0; unsigned in = 0; int start[kMaxMaskRun] = {0}; };
     std::vector<MaskRuns> mask_runs;  // per block sweep: the mask run-length encoded (n = 0: too many runs)
     DevBuf<double> hist, lp_hist, mig_rows, scratch_theta, scratch_w;
     DevBuf<long long> id;
@@ -252,6 +245,7 @@ int fail(demc_handle* h, int code, const std::string& msg) noexcept {
     }
     return code;
 }
+int fail(demc_handle* h, const Refusal& r) noexcept { return fail(h, r.code, r.message); }
 
 // No C++ exception crosses the C-ABI (include/demc.h): every extern "C" body runs inside this guard.
 template <typename F>
@@ -295,6 +289,14 @@ int dev_alloc(demc_handle* h, DevBuf<T>& p, size_t n) {
         int rc_ = dev_alloc(h, (ptr), (n));    \
         if (rc_ != DEMC_OK) return rc_;        \
     } while (0)
+
+// a prepared vector to a device buffer of its size; an empty one leaves the buffer unallocated
+int upload(demc_handle* h, DevBuf<double>& dst, const std::vector<double>& src) {
+    if (src.empty()) return DEMC_OK;
+    ALLOC(dst, src.size());
+    HIPCHK(hipMemcpy(dst, src.data(), sizeof(double) * src.size(), hipMemcpyHostToDevice));
+    return DEMC_OK;
+}
 
 // Device time per kernel class (demc_timing_enable): the events of a bracket travel IN the dispatch packets of its kernels
 // (hipExtLaunchKernelGGL: start event on the first, stop event on every one -- the last record stands), so they read the
@@ -371,12 +373,6 @@ int wgs_per_cu(demc_handle* h, const void* fn, int* cached) {
 }
 
 bool is_mvn(int fam);
-
-int pow2_ceil(int x) {
-    int p = 1;
-    while (p < x) p <<= 1;
-    return p;
-}
 
 KParams base_params(demc_handle* h) {
     KParams k;
@@ -759,7 +755,7 @@ void launch_k1(demc_handle* h, const K1Inst* e, unsigned grid, int wg, size_t ld
     tick(h, 0, false);
 }
 
-// {scalars inside the block, its longest run} of a block mask in run-length form (demc_handle::MaskRuns / KParams::mrun_*)
+// {scalars inside the block, its longest run} of a block mask in run-length form (MaskRuns / KParams::mrun_*)
 struct BlockSpan { int inside = 0, longest = 0; };
 BlockSpan block_span(int n_run, unsigned in, const int* start, int D) {
     BlockSpan s;
@@ -1395,37 +1391,6 @@ int compile_module(demc_handle* h, const std::string& src, const char* file, con
     return DEMC_OK;
 }
 
-bool chol_inv(const double* S, int d, std::vector<double>& Ainv, double& logdet, std::vector<double>* Linv = nullptr) {
-    std::vector<double> L((size_t)d * d, 0.0), Li((size_t)d * d, 0.0);
-    for (int i = 0; i < d; ++i)
-        for (int j = 0; j <= i; ++j) {
-            double s = S[i * d + j];
-            for (int k = 0; k < j; ++k) s -= L[i * d + k] * L[j * d + k];
-            if (i == j) {
-                if (!(s > 0.0)) return false;
-                L[i * d + i] = std::sqrt(s);
-            } else
-                L[i * d + j] = s / L[j * d + j];
-        }
-    logdet = 0.0;
-    for (int i = 0; i < d; ++i) logdet += 2.0 * std::log(L[i * d + i]);
-    for (int c = 0; c < d; ++c)  // Li = L^-1 by forward substitution on unit vectors
-        for (int i = 0; i < d; ++i) {
-            double s = (i == c) ? 1.0 : 0.0;
-            for (int k = 0; k < i; ++k) s -= L[i * d + k] * Li[k * d + c];
-            Li[i * d + c] = s / L[i * d + i];
-        }
-    Ainv.assign((size_t)d * d, 0.0);
-    for (int i = 0; i < d; ++i)
-        for (int j = 0; j < d; ++j) {
-            double s = 0.0;
-            for (int k = 0; k < d; ++k) s += Li[k * d + i] * Li[k * d + j];
-            Ainv[i * d + j] = s;
-        }
-    if (Linv) *Linv = Li;
-    return true;
-}
-
 }  // namespace
 
 extern "C" {
@@ -1588,211 +1553,18 @@ int32_t demc_set_model(demc_handle* h, int32_t family, const double* data, const
     if (!h) return DEMC_EINVAL;
     USE_DEVICE(h);
     if (ndims < 0 || ndims > 4 || (ndims > 0 && !dims)) return fail(h, DEMC_EINVAL, "bad dims");
-    long long dm[4] = {0, 0, 0, 0};
-    for (int i = 0; i < ndims; ++i) dm[i] = dims[i];
-    const int D = h->c.D;
     if (int rc = clear_model(h)) return rc;
-    std::vector<double> dev;  // what goes to h->m.data
-    switch (family) {
-        case DEMC_FAM_GAUSSIAN:
-            if (D != 2 || dm[0] < 1) return fail(h, DEMC_EINVAL, "GAUSSIAN: theta=(mu,sigma), dims=[N]");
-            h->m.N = dm[0];
-            dev.assign(data, data + dm[0]);
-            break;
-        case DEMC_FAM_BINOMIAL: {
-            if (D != 1 || dm[0] < 1) return fail(h, DEMC_EINVAL, "BINOMIAL: theta=p, dims=[N], data=[n[N],k[N]]");
-            const long long N = dm[0];
-            h->m.N = N;
-            dev.assign(data, data + 2 * N);
-            dev.resize(3 * N);
-            for (long long i = 0; i < N; ++i) {
-                const double n = data[i], k = data[N + i];
-                dev[2 * N + i] = std::lgamma(n + 1.0) - std::lgamma(k + 1.0) - std::lgamma(n - k + 1.0);
-            }
-            h->m.data2_off = (size_t)N;
-        } break;
-        case DEMC_FAM_HIER_BINOMIAL: {
-            if (D != dm[0] + 2 || nhyper < 1) return fail(h, DEMC_EINVAL, "HIER_BINOMIAL: D=S+2, dims=[S], hyper=[n]");
-            const long long S = dm[0];
-            h->m.N = S;
-            h->m.c0 = hyper[0];
-            dev.assign(data, data + S);
-            dev.resize(2 * S);
-            double lgc_sum = 0.0;
-            for (long long s = 0; s < S; ++s) {
-                const double n = hyper[0], k = data[s];
-                dev[S + s] = std::lgamma(n + 1.0) - std::lgamma(k + 1.0) - std::lgamma(n - k + 1.0);
-                lgc_sum += dev[S + s];
-            }
-            h->m.c2 = lgc_sum;  // the long-row kernel adds the coefficients as one data-only constant
-        } break;
-        case DEMC_FAM_HIER_GAUSSIAN:
-            if (D != dm[0] + 3 || dm[1] < 1) return fail(h, DEMC_EINVAL, "HIER_GAUSSIAN: D=S+3, dims=[S,n]");
-            h->m.N = dm[0];
-            h->m.d = (int)dm[1];
-            dev.assign(data, data + dm[0] * dm[1]);
-            break;
-        case DEMC_FAM_LBA:
-        case DEMC_FAM_LNR: {
-            const int extra = (family == DEMC_FAM_LBA) ? 3 : 1;
-            if (dm[1] < 1 || dm[1] > 8 || D != dm[1] + extra) return fail(h, DEMC_EINVAL, "LBA/LNR: dims=[N,n_acc<=8]");
-            // data = [choice[N] ; rt[N]]: the kernels pick the winning accumulator by comparing the choice code with 1..n_acc
-            // (k_lba_wave: exact double equality) and the sort below compares decision times -- a non-integral or out-of-range
-            // code would silently make every accumulator a loser, a NaN is no strict weak ordering: refused here
-            for (long long i = 0; i < dm[0]; ++i) {
-                const double ch = data[i], rt = data[dm[0] + i];
-                if (!(ch >= 1.0 && ch <= (double)dm[1] && ch == std::floor(ch)))
-                    return fail(h, DEMC_EINVAL, "LBA/LNR: choice of trial " + std::to_string(i) + " is not an integer in [1, n_acc]");
-                if (!std::isfinite(rt)) return fail(h, DEMC_EINVAL, "LBA/LNR: decision time of trial " + std::to_string(i) + " is not finite");
-            }
-            h->m.N = dm[0];
-            h->m.n_acc = (int)dm[1];
-            h->m.c0 = (family == DEMC_FAM_LNR) ? (nhyper > 0 ? hyper[0] : 1.0) : 0.0;
-            dev.assign(data, data + 2 * dm[0]);
-            h->m.data2_off = (size_t)dm[0];
-            if (family == DEMC_FAM_LBA) {
-                // The log-likelihood is a sum over trials: their order is the library's to choose.  Sorted by (choice, decision time)
-                // the 64 lanes of k_lba_wave -- 64 consecutive trials of one proposal -- read the same row or two of the Phi table and
-                // share their winner (demc_kernels.hpp).
-                const size_t N = (size_t)dm[0];
-                std::vector<size_t> order(N);
-                for (size_t i = 0; i < N; ++i) order[i] = i;
-                std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b2) {
-                    return data[a] != data[b2] ? data[a] < data[b2] : data[N + a] < data[N + b2];
-                });
-                for (size_t i = 0; i < N; ++i) { dev[i] = data[order[i]]; dev[N + i] = data[N + order[i]]; }
-            }
-        } break;
-        case DEMC_FAM_RASTRIGIN:
-            h->m.N = 1;
-            break;
-        case DEMC_FAM_ODE_LV: {
-            if (D != 5) return fail(h, DEMC_EINVAL, "ODE_LV: D = 5 required, theta=(alpha,beta,gamma,delta,sigma)");
-            if (ndims < 2 || dm[1] != 2) return fail(h, DEMC_EINVAL, "ODE_LV: dims[1] = 2 required, dims=[T,2] (the observed x and y per time)");
-            if (dm[0] < 1 || dm[0] > kOdeMaxT)
-                return fail(h, DEMC_EINVAL, "ODE_LV: T = dims[0] = " + std::to_string(dm[0]) + " is outside [1, " + std::to_string(kOdeMaxT) + "]");
-            if (nhyper != 4 || !hyper) return fail(h, DEMC_EINVAL, "ODE_LV: hyper=[x0, y0, dt, substeps] (nhyper = 4)");
-            if (!(hyper[3] >= 1.0 && hyper[3] <= (double)kOdeMaxSubsteps && hyper[3] == std::floor(hyper[3])))
-                return fail(h, DEMC_EINVAL, "ODE_LV: substeps (hyper[3]) must be an integer in [1, " + std::to_string(kOdeMaxSubsteps) + "]");
-            if (!(std::isfinite(hyper[2]) && hyper[2] > 0.0)) return fail(h, DEMC_EINVAL, "ODE_LV: dt (hyper[2]) must be finite and positive");
-            if (!std::isfinite(hyper[0]) || !std::isfinite(hyper[1])) return fail(h, DEMC_EINVAL, "ODE_LV: u0 = (x0, y0) (hyper[0], hyper[1]) must be finite");
-            if (!data) return fail(h, DEMC_EINVAL, "ODE_LV: data = Y[T][2] required");
-            for (long long i = 0; i < 2 * dm[0]; ++i)
-                if (!std::isfinite(data[i]))
-                    return fail(h, DEMC_EINVAL, "ODE_LV: data value " + std::to_string(i) + " (time " + std::to_string(i / 2) + ") is not finite");
-            h->m.N = dm[0];
-            h->m.ode_substeps = (int)hyper[3];
-            h->m.ode_u0[0] = hyper[0]; h->m.ode_u0[1] = hyper[1]; h->m.ode_u0[2] = h->m.ode_u0[3] = 0.0;
-            h->m.ode_h = hyper[2] / hyper[3];
-            dev.assign(data, data + 2 * dm[0]);
-        } break;
-        case DEMC_FAM_MVN_ISO:
-        case DEMC_FAM_MVN_FULL: {
-            const long long N = dm[0];
-            const int d = (int)dm[1];
-            if (N < 1 || d < 1) return fail(h, DEMC_EINVAL, "MVN: dims=[N,d]");
-            if (d > 1024) return fail(h, DEMC_EUNSUPPORTED, "MVN families: data dimension d <= 1024");
-            if (family == DEMC_FAM_MVN_ISO && D != d + 1) return fail(h, DEMC_EINVAL, "MVN_ISO: D=d+1");
-            if (family == DEMC_FAM_MVN_FULL && (D != d || nhyper != d * d)) return fail(h, DEMC_EINVAL, "MVN_FULL: D=d, hyper=Sigma[d][d]");
-            h->m.N = N;
-            h->m.d = d;
-            // k-steps of 4 dims: one pass of KS in {1,2,4,8,16} steps for d <= 64, else passes of 16 steps
-            if (d <= 64) { h->m.ks_t = pow2_ceil((d + 3) / 4); h->m.n_kpass = 1; }
-            else { h->m.ks_t = 16; h->m.n_kpass = (d + 63) / 64; }
-            h->m.dpad = 4 * h->m.ks_t * h->m.n_kpass;
-            if ((N + 15) / 16 > 0x3fffffff) return fail(h, DEMC_EINVAL, "too many observations");
-            h->m.n_tiles = (int)((N + 15) / 16);
-            const bool direct = h->c.loglike_mode == DEMC_LOGLIKE_DIRECT;
-            if (direct && d > 64) return fail(h, DEMC_EUNSUPPORTED, "DIRECT likelihood: data dimension d <= 64 (the whitened proposal lives in registers)");
-            std::vector<double> Ainv, Linv;
-            double logdet = 0.0;
-            if (family == DEMC_FAM_MVN_FULL) {
-                if (!chol_inv(hyper, d, Ainv, logdet, &Linv)) return fail(h, DEMC_EINVAL, "Sigma is not positive definite");
-                h->m.c0 = -0.5 * (double)N * (d * kLog2Pi + logdet);
-                ALLOC(h->m.Ainv, (size_t)d * d);
-                // K1's preparation forms y_c = sum_k M[k][c] (theta' - xbar)_k.  M = Sigma^-1 (symmetric) gives y = Sigma^-1 mu~;
-                // in DIRECT mode M = (L^-1)' gives the whitened proposal m = L^-1 mu~ instead.
-                std::vector<double> M = Ainv;
-                if (direct)
-                    for (int r = 0; r < d; ++r)
-                        for (int cc = 0; cc < d; ++cc) M[(size_t)r * d + cc] = Linv[(size_t)cc * d + r];
-                HIPCHK(hipMemcpy(h->m.Ainv, M.data(), sizeof(double) * d * d, hipMemcpyHostToDevice));
-            }
-            // The data are CENTRED once (x~_i = x_i - xbar) and proposals are shifted the same way in K1
-            // (mu~ = theta' - xbar): (x_i - mu) = (x~_i - mu~), but every term of the expanded quadratic form
-            //   sum_i x~_i' A^-1 x~_i  -  2 y . sum_i x~_i  +  N mu~' A^-1 mu~ ,   y = A^-1 mu~
-            // is then O(N d) whatever the offset of the data, so the expansion loses no digits to cancellation.
-            // data-only constants: c1 = sum_i x~_i' A^-1 x~_i (A = I for ISO), sx = sum_i x~_i (~ 0)
-            std::vector<double> xbar(d, 0.0);
-            for (long long i = 0; i < N; ++i)
-                for (int k = 0; k < d; ++k) xbar[k] += data[i * d + k];
-            for (int k = 0; k < d; ++k) xbar[k] /= (double)N;
-            std::vector<double> xc((size_t)N * d);
-            for (long long i = 0; i < N; ++i)
-                for (int k = 0; k < d; ++k) xc[(size_t)i * d + k] = data[i * d + k] - xbar[k];
-            data = xc.data();
-            std::vector<double> sx(d, 0.0), t(d);
-            double c1 = 0.0;
-            for (long long i = 0; i < N; ++i) {
-                const double* x = data + i * d;
-                double q = 0.0;
-                if (family == DEMC_FAM_MVN_FULL) {
-                    for (int r = 0; r < d; ++r) {
-                        double sr = 0.0;
-                        for (int k = 0; k < d; ++k) sr += Ainv[r * d + k] * x[k];
-                        q += x[r] * sr;
-                    }
-                } else
-                    for (int k = 0; k < d; ++k) q += x[k] * x[k];
-                c1 += q;
-                for (int k = 0; k < d; ++k) sx[k] += x[k];
-            }
-            h->m.c1 = c1;
-            ALLOC(h->m.sx, (size_t)d);
-            HIPCHK(hipMemcpy(h->m.sx, sx.data(), sizeof(double) * d, hipMemcpyHostToDevice));
-            ALLOC(h->m.xbar, (size_t)d);
-            HIPCHK(hipMemcpy(h->m.xbar, xbar.data(), sizeof(double) * d, hipMemcpyHostToDevice));
-            ALLOC(h->m.Ypad, (size_t)h->P * h->m.dpad);
-            // fragment-ordered copy of X for v_mfma_f64_16x16x4_f64's B operand:
-            //   Xf[tile][kstep][lane] = X[16*tile + (lane&15)][4*kstep + (lane>>4)], zero padded
-            const int ksx = h->m.dpad / 4;
-            std::vector<double> xf(((size_t)h->m.n_tiles + 1) * ksx * 64, 0.0);  // +1: the all-zero tail tile
-            for (long long tI = 0; tI < h->m.n_tiles; ++tI)
-                for (int ks = 0; ks < ksx; ++ks)
-                    for (int l = 0; l < 64; ++l) {
-                        const long long i = 16 * tI + (l & 15);
-                        const int k = 4 * ks + (l >> 4);
-                        if (i < N && k < d) xf[((size_t)tI * ksx + ks) * 64 + l] = data[i * d + k];
-                    }
-            ALLOC(h->m.Xf, xf.size());
-            HIPCHK(hipMemcpy(h->m.Xf, xf.data(), sizeof(double) * xf.size(), hipMemcpyHostToDevice));
-            if (direct) {
-                // whitened, centred observations z_i = L^-1 x~_i (ISO: x~_i), rows padded with zeros to DP scalars
-                h->m.dp_direct = d <= 8 ? 8 : d <= 16 ? 16 : d <= 32 ? 32 : 64;
-                const int DP = h->m.dp_direct;
-                dev.assign((size_t)N * DP, 0.0);
-                for (long long i = 0; i < N; ++i) {
-                    const double* x = data + i * d;
-                    double* zr = dev.data() + (size_t)i * DP;
-                    if (family == DEMC_FAM_MVN_FULL) {
-                        for (int r = 0; r < d; ++r) {
-                            double sr = 0.0;
-                            for (int k = 0; k <= r; ++k) sr += Linv[(size_t)r * d + k] * x[k];
-                            zr[r] = sr;
-                        }
-                    } else
-                        for (int k = 0; k < d; ++k) zr[k] = x[k];
-                }
-            }
-        } break;
-        default:
-            return fail(h, DEMC_EUNSUPPORTED, "model family is not registered; arbitrary closures cannot run on the device");
-    }
-    if (!dev.empty()) {
-        ALLOC(h->m.data, dev.size());
-        HIPCHK(hipMemcpy(h->m.data, dev.data(), sizeof(double) * dev.size(), hipMemcpyHostToDevice));
-    }
-    h->m.family = family;
+    const PreparedModel pm = prepare_model(family, h->c.D, h->c.loglike_mode, data, dims, ndims, hyper, nhyper);
+    if (pm.refused) return fail(h, pm.refused);
+    Model& m = h->m;
+    static_cast<ModelShape&>(m) = pm;
+    if (int rc = upload(h, m.Ainv, pm.M)) return rc;
+    if (int rc = upload(h, m.sx, pm.sx)) return rc;
+    if (int rc = upload(h, m.xbar, pm.xbar)) return rc;
+    if (is_mvn(family)) ALLOC(m.Ypad, (size_t)h->P * m.dpad);
+    if (int rc = upload(h, m.Xf, pm.Xf)) return rc;
+    if (int rc = upload(h, m.data, pm.data)) return rc;
+    m.family = family;
     return size_k1_lds(h);
     });
 }
@@ -1852,56 +1624,9 @@ int32_t demc_set_model_sim(demc_handle* h, int32_t simulator, int32_t estimator,
     return guarded(h, [&]() -> int32_t {
     if (!h) return DEMC_EINVAL;
     USE_DEVICE(h);
-    if (simulator != DEMC_SIM_NORMAL && simulator != DEMC_SIM_BINOMIAL && simulator != DEMC_SIM_LNR && simulator != DEMC_SIM_USER)
-        return fail(h, DEMC_EINVAL, "demc_set_model_sim: unknown simulator");
-    if (estimator != DEMC_SIMEST_KDE_EPANECHNIKOV && estimator != DEMC_SIMEST_FREQUENCY && estimator != DEMC_SIMEST_KDE_CHOICE)
-        return fail(h, DEMC_EINVAL, "demc_set_model_sim: unknown estimator");
-    const bool pairs = estimator == DEMC_SIMEST_KDE_CHOICE;
-    if (simulator == DEMC_SIM_LNR && !pairs)
-        return fail(h, DEMC_EINVAL, std::string("demc_set_model_sim: DEMC_SIM_LNR simulates (choice, time) pairs and cannot be scored by the scalar estimator ") +
-                                        (estimator == DEMC_SIMEST_FREQUENCY ? "DEMC_SIMEST_FREQUENCY" : "DEMC_SIMEST_KDE_EPANECHNIKOV") + " (use DEMC_SIMEST_KDE_CHOICE)");
-    if (pairs && (simulator == DEMC_SIM_NORMAL || simulator == DEMC_SIM_BINOMIAL))
-        return fail(h, DEMC_EINVAL, std::string("demc_set_model_sim: ") + (simulator == DEMC_SIM_NORMAL ? "DEMC_SIM_NORMAL" : "DEMC_SIM_BINOMIAL") +
-                                        " simulates scalars and cannot be scored by DEMC_SIMEST_KDE_CHOICE (use DEMC_SIM_LNR or a user simulator of pairs)");
-    if (n_sim < 2) return fail(h, DEMC_EINVAL, "demc_set_model_sim: n_sim < 2 (a density estimate needs at least two simulated values)");
-    const int64_t cap = pairs ? kSimChoiceMaxN : kSimMaxN;
     static_assert(sim_choice_lds(kSimChoiceMaxN) <= kMaxDynLds && sim_choice_lds(10000) <= kMaxDynLds, "k_sim_choice: the cap does not fit the LDS of a launch");
-    if (n_sim > cap)
-        return fail(h, DEMC_EINVAL, "demc_set_model_sim: n_sim = " + std::to_string(n_sim) + " is above the cap of " + std::to_string(cap) +
-                                        " simulated values (the sample of a proposal is held in LDS)");
-    if (n_obs < 1 || !data) return fail(h, DEMC_EINVAL, "demc_set_model_sim: n_obs >= 1 observations required");
-    if (nhyper < 0 || (nhyper > 0 && !hyper)) return fail(h, DEMC_EINVAL, "demc_set_model_sim: nhyper > 0 without hyper");
-    if (simulator == DEMC_SIM_USER && (!hip_source || !hip_source[0]))
-        return fail(h, DEMC_EINVAL, "demc_set_model_sim: DEMC_SIM_USER needs hip_source (a definition of demc_user_sim; demc_user_sim_choice under DEMC_SIMEST_KDE_CHOICE)");
-    if (simulator != DEMC_SIM_USER && hip_source && hip_source[0])
-        return fail(h, DEMC_EINVAL, "demc_set_model_sim: hip_source given with a registered simulator");
-    if (simulator == DEMC_SIM_NORMAL && h->c.D != 2) return fail(h, DEMC_EINVAL, "SIM_NORMAL: theta=(mu,sigma)");
-    if (simulator == DEMC_SIM_BINOMIAL) {
-        if (h->c.D != 1) return fail(h, DEMC_EINVAL, "SIM_BINOMIAL: theta=p");
-        if (nhyper < 2 || !(hyper[1] >= 1.0 && hyper[1] <= 1024.0 && hyper[1] == std::floor(hyper[1])))
-            return fail(h, DEMC_EINVAL, "SIM_BINOMIAL: hyper=[bandwidth, n_trials], n_trials an integer in [1, 1024]");
-        if (n_sim * (((int64_t)hyper[1] + 3) / 4) > 0x7fffffffLL) return fail(h, DEMC_EINVAL, "SIM_BINOMIAL: too many Philox blocks per proposal");
-    }
-    if (simulator == DEMC_SIM_LNR) {
-        if (h->c.D < 3 || h->c.D > 9) return fail(h, DEMC_EINVAL, "SIM_LNR: theta=(nu[K],tau), K = D - 1 in [2, 8]");
-        if (nhyper < 2 || !(hyper[1] > 0.0)) return fail(h, DEMC_EINVAL, "SIM_LNR: hyper=[bandwidth, sigma], sigma > 0");
-    }
-    int kmax = 0;
-    if (pairs) {  // host_data = the n_obs choices, then the n_obs times
-        const int hi = simulator == DEMC_SIM_LNR ? h->c.D - 1 : 255;
-        for (int64_t j = 0; j < n_obs; ++j) {
-            const double c = data[j];
-            if (!(c >= 1.0 && c <= (double)hi && c == std::floor(c)))
-                return fail(h, DEMC_EINVAL, "demc_set_model_sim: the choice of observation " + std::to_string(j) + " is not an integer in [1, " + std::to_string(hi) + "]");
-            if (!std::isfinite(data[n_obs + j]))
-                return fail(h, DEMC_EINVAL, "demc_set_model_sim: the response time of observation " + std::to_string(j) + " is not finite");
-            kmax = std::max(kmax, (int)c);
-        }
-    }
-    if (estimator == DEMC_SIMEST_FREQUENCY)
-        for (int64_t j = 0; j < n_obs; ++j)
-            if (!(data[j] == std::floor(data[j])))
-                return fail(h, DEMC_EINVAL, "demc_set_model_sim: the FREQUENCY estimator needs integer-valued data (observation " + std::to_string(j) + " is not)");
+    const PreparedSim ps = prepare_sim(h->c.D, simulator, estimator, n_sim, hip_source, data, n_obs, hyper, nhyper);
+    if (ps.refused) return fail(h, ps.refused);
     if (int rc = clear_model(h)) return rc;
     if (simulator == DEMC_SIM_USER) {
         // the one kernel text (demc_simlike.hpp) with n_sim and the estimator compiled in, the user's function behind it
@@ -1912,70 +1637,28 @@ int32_t demc_set_model_sim(demc_handle* h, int32_t simulator, int32_t estimator,
             return rc;
     }
     h->m.N = n_obs;
-    const size_t n_data = (size_t)n_obs * (pairs ? 2 : 1);
+    const size_t n_data = (size_t)n_obs * (estimator == DEMC_SIMEST_KDE_CHOICE ? 2 : 1);
     ALLOC(h->m.data, n_data);
     HIPCHK(hipMemcpy(h->m.data, data, sizeof(double) * n_data, hipMemcpyHostToDevice));
-    h->m.sim_kmax = kmax;
-    // hyper as the kernels see it: [bandwidth, the simulator's own ...]
-    h->m.user_nhyper = nhyper > 0 ? nhyper : 1;
-    {
-        std::vector<double> hy((size_t)h->m.user_nhyper, 0.0);
-        for (int i = 0; i < nhyper; ++i) hy[(size_t)i] = hyper[i];
-        ALLOC(h->m.user_hyper, hy.size());
-        HIPCHK(hipMemcpy(h->m.user_hyper, hy.data(), sizeof(double) * hy.size(), hipMemcpyHostToDevice));
-        h->m.sim_bw = hy[0] > 0.0 ? hy[0] : 0.0;
-    }
-    if (estimator == DEMC_SIMEST_FREQUENCY) {
-        std::vector<double> lt((size_t)n_sim + 1);
-        for (int64_t c = 0; c <= n_sim; ++c) lt[(size_t)c] = std::log((double)c / (double)n_sim);  // (log 0 = -Inf: a count of zero)
-        ALLOC(h->m.sim_logtab, lt.size());
-        HIPCHK(hipMemcpy(h->m.sim_logtab, lt.data(), sizeof(double) * lt.size(), hipMemcpyHostToDevice));
-    }
+    h->m.sim_kmax = ps.kmax;
+    h->m.user_nhyper = (int)ps.hyper.size();
+    if (int rc = upload(h, h->m.user_hyper, ps.hyper)) return rc;
+    h->m.sim_bw = ps.sim_bw;
+    if (int rc = upload(h, h->m.sim_logtab, ps.logtab)) return rc;
     h->m.sim_kind = simulator; h->m.sim_est = estimator; h->m.sim_n = (int)n_sim;
     h->m.family = FAM_SIM;
     return size_k1_lds(h);
     });
 }
 
-// DEMC_PRIOR_TRUNCNORMAL: log(Phi((hi - a) / b) - Phi((lo - a) / b)), the mass of Normal(a, b) between the bounds of scalar j, from
-// erfc on the side of the mean where the difference does not cancel (both bounds above the mean: the upper tails).  DEMC_EINVAL
-// when the bounds are empty or the mass is 0 or not finite -- the density would be a division by it.
-static int truncnormal_log_mass(demc_handle* h, size_t j, double a, double b, double lo, double hi, double* out) {
-    const std::string who = "DEMC_PRIOR_TRUNCNORMAL, scalar " + std::to_string(j) + ": ";
-    if (!(std::isfinite(a) && std::isfinite(b) && b > 0.0)) return fail(h, DEMC_EINVAL, who + "Normal(a, b) needs a finite a and a finite b > 0");
-    if (!(lo < hi)) return fail(h, DEMC_EINVAL, who + "the bounds lo >= hi leave nothing to truncate to");
-    const double zl = (lo - a) / b, zh = (hi - a) / b, r = std::sqrt(0.5);
-    // Phi(z) = erfc(-z / sqrt 2) / 2; 1 - Phi(z) = erfc(z / sqrt 2) / 2
-    const double mass = zl > 0.0 ? 0.5 * (std::erfc(zl * r) - std::erfc(zh * r)) : 0.5 * (std::erfc(-zh * r) - std::erfc(-zl * r));
-    if (!(mass > 0.0) || !std::isfinite(mass))
-        return fail(h, DEMC_EINVAL, who + "the mass of the Normal between the bounds is 0 or not finite");
-    *out = std::log(mass);
-    return DEMC_OK;
-}
-
 static int upload_dimtab(demc_handle* h) {
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipMemcpy(h->dimtab, h->h_tab.data(), (size_t)h->c.D * sizeof(DimTab), hipMemcpyHostToDevice));
-    // run-length form: consecutive scalars with byte-identical entries share a segment
-    DimSeg segs[kMaxDimSeg];
-    std::memset(segs, 0, sizeof segs);
-    int n = 0;
-    for (int j = 0; j < h->c.D; ++j) {
-        if (j == 0 || std::memcmp(&h->h_tab[(size_t)j], &h->h_tab[(size_t)j - 1], sizeof(DimTab)) != 0) {
-            if (n == kMaxDimSeg) { n = -1; break; }
-            segs[n].start = j;
-            segs[n].t = h->h_tab[(size_t)j];
-            ++n;
-        }
-    }
-    h->n_seg = n > 0 ? n : 0;
-    h->seg_plain = 0;
-    for (int q = 0; q < kMaxDimSeg; ++q) {
-        h->seg_start[q] = q < h->n_seg ? segs[q].start : 0;
-        const int kd = segs[q].t.kind;
-        if (q < h->n_seg && (kd == PR_FLAT || kd == PR_NORMAL || kd == PR_NORMAL_REF)) h->seg_plain |= 1u << q;
-    }
-    HIPCHK(hipMemcpy(h->dimseg, segs, sizeof segs, hipMemcpyHostToDevice));
+    const SegTable st = encode_segments(h->h_tab);
+    h->n_seg = st.n_seg;
+    std::memcpy(h->seg_start, st.seg_start, sizeof h->seg_start);
+    h->seg_plain = st.seg_plain;
+    HIPCHK(hipMemcpy(h->dimseg, st.segs, sizeof st.segs, hipMemcpyHostToDevice));
     // the lean resident kernel reads the table in its run-length form and knows no Normal(a, theta[ref]) prior: priors and
     // bounds arrive AFTER demc_set_model in every caller, so its plan is taken again whenever the table changes
     return h->m.family >= 0 ? plan_lean(h) : DEMC_OK;
@@ -1985,40 +1668,8 @@ int32_t demc_set_priors(demc_handle* h, const int32_t* kind, const double* a, co
     return guarded(h, [&]() -> int32_t {
     if (!h || !kind) return DEMC_EINVAL;
     USE_DEVICE(h);
-    const size_t D = (size_t)h->c.D;
-    for (size_t j = 0; j < D; ++j) {
-        if (kind[j] < 0 || kind[j] > DEMC_PRIOR_TRUNCNORMAL) return fail(h, DEMC_EUNSUPPORTED, "prior kind not registered");
-        if (kind[j] == DEMC_PRIOR_NORMAL_REF && (!ref || ref[j] < 0 || ref[j] >= (int)D))
-            return fail(h, DEMC_EINVAL, "prior ref out of range");
-    }
     // (checked against the bounds in force before anything is stored: a refused call leaves the table as it was)
-    for (size_t j = 0; j < D; ++j)
-        if (kind[j] == DEMC_PRIOR_TRUNCNORMAL) {
-            double lm = 0.0;
-            if (int rc = truncnormal_log_mass(h, j, a ? a[j] : 0.0, b ? b[j] : 1.0, h->h_tab[j].lo, h->h_tab[j].hi, &lm)) return rc;
-        }
-    h->trunc_sd.assign(D, 0.0);
-    for (size_t j = 0; j < D; ++j) {
-        DimTab& t = h->h_tab[j];
-        const double aj = a ? a[j] : 0.0, bj = b ? b[j] : 1.0;
-        // truncated(Normal(a, b), lo, hi): the device's Normal entry, its constant lowered by the log of the mass between the bounds
-        const bool trunc = kind[j] == DEMC_PRIOR_TRUNCNORMAL;
-        const int kd = trunc ? (int)PR_NORMAL : kind[j];
-        t.kind = kd;
-        t.ref = ref ? ref[j] : 0;
-        t.a = aj;
-        // reciprocal scale for the location-scale families: no FP64 division per scalar in the kernels
-        const bool recip = kd == PR_NORMAL || kd == PR_HALFCAUCHY || kd == PR_GAMMA ||
-                           kd == PR_EXPONENTIAL || kd == PR_LOGNORMAL || kd == PR_CAUCHY;
-        t.b = recip ? 1.0 / bj : bj;
-        t.c = prior_const(kd, aj, bj);
-        if (trunc) {
-            double lm = 0.0;
-            truncnormal_log_mass(h, j, aj, bj, t.lo, t.hi, &lm);
-            t.c -= lm;
-            h->trunc_sd[j] = bj;
-        }
-    }
+    if (Refusal r = prepare_priors(h->h_tab, h->trunc_sd, kind, a, b, ref)) return fail(h, r);
     return upload_dimtab(h);
     });
 }
@@ -2027,19 +1678,8 @@ int32_t demc_set_bounds(demc_handle* h, const double* lo, const double* hi) {
     return guarded(h, [&]() -> int32_t {
     if (!h || !lo || !hi) return DEMC_EINVAL;
     USE_DEVICE(h);
-    const size_t D = (size_t)h->c.D;
-    // Truncated Normal priors: their constant holds the mass between the bounds, so it is formed again from the new ones -- priors
-    // and bounds arrive in either order.  Checked first: a refused call leaves the table as it was.
-    std::vector<double> lm(D, 0.0);
-    for (size_t j = 0; j < D; ++j)
-        if (j < h->trunc_sd.size() && h->trunc_sd[j] != 0.0)
-            if (int rc = truncnormal_log_mass(h, j, h->h_tab[j].a, h->trunc_sd[j], lo[j], hi[j], &lm[j])) return rc;
-    for (size_t j = 0; j < D; ++j) {
-        h->h_tab[j].lo = lo[j];
-        h->h_tab[j].hi = hi[j];
-        if (j < h->trunc_sd.size() && h->trunc_sd[j] != 0.0)
-            h->h_tab[j].c = prior_const(PR_NORMAL, h->h_tab[j].a, h->trunc_sd[j]) - lm[j];
-    }
+    // (checked first: a refused call leaves the table as it was)
+    if (Refusal r = prepare_bounds(h->h_tab, h->trunc_sd, lo, hi)) return fail(h, r);
     return upload_dimtab(h);
     });
 }
@@ -2054,19 +1694,8 @@ int32_t demc_set_blocks(demc_handle* h, const uint8_t* masks, int32_t n_blocks) 
         ALLOC(h->masks, (size_t)n_blocks * h->c.D);
         HIPCHK(hipMemcpy(h->masks, masks, (size_t)n_blocks * h->c.D, hipMemcpyHostToDevice));
     }
-    h->mask_runs.assign((size_t)n_blocks, demc_handle::MaskRuns());
-    for (int b = 0; b < n_blocks; ++b) {  // run-length form of each mask (kernarg table of the long-row kernel)
-        auto& mr = h->mask_runs[(size_t)b];
-        const uint8_t* mk = masks + (size_t)b * h->c.D;
-        for (int j = 0; j < h->c.D; ++j)
-            if (j == 0 || (mk[j] != 0) != (mk[j - 1] != 0)) {
-                if (mr.n == kMaxMaskRun) { mr.n = -1; break; }
-                mr.start[mr.n] = j;
-                if (mk[j]) mr.in |= 1u << mr.n;
-                ++mr.n;
-            }
-        if (mr.n < 0) mr = demc_handle::MaskRuns();
-    }
+    h->mask_runs.clear();
+    for (int b = 0; b < n_blocks; ++b) h->mask_runs.push_back(encode_mask(masks + (size_t)b * h->c.D, h->c.D));
     return plan_snap2(h);
     });
 }

@@ -29,27 +29,7 @@ enum Family : int {
 };
 enum Mode : int { MODE_STEP = 0, MODE_IDENT = 1 };  // IDENT: theta' = theta, always accepted (init / logpost)
 
-// Per-scalar constants, packed so that one dimension costs three 16-byte loads: bounds (de.bounds flattened) and
-// the prior entry (model.prior_loglike as data).  b = 1/scale for Normal / half-Cauchy; c = the x-independent
-// part of the log-density (prior_const()).
-struct DimTab {
-    double lo, hi;
-    double a, b;
-    double c;
-    int kind, ref;
-};
-
-// Run-length form of the DimTab array: models give whole blocks of scalars the same bounds and prior (cfg4: 10 000 subject
-// effects ~ Normal(0, sd); cfg3: 32 means ~ Normal(0,1)), so the table is a handful of segments.  The kernels keep them in LDS
-// and look a scalar's entry up by its segment instead of streaming 48 bytes per scalar from L2/HBM -- at D = 10 002 that
-// stream was larger than the particle rows themselves.
-struct DimSeg {
-    int start, pad;  // first scalar of the segment
-    DimTab t;
-    double pad2;
-};
-constexpr int kMaxDimSeg = 16;
-constexpr int kMaxMaskRun = 16;
+// DimTab, DimSeg, kMaxDimSeg, kMaxMaskRun: demc_dimtab.hpp (through demc_device.hpp)
 
 // Everything a sweep needs, passed by value as the kernarg.
 struct KParams {

@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LOG_2PI = 1.8378770664093454835606594728112  # kLog2Pi of csrc/demc_device.hpp: the double the kernel adds
+LOG_2PI = 1.8378770664093454835606594728112  # kLog2Pi of csrc/demc_dimtab.hpp: the double the kernel adds
 TRUTH = (1.5, 1.0, 3.0, 1.0)       # Examples/Predator_Prey_Example.jl:14
 U0, DT, T_EXAMPLE = (1.0, 1.0), 0.1, 101
 
