@@ -30,6 +30,8 @@ EXPORTS = [
 SUMMARY_EXPORTS = ["demc_summarize"]  # include/demc_summary.h: the header next to demc.h (what follows a run)
 QUANTILE_EXPORTS = ["demc_quantiles"]  # include/demc_quantile.h: the second table of describe(chains)
 QUANTILE_MAX_PROBS = 16  # DEMC_QUANTILE_MAX_PROBS
+COV_EXPORTS = ["demc_covariance"]  # include/demc_cov.h: cov(chains) / cor(chains)
+COV_MAX_COLS = 64  # DEMC_COV_MAX_COLS
 COMM_ID_BYTES = 128
 _NOT_STATUS = {"demc_last_error": C.c_char_p, "demc_multi_last_error": C.c_char_p, "demc_multi_shard": C.c_void_p}
 
@@ -146,6 +148,7 @@ def load():
     L.demc_export_chains.argtypes = [H, C.c_int64, C.c_int64, C.c_int32, _dp]
     L.demc_summarize.argtypes = [H, C.c_int64, C.c_int64, C.c_int32, _dp, _dp, C.c_int64]
     L.demc_quantiles.argtypes = [H, C.c_int64, C.c_int64, _dp, C.c_int32, _dp]
+    L.demc_covariance.argtypes = [H, C.c_int64, C.c_int64, C.POINTER(C.c_int32), C.c_int32, _dp, _dp, _dp]
     L.demc_step.argtypes = [H, C.c_int64, C.c_int32]
     L.demc_update.argtypes = [H, C.c_int64, C.c_int32]
     L.demc_migration_due.argtypes = [C.POINTER(DemcConfig), C.c_int64]
@@ -178,7 +181,7 @@ def load():
     L.demc_multi_size.argtypes = [H]
     L.demc_multi_shard.argtypes = [H, C.c_int32]
     L.demc_multi_step.argtypes = [H, C.c_int64, C.c_int32]
-    for name in EXPORTS + SUMMARY_EXPORTS + QUANTILE_EXPORTS:  # every entry point returns an int32 status, except the error strings and the shard accessor
+    for name in EXPORTS + SUMMARY_EXPORTS + QUANTILE_EXPORTS + COV_EXPORTS:  # every entry point returns an int32 status, except the error strings and the shard accessor
         getattr(L, name).restype = _NOT_STATUS.get(name, C.c_int32)
     _lib = L
     return L
@@ -364,6 +367,19 @@ class HipEngine:
         out = np.empty((self.D + 2, len(probs)))
         self._ck(self.L.demc_quantiles(self.h, row0, row1, _d(probs), len(probs), _d(out)))
         return out
+
+    def covariance(self, row0, row1, cols=None):
+        """mean, covariance and correlation of history rows [row0,row1) formed on the device (demc_covariance of include/demc_cov.h,
+        DESIGN.md 5.7), chains pooled -> (mean[K], cov[K][K], cor[K][K]) of the series cols (None: all D + 2, in their order)"""
+        if cols is None:
+            K, cp = self.D + 2, None
+        else:
+            cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
+            K, cp = len(cols), cols.ctypes.data_as(C.POINTER(C.c_int32))
+        k = max(K, 1)
+        mean, cov, cor = np.empty(k), np.empty((k, k)), np.empty((k, k))
+        self._ck(self.L.demc_covariance(self.h, row0, row1, cp, K, _d(mean), _d(cov), _d(cor)))
+        return mean, cov, cor
 
     def step(self, iter0, n_iters=1):
         self._ck(self.L.demc_step(self.h, iter0, n_iters))

@@ -1,28 +1,35 @@
 """Minimal stand-in for MCMCChains.Chains: value array (iterations x parameters x chains) + names, and the
 summary statistics the reference's tests read from describe(chains)[1] (:mean, :std, :rhat), plus the effective sample size,
 its Monte-Carlo standard error and the autocorrelation MCMCChains adds to them (DESIGN.md section 5.5 is the definition; the device
-computes the same numbers from the history without exporting it: demc_summarize), and the quantile table of describe(chains)
-(demc_quantiles on the device)."""
+computes the same numbers from the history without exporting it: demc_summarize), the quantile table of describe(chains)
+(demc_quantiles on the device), and cov(chains) / cor(chains) (demc_covariance)."""
 import math
 
 import numpy as np
 
 SUMMARY_COLS = ("mean", "std", "rhat", "ess", "mcse", "pairs")  # the columns of demc_summarize's out (DEMC_SUMMARY_COLS)
 DEFAULT_QUANTILES = (0.025, 0.25, 0.5, 0.75, 0.975)  # MCMCChains' describe(chains)[2]
+COV_MAX_COLS = 64  # DEMC_COV_MAX_COLS: the series one call of demc_covariance takes
 
 
 class Summary:
     """The summary table of a run: `values[j]` = (mean, std, rhat, ess, mcse, pairs) of series names[j] -- the parameters,
     then acceptance and lp.  `rho` (or None): [series][lags] autocorrelations, NaN beyond the lags that were evaluated.
-    `quantiles` (or None): [series][len(probs)] quantiles at `probs`, chains pooled."""
+    `quantiles` (or None): [series][len(probs)] quantiles at `probs`, chains pooled.  `cov_matrix` / `cor_matrix`
+    (or None): the covariance and correlation of the series `cov_names`, chains pooled."""
 
-    def __init__(self, names, values, internals=("acceptance", "lp"), rho=None, quantiles=None, probs=None):
+    def __init__(self, names, values, internals=("acceptance", "lp"), rho=None, quantiles=None, probs=None, cov=None, cor=None,
+                 cov_names=None):
         self.names = list(names)
         self.values = np.asarray(values, dtype=np.float64).reshape(len(self.names), len(SUMMARY_COLS))
         self.internals = list(internals)
         self.rho = rho
         self.probs = None if quantiles is None else tuple(float(q) for q in probs)
         self.quantiles = None if quantiles is None else np.asarray(quantiles, dtype=np.float64).reshape(len(self.names), len(self.probs))
+        self.cov_names = None if cov_names is None else list(cov_names)
+        k = 0 if cov_names is None else len(self.cov_names)
+        self.cov_matrix = None if cov is None else np.asarray(cov, dtype=np.float64).reshape(k, k)
+        self.cor_matrix = None if cor is None else np.asarray(cor, dtype=np.float64).reshape(k, k)
 
     def __getitem__(self, name):
         return dict(zip(SUMMARY_COLS, (float(v) for v in self.values[self.names.index(name)])))
@@ -37,6 +44,18 @@ class Summary:
             raise ValueError("this Summary holds no quantiles: summarize(..., quantiles=DEFAULT_QUANTILES)")
         return {nm: dict(zip(self.probs, (float(v) for v in self.quantiles[j])))
                 for j, nm in enumerate(self.names) if nm not in self.internals}
+
+    def cov(self):
+        """(names, matrix): the covariance of the series the run was summarised with -- what Chains.cov(names) gives"""
+        if self.cov_matrix is None:
+            raise ValueError("this Summary holds no covariance: summarize(..., cor=True)")
+        return list(self.cov_names), self.cov_matrix
+
+    def cor(self):
+        """(names, matrix): the correlation of the series the run was summarised with -- what Chains.cor(names) gives"""
+        if self.cor_matrix is None:
+            raise ValueError("this Summary holds no correlation: summarize(..., cor=True)")
+        return list(self.cov_names), self.cor_matrix
 
 
 _SIGN, _ALL = np.uint64(1 << 63), np.uint64(0xFFFFFFFFFFFFFFFF)
@@ -77,6 +96,39 @@ def series_quantiles(x, probs):
             else:
                 out[i] = np.float64(1.0 - g) * np.float64(a) + np.float64(g) * np.float64(c)
     return out
+
+
+def series_cov(value, cols=None):
+    """DESIGN.md 5.7 on the host: value[n][series][chains] (the Chains value array), cols (None: every series) -> (mean[K], cov[K][K],
+    cor[K][K]) of the selected series, the chains pooled -- the corrected two-pass form demc_covariance computes on the device, in
+    FP64 with numpy's summation order"""
+    value = np.asarray(value, dtype=np.float64)
+    cols = list(range(value.shape[1])) if cols is None else [int(c) for c in cols]
+    K = len(cols)
+    if not 1 <= K or len(set(cols)) != K or min(cols) < 0 or max(cols) >= value.shape[1]:
+        raise ValueError("series_cov needs distinct series of the value array, at least one")
+    x = np.stack([value[:, c, :].reshape(-1) for c in cols], axis=1)  # [N][K]
+    N = x.shape[0]
+    if N < 1:
+        raise ValueError("series_cov needs at least one row")
+    nan = float("nan")
+    with np.errstate(all="ignore"):
+        mhat = x.sum(axis=0) / float(N)
+        c = x - mhat
+        s = c.sum(axis=0)
+        Q = np.einsum("ei,ej->ij", c, c)  # (not c.T @ c: a NaN column must stay in its own row and column whatever BLAS does)
+        S = Q - np.outer(s, s) / float(N)
+        S = np.triu(S) + np.triu(S, 1).T
+        mean = mhat + s / float(N)
+        if N == 1:
+            return mean, np.full((K, K), nan), np.full((K, K), nan)
+        cov = S / float(N - 1)
+        d = np.sqrt(np.diag(S))
+        cor = S / (d[:, None] * d[None, :])
+        cor = np.where(cor < -1.0, -1.0, np.where(cor > 1.0, 1.0, cor))
+        dg = np.diag(S)
+        cor[np.arange(K), np.arange(K)] = np.where(np.isfinite(dg) & (dg > 0.0), 1.0, nan)
+    return mean, cov, cor
 
 
 def series_summary(x, max_lag=0, rho_len=0):
@@ -175,6 +227,22 @@ class Chains:
         q = tuple(float(v) for v in q)
         return {nm: dict(zip(q, (float(v) for v in series_quantiles(self.value[:, j, :], q))))
                 for j, nm in enumerate(self.names) if nm not in self.internals}
+
+    def _cols(self, names):
+        """the series a covariance call selects: None -> the parameters; names may hold the internals too"""
+        names = [nm for nm in self.names if nm not in self.internals] if names is None else list(names)
+        return names, [self.names.index(nm) for nm in names]
+
+    def cov(self, names=None):
+        """(names, matrix): the sample covariance of the parameters (or of the series `names`), the chains pooled as
+        cov(Array(chains)) pools them"""
+        names, cols = self._cols(names)
+        return names, series_cov(self.value, cols)[1]
+
+    def cor(self, names=None):
+        """(names, matrix): the correlation matrix that goes with cov()"""
+        names, cols = self._cols(names)
+        return names, series_cov(self.value, cols)[2]
 
     def summarystats(self, max_lag=0, rho_len=0):
         """The Summary of this object computed on the host (numpy): what demc_summarize computes on the device for a history that

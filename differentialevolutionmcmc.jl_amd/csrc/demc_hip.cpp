@@ -11,6 +11,7 @@
 #include "../../include/demc.h"
 #include "../../include/demc_summary.h"  // demc_summarize
 #include "../../include/demc_quantile.h"  // demc_quantiles
+#include "../../include/demc_cov.h"  // demc_covariance
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -43,6 +44,7 @@
 #include "demc_ode.hpp"
 #include "demc_summary.hpp"  // demc_summarize: its kernels and their launches live in demc_summary.cpp
 #include "demc_quantile.hpp"  // demc_quantiles: likewise, demc_quantile.cpp
+#include "demc_cov.hpp"  // demc_covariance: likewise, demc_cov.cpp
 #include "demc_devmem.hpp"  // owners of the device memory, pinned memory, events and modules the handle holds
 #include "demc_prep.hpp"  // host-only: a model's data and constants, the prior table and its run-length forms, every refusal of those
 #include "demc_instances.hpp"  // one table per templated kernel, built from the lists above: every choice of an instance goes through them
@@ -1849,6 +1851,33 @@ int32_t demc_quantiles(demc_handle* h, int64_t row0, int64_t row1, const double*
     QArgs a{h->hist, h->acc_hist, h->lp_hist, h->P, (long long)row0, (long long)row1, h->c.D, h->hist_ld};
     std::string msg;
     const int rc = quantile_run(a, h->stream, probs, (int)n_probs, out, msg);
+    return rc == DEMC_OK ? DEMC_OK : fail(h, rc, msg);
+    });
+}
+
+int32_t demc_covariance(demc_handle* h, int64_t row0, int64_t row1, const int32_t* cols, int32_t n_cols, double* mean_out, double* cov_out,
+                        double* cor_out) {
+    return guarded(h, [&]() -> int32_t {
+    if (!h) return DEMC_EINVAL;
+    USE_DEVICE(h);
+    if (!mean_out && !cov_out && !cor_out) return fail(h, DEMC_EINVAL, "demc_covariance: mean_out, cov_out and cor_out are all NULL");
+    if (!h->hist) return fail(h, DEMC_EINVAL, "history is not stored on this handle");
+    if (row0 < 0 || row1 - row0 < 1 || row1 > h->c.n_rows) return fail(h, DEMC_EINVAL, "bad rows: demc_covariance needs at least one row of the history");
+    if (n_cols < 1 || n_cols > DEMC_COV_MAX_COLS) return fail(h, DEMC_EINVAL, "demc_covariance: n_cols must be in 1 .. 64");
+    const int D2 = h->c.D + 2;
+    if (!cols && n_cols != D2) return fail(h, DEMC_EINVAL, "demc_covariance: cols == NULL selects all D + 2 series: n_cols must equal D + 2 (at most 64)");
+    int sel[DEMC_COV_MAX_COLS];
+    for (int k = 0; k < n_cols; ++k) {
+        sel[k] = cols ? (int)cols[k] : k;
+        if (sel[k] < 0 || sel[k] >= D2) return fail(h, DEMC_EINVAL, "demc_covariance: a column is outside [0, D + 2)");
+        for (int j = 0; j < k; ++j)
+            if (sel[j] == sel[k]) return fail(h, DEMC_EINVAL, "demc_covariance: a column is repeated");
+    }
+    if (h->c.n_groups_total != h->c.n_groups)
+        return fail(h, DEMC_EINVAL, "sharded handle: gather demc_get_history from every rank and take the covariance on the host");
+    CovArgs a{h->hist, h->acc_hist, h->lp_hist, h->P, (long long)row0, (long long)row1, h->c.D, h->hist_ld};
+    std::string msg;
+    const int rc = cov_run(a, h->stream, sel, (int)n_cols, mean_out, cov_out, cor_out, msg);
     return rc == DEMC_OK ? DEMC_OK : fail(h, rc, msg);
     });
 }

@@ -3,7 +3,7 @@ C-ABI engine.  The per-iteration work -- step!/pstep! (main.jl:84-107) -- happen
 import numpy as np
 
 from . import _ffi
-from .chains import Chains, Summary, series_quantiles
+from .chains import COV_MAX_COLS, Chains, Summary, series_cov, series_quantiles
 from .families import PRIOR_NORMAL_REF, Priors, SimulatedLikelihood, SourceLikelihood
 from .structs import (DE, HIPBackend, LOGLIKE_MODES, MCMCThreads, SCHEDULES, DEModel, Particle, maximize)
 
@@ -193,6 +193,9 @@ def _run(model, de, n_iter, backend, progress, engine_factory, summary=None):
     theta0 = model.sample_prior()
     lay = _flat_layout(model, de, theta0)
     P = de.n_groups * de.Np
+    cov_cols = None
+    if summary is not None and len(summary) > 4 and summary[4] is not None:  # the series of cor=...: checked before the run
+        cov_cols = _cov_cols(get_names(model, lay["shapes"]), summary[4])[1]
     cfg = engine_config(de, lay, n_iter, backend)
     eng = (engine_factory or _ffi.HipEngine)(**cfg)
     try:
@@ -221,12 +224,14 @@ def _run(model, de, n_iter, backend, progress, engine_factory, summary=None):
             print()
         de.iter = n_iter + de.n_initial
         n_rows = n_iter + de.n_initial
-        if summary is not None and hasattr(eng, "summarize") and (len(summary) < 4 or summary[3] is None or hasattr(eng, "quantiles")):
-            # summarize(): the statistics (and the quantiles, when asked for) on the device, no export at all
+        if (summary is not None and hasattr(eng, "summarize") and (len(summary) < 4 or summary[3] is None or hasattr(eng, "quantiles"))
+                and (cov_cols is None or hasattr(eng, "covariance"))):
+            # summarize(): the statistics (and the quantiles and the covariance, when asked for) on the device, no export at all
             stats = eng.summarize(summary[0], summary[1], summary[2])[0]
-            if len(summary) < 4 or summary[3] is None:
-                return lay, stats, None
-            return lay, (stats, eng.quantiles(summary[0], summary[1], summary[3])), None
+            q = None if len(summary) < 4 or summary[3] is None else eng.quantiles(summary[0], summary[1], summary[3])
+            if cov_cols is not None:
+                return lay, (stats, q, eng.covariance(summary[0], summary[1], cov_cols)), None
+            return lay, (stats if q is None else (stats, q)), None
         if hasattr(eng, "export_chains"):  # device-side re-key + layout (demc_export_chains)
             full = eng.export_chains(0, n_rows)  # [n_rows][D+2][P] by particle id
         else:  # engines without it (the CPU oracle injected by tests): re-key on the host
@@ -247,21 +252,36 @@ def sample(model, de, *args, progress=False, engine_factory=None, **kwargs):
     return bundle_samples(model, de, lay, full, n_iter)
 
 
-def summarize(model, de, *args, max_lag=0, quantiles=None, progress=False, engine_factory=None, **kwargs):
-    """summarize(model, de, [HIPBackend(...)], n_iter, max_lag=0, quantiles=None): the run of sample() followed by the summary
+def _cov_cols(names, cor):
+    """cor=True: the parameters; a tuple of names: those series (acceptance and lp may be among them) -> (names, indices)"""
+    sel = [nm for nm in names if nm not in ("acceptance", "lp")] if cor is True else list(cor)
+    unknown = [nm for nm in sel if nm not in names]
+    if unknown or len(set(sel)) != len(sel) or not 1 <= len(sel) <= COV_MAX_COLS:
+        raise ValueError(f"cor= takes between 1 and {COV_MAX_COLS} distinct names of {names}" + (f": {unknown} are not among them" if unknown else ""))
+    return sel, [names.index(nm) for nm in sel]
+
+
+def summarize(model, de, *args, max_lag=0, quantiles=None, cor=False, progress=False, engine_factory=None, **kwargs):
+    """summarize(model, de, [HIPBackend(...)], n_iter, max_lag=0, quantiles=None, cor=False): the run of sample() followed by the summary
     statistics of the rows bundle_samples keeps (offset = burnin or 0, quirk q1 included) -- computed on the device by
     demc_summarize, so that the history is never exported.  Returns a Summary (chains.py); equal to
     sample(...).summarystats(max_lag) for the same seed.  quantiles: a tuple of probs (chains.DEFAULT_QUANTILES) -- the same run
     also selects those quantiles of the kept rows on the device (demc_quantiles) and the Summary carries them: Summary.quantile()
-    equals sample(...).quantile(probs).  An engine without summarize or quantiles (an injected one) exports as sample() does and
-    computes on the host."""
+    equals sample(...).quantile(probs).  cor: True (the parameters) or a tuple of names (acceptance and lp allowed, 64 at most) --
+    the same run also forms the covariance and correlation matrices of those series over the kept rows on the device
+    (demc_covariance): Summary.cor() / Summary.cov() equal sample(...).cor(names) / .cov(names) to rounding.  An engine without
+    summarize, quantiles or covariance (an injected one) exports as sample() does and computes on the host."""
     backend, n_iter = _parse(args)
     Ns = n_iter - de.burnin if de.discard_burnin else n_iter
     offset = de.burnin if de.discard_burnin else 0
     probs = None if quantiles is None else tuple(float(q) for q in quantiles)
-    lay, res, state = _run(model, de, n_iter, backend, progress, engine_factory, summary=(offset, offset + Ns, max_lag, probs))
+    want_cov = None if cor is False or cor is None else (True if cor is True else tuple(cor))
+    lay, res, state = _run(model, de, n_iter, backend, progress, engine_factory, summary=(offset, offset + Ns, max_lag, probs, want_cov))
     if state is None:
         names = get_names(model, lay["shapes"])
+        if want_cov is not None:
+            stats, q, (_, cov, cor_m) = res
+            return Summary(names, stats, quantiles=q, probs=probs, cov=cov, cor=cor_m, cov_names=_cov_cols(names, want_cov)[0])
         if probs is None:
             return Summary(names, res)
         return Summary(names, res[0], quantiles=res[1], probs=probs)
@@ -270,6 +290,9 @@ def summarize(model, de, *args, max_lag=0, quantiles=None, progress=False, engin
     if probs is not None:
         out.probs = probs
         out.quantiles = np.stack([series_quantiles(chains.value[:, j, :], probs) for j in range(len(chains.names))])
+    if want_cov is not None:
+        out.cov_names, cols = _cov_cols(chains.names, want_cov)
+        _, out.cov_matrix, out.cor_matrix = series_cov(chains.value, cols)
     return out
 
 

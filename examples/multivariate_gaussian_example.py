@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Examples/Multivariate_Guassian_Example.jl: 30 means + one sigma, nested Theta [mu, sigma], history partners
-(sample = resample, DE-MC_Z) with snooker updates, one group of three particles."""
+(sample = resample, DE-MC_Z) with snooker updates, one group of three particles.  Ends with the joint structure of the posterior:
+the correlation matrix of the first means, σ and lp formed on the device (demc_covariance through summarize(..., cor=names)) beside
+the closed-form posterior's -- given σ the means are independent with variance 1 / (n_d / σ² + 1), so its correlation matrix is I."""
 import os
 import sys
 import warnings
@@ -32,3 +34,20 @@ d = chains.describe()
 means = np.array([d[f"μ[{i + 1}]"]["mean"] for i in range(n_mu)])
 print("cor(true means, posterior means) =", np.corrcoef(mus, means)[0, 1])
 print("posterior sd of the means ~ 0.1:", np.round([d[f"μ[{i + 1}]"]["std"] for i in range(5)], 3), "…  σ:", d["σ"])
+
+# the same run summarised on the device: the history is not exported, only the 6 x 6 matrices reach the host
+names = ("μ[1]", "μ[2]", "μ[3]", "μ[4]", "σ", "lp")
+with warnings.catch_warnings():
+    warnings.simplefilter("ignore")
+    de = D.DE(sample_prior=sample_prior, bounds=((-np.inf, np.inf), (0.0, np.inf)), sample=D.resample, burnin=5000,
+              n_initial=(n_mu + 1) * 4, Np=3, n_groups=1, θsnooker=0.1)
+summary = D.summarize(model, de, D.MCMCThreads(), 20000, cor=names)
+_, cor = summary.cor()
+_, cov = summary.cov()
+sigma = summary["σ"]["mean"]
+print("posterior correlation on the device (rows: " + ", ".join(names) + ") | closed form given σ (means only)")
+for i, nm in enumerate(names):
+    closed = "  ".join(f"{float(i == j):6.3f}" for j in range(4)) if i < 4 else ""
+    print("  ".join(f"{v:6.3f}" for v in cor[i]) + "   |   " + closed)
+print("posterior sd of μ[1..4] on the device:", np.round(np.sqrt(np.diag(cov)[:4]), 4),
+      " closed form sqrt(1 / (n_d / σ² + 1)) =", round(float(np.sqrt(1.0 / (n_d / sigma ** 2 + 1.0))), 4))

@@ -278,6 +278,8 @@ end
 include("DEMCHIPSummary.jl")
 # ... and its quantile table (include/demc_quantile.h): `quantiles`, likewise
 include("DEMCHIPQuantile.jl")
+# ... and cov(chains) / cor(chains) (include/demc_cov.h): `covariance`, likewise
+include("DEMCHIPCov.jl")
 
 "final state of the particle objects behind handle `h` (bundle_samples reads accept/lp from them; Θ for completeness)"
 function pull_state!(h, particles, Pl, D, shapes, lens, offs)
