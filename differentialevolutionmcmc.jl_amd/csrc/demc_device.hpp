@@ -102,13 +102,18 @@ __device__ inline double softplus(double x) { return x > 0 ? x + log1p(exp(-x)) 
 // softplus with a short log1p: for t = exp(-|x|) in (0, 1], log1p(t) = 2 atanh(z), z = t / (2 + t) in (0, 1/3], whose odd
 // series in z converges as 9^-n (17 terms reach 1e-17 relative); the quotient by reciprocal + two Newton steps (the
 // denominator lies in [2, 3]: no scaling needed).  About a third of the instructions of the library's log1p on top of
-// exp; agrees with softplus() to ~2e-16 relative (tests/test_gpu_parity.py compares the hierarchical families with the
-// oracle's libm forms at 1e-9).  The hierarchical likelihoods spend most of their instructions here.
+// exp; within 4.54e-16 relative of the exact softplus (measured on the device against 80-bit arithmetic, largest at x = -7.609;
+// bar 6e-16, tests/test_gpu_device_math.py; tests/test_gpu_parity.py compares the hierarchical families with the oracle's libm
+// forms at 1e-9).  The hierarchical likelihoods spend most of their instructions here.  Clamps: the argument of exp stops at -700,
+// so softplus_fast(x) = 9.86e-305 for every x <= -700 (-Inf included), +Inf gives +Inf, and a NaN is swallowed by the two fmax --
+// softplus_fast(NaN) = softplus_fast(-700) = 9.8596765437597708e-305, not NaN: callers that must see a NaN test their own inputs.
 // exp(a) for a <= 0 without a quarter-rate instruction: the library's exp spends v_rndne_f64, v_cvt_i32_f64 and v_ldexp_f64 (16
 // cycles a wave each, against 4 for an FP64 add) on range reduction and scaling.  Here: n = round(a log2 e) by adding and
 // subtracting 1.5 * 2^52 (n sits in the low word of the sum), r = a - n ln 2 in two FMAs (hi / lo split), e^r by its degree-13
 // Taylor polynomial (|r| <= 0.347: truncation 4e-18), and 2^n built in the exponent field by integer adds.  a is clamped at
-// -700 (e^-700 ~ 1e-304: still a normal number; below it the callers' results do not change).  Relative error < 2.5e-16.
+// -700 (e^-700 ~ 1e-304: still a normal number; below it the callers' results do not change).  Relative error < 2.5e-16 (measured
+// on the device: 1.35e-16 over [-700, 0], every rounding tie of n included).  The clamp is v_max, which reads a NaN as a number:
+// exp_nonpos(NaN) = exp_nonpos(-700) = 9.8596765437597708e-305.
 __device__ __forceinline__ double exp_nonpos(double a) {
     a = fmax(a, -700.0);
     const double kMagic = 6755399441055744.0;  // 1.5 * 2^52
@@ -149,7 +154,9 @@ __device__ inline double softplus_fast(double x) {
 //                      (|r| <= ln2/128: truncation 3e-17), times E[k & 63] = 2^((k & 63)/64), times 2^(k >> 6) built in the exponent field
 //   log1p(t):          j = round(128 t), f = (t - j/128) / c_j with c_j = 1 + j/128 (the difference is exact, 1/c_j from the table),
 //                      log1p(t) = log c_j + f Q6(f), |f| <= 2^-8 (truncation f^7/8: 2e-18 relative to f)
-// Relative error < 6e-16 (the generator checks a dense grid against 50-digit arithmetic); not bit-identical to softplus_fast.
+// Relative error < 6e-16 (the generator checks a dense grid against 50-digit arithmetic; measured on the device: 4.44e-16, every tie of
+// k and of j included); not bit-identical to softplus_fast.  As there, x <= -700 returns softplus_tab(-700) and so does a NaN (the fmax
+// in front of the floor reads it as -700): softplus_tab(NaN) = 9.8596765437597708e-305.
 __device__ __forceinline__ void load_softplus_table(double* s_tab, int tid, int n_threads) {
     for (int i = tid; i < kSpDoubles; i += n_threads) s_tab[i] = kSpTable[i];
 }
@@ -239,7 +246,8 @@ __device__ __forceinline__ void phiS_Phi_table(const double* tab, double zs, dou
 // 2.2e-16 relative to max(1, |g|)): nine FMAs and ten coefficients per value -- no erfcx, no exp, no log.  Row and u as for the
 // Phi table (1.5 * 2^52 added and subtracted).  Below -8.5 the value is 0 to double precision (clamp); beyond 38.5 --
 // survival probabilities under 1e-324 -- Mills' ratio: log Phi(-z) = -z^2/2 - log z - log sqrt(2 pi) + log(1 - 1/z^2 + 3/z^4
-// - 15/z^6) (relative error < 1e-11 there), out of line.  tab points at a copy of kLogPhiTable.
+// - 15/z^6) (relative error < 1e-11 there; measured on the device: 2.9e-14, largest at the seam), out of line; -Inf once z^2
+// overflows, never NaN.  tab points at a copy of kLogPhiTable.
 __device__ __attribute__((noinline)) double log_Phi_neg_far(double z) {
     const double i2 = 1.0 / (z * z);
     return -0.5 * z * z - log(z) - 0.5 * kLog2Pi + log1p(i2 * (-1.0 + i2 * (3.0 - 15.0 * i2)));
@@ -277,7 +285,9 @@ __device__ __forceinline__ double lba_factor(const double* tab, bool win, double
     if (win) return inv_A * fma(kPhiS, dq, v * (P2 - P1));
     return t_inv_SA * fma(-(kPhiS * kPhiS), dq, fma(m2, P2, -(m1 * P1)));
 }
-// 1/x for x > 0 to the last bit or two: hardware reciprocal + two Newton steps (the IEEE division is ~25 instructions)
+// 1/x for x > 0 to the last bit or two: hardware reciprocal + two Newton steps (the IEEE division is ~25 instructions).  Measured on
+// the device: within 1 ulp on [1e-300, 1e300], exact at the powers of two.  A denormal x whose reciprocal overflows (5e-324, 1e-310)
+// gives NaN (rcp = Inf, 0 * Inf in the Newton steps): lba_trial guards it.
 __device__ __forceinline__ double recip_pos(double x) {
     double r = __builtin_amdgcn_rcp(x);
     r = fma(fma(-x, r, 1.0), r, r);

@@ -450,6 +450,14 @@ __device__ inline U4 bcast_u4(const U4& v, int lpp, int sub_base) {
     return r;
 }
 
+// log(1 + z^2) of the Cauchy densities.  z * z leaves the double range at |z| = 1.34e154 and log1p(Inf) made the log-density -Inf,
+// where it is about -710 and finite up to the largest double (Distributions.jl's log1psq); beyond 2^511 it is 2 log(1 + |z|), which
+// differs from log(1 + z^2) by 2/|z| < 2^-510.  One log1p either way, and the same bits as log1p(z * z) below the switch.
+__device__ inline double log1p_sq(double z) {
+    const bool big = fabs(z) > 0x1p511;
+    const double l = log1p(big ? fabs(z) : z * z);
+    return big ? 2.0 * l : l;
+}
 // x-dependent part of one scalar's log-prior; DimTab.b holds 1/scale for Normal / half-Cauchy
 __device__ inline double prior_term(const DimTab& t, double x, double inv_sref, double log_sref) {
     switch (t.kind) {
@@ -464,7 +472,7 @@ __device__ inline double prior_term(const DimTab& t, double x, double inv_sref, 
         case PR_HALFCAUCHY: {
             if (x < 0.0) return -INFINITY;
             const double z = (x - t.a) * t.b;
-            return t.c - log1p(z * z);
+            return t.c - log1p_sq(z);
         }
         case PR_UNIFORM:
             return (x >= t.a && x <= t.b) ? t.c : -INFINITY;
@@ -485,7 +493,7 @@ __device__ inline double prior_term(const DimTab& t, double x, double inv_sref, 
         }
         case PR_CAUCHY: {  // b = 1/scale
             const double z = (x - t.a) * t.b;
-            return t.c - log1p(z * z);
+            return t.c - log1p_sq(z);
         }
         default:
             return 0.0;

@@ -367,6 +367,13 @@ static inline double Phi(double x) { return 0.5 * erfc(-x * 0.707106781186547524
 static inline double phi(double x) { return exp(-0.5 * x * x) * 0.39894228040143267794; }
 static inline double softplus(double x) { return x > 0 ? x + log1p(exp(-x)) : log1p(exp(x)); }
 
+/* log(1 + z^2) that stays finite where z * z overflows (Distributions.jl's log1psq); the device's log1p_sq, same switch */
+static inline double log1p_sq(double z) {
+    const int big = fabs(z) > 0x1p511;
+    const double l = log1p(big ? fabs(z) : z * z);
+    return big ? 2.0 * l : l;
+}
+
 static double prior_scalar(int kind, double a, double b, double sref, double x) {
     switch (kind) {
         case ORC_PRIOR_FLAT:
@@ -380,7 +387,7 @@ static double prior_scalar(int kind, double a, double b, double sref, double x) 
             if (x < 0.0) return -INFINITY;
             const double z = (x - a) / b;
             const double tp = 1.0 - (atan((0.0 - a) / b) / PI_D + 0.5);
-            return -LOG_PI - log(b) - log1p(z * z) - log(tp);
+            return -LOG_PI - log(b) - log1p_sq(z) - log(tp);
         }
         case ORC_PRIOR_UNIFORM:
             return (x >= a && x <= b) ? -log(b - a) : -INFINITY;
@@ -397,7 +404,7 @@ static double prior_scalar(int kind, double a, double b, double sref, double x) 
         }
         case ORC_PRIOR_CAUCHY: {
             const double z = (x - a) / b;
-            return -LOG_PI - log(b) - log1p(z * z);
+            return -LOG_PI - log(b) - log1p_sq(z);
         }
         case ORC_PRIOR_BETA: {
             if (x < 0.0 || x > 1.0) return -INFINITY;
