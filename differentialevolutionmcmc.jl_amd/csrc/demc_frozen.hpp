@@ -33,8 +33,6 @@
 
 namespace demc {
 
-constexpr int kFrozenMax = 8;  // scalars a block may move for this kernel
-
 // softplus_fast (demc_device.hpp) with its 35 polynomial and range-reduction constants handed in as wave-uniform values: the
 // same operations in the same order -- the same bits -- but the compiler keeps a uniform value in an SGPR pair and feeds it to
 // v_fma_f64 as the addend, where a literal costs a v_mov_b64 into the accumulator in front of every v_fmac (31 of ~95 vector

@@ -8,6 +8,10 @@
 // loop needs no device->host traffic: the only host-side draw is the alpha coin (pure function of seed, iter).
 //
 // There is NO CPU fallback in this file: every compute entry point launches HIP kernels or fails.
+//
+// What is launched -- kernel instance, grid, workgroup size, LDS bytes, chunk counts, fuse flags -- is decided in demc_geometry.hpp,
+// host-only code that knows neither HIP nor the handle; what a model's data become before they are uploaded, in demc_prep.hpp.
+// This file gathers their inputs from the handle, asks the device what only it knows, and does what the plans say.
 #include "../../include/demc.h"
 #include "../../include/demc_summary.h"  // demc_summarize
 #include "../../include/demc_quantile.h"  // demc_quantiles
@@ -48,13 +52,13 @@
 #include "demc_devmem.hpp"  // owners of the device memory, pinned memory, events and modules the handle holds
 #include "demc_prep.hpp"  // host-only: a model's data and constants, the prior table and its run-length forms, every refusal of those
 #include "demc_instances.hpp"  // one table per templated kernel, built from the lists above: every choice of an instance goes through them
+#include "demc_geometry.hpp"  // host-only: every launch-geometry decision, as plans the launches below carry out
 
 using namespace demc;
 
 #ifndef DEMC_ARCH_STR
 #define DEMC_ARCH_STR "gfx950"  // the Makefile passes its ARCH, so that the JIT-compiled plug-in matches the library
 #endif
-constexpr size_t kMaxDynLds = 150 * 1024;  // of the 160 KB per CU; the rest covers the kernels' static __shared__
 static_assert(kPrepOdeMaxT == kOdeMaxT && kPrepOdeMaxSubsteps == kOdeMaxSubsteps && kPrepSimMaxN == kSimMaxN && kPrepSimChoiceMaxN == kSimChoiceMaxN,
               "demc_prep.hpp refuses by the kernels' caps");
 
@@ -66,38 +70,17 @@ struct Timed {
     bool started = false;  // a kernel of the bracket carries the events (LAUNCH_T)
 };
 
-// The kernel forms that can carry an update.  FORM_PHASE -- a K1 [-> K2 -> K3] chain per sweep and colour phase, k_longrow and
-// k_frozen_sweep beneath it -- serves every configuration and is planned per launch (launch_phase).  The others run whole updates
-// in one launch: planned once per model into a FormPlan (size_k1_lds), chosen per step (choose_form), launched by launch_form.
-enum Form {
-    FORM_PHASE,
-    FORM_RESIDENT,        // k_propose<..., RES>: the group in LDS, both colour phases of several iterations
-    FORM_STREAM,          // k_propose<..., RES, LEAN, STREAM>: ... with the MvNormal observation stream inside
-    FORM_LEAN_SUFFSTAT,   // k_res_mvn<WG, false, DT>: the default sampler on MvNormal-full (demc_resmvn.hpp)
-    FORM_LEAN_STREAMING,  // k_res_mvn<WG, true, DT>
-    FORM_LEAN_DIRECT,     // k_res_mvn<WG, true, DT, direct>
-    FORM_LEAN_OBS,        // k_res_obs: the default sampler on the per-observation families (demc_resobs.hpp)
-    FORM_LEAN_Z,          // k_res_mvn<WG, false, DT, HIST>: DE-MC_Z, one iteration per launch
-    N_FORMS
-};
-// a group's observations in chunks, a workgroup each, which spin on each other's progress: the whole grid must be resident at once
-constexpr bool spin_waiting(Form f) { return f == FORM_STREAM || f == FORM_LEAN_STREAMING || f == FORM_LEAN_DIRECT; }
-
-struct FormPlan {
-    bool ok = false;           // the form serves this model and configuration
+// The whole-update forms (enum Form, demc_geometry.hpp): planned once per model into a FormPlan -- the geometry plus the
+// instance(s) it names (size_k1_lds) --, chosen per step (choose_form), launched by launch_form.  FORM_PHASE, which serves every
+// configuration, is planned per launch (launch_phase).
+struct FormPlan : FormGeo {
     // the instance(s), resolved when the model is planned (a missing one fails there, not at step 1): per LEAN level for the two
     // k_propose forms (a trace or a replay lowers it to 0 at run time: lean_level), per HIST - 1 for FORM_LEAN_Z, else [0]
     const K1Inst* k1[3] = {};
-    int wg = 0;                // workgroup size
-    size_t lds = 0;            // dynamic LDS bytes
-    int lpp = 0, scr_doubles = 0;  // k_propose forms: lanes per particle, doubles of the theta' scratch
 };
 
-// Geometry of the observation stream inside a resident kernel (plan_stream), shared by the spin-waiting forms: a handle runs in one
-// likelihood mode, so at most one of FORM_STREAM / FORM_LEAN_STREAMING (STREAMING) and FORM_LEAN_DIRECT (DIRECT) reads it.
-struct StreamGeo {
-    bool ok = false;
-    int C = 0, nact_max = 0, rows = 0, x_lds = 0, chunk_tiles = 0;  // chunks per group, moving particles, scratch rows, X chunk in LDS, tiles per chunk
+// The observation stream inside a resident kernel: its geometry (StreamDims) and the buffers that go with it.
+struct StreamGeo : StreamDims {
     DevBuf<unsigned long long> gran;  // hand-over granules (device), [2][n_groups][C][nact_max][2]
     PinnedBuf<unsigned> err;          // time-out flag (host-mapped, zero-copy)
 };
@@ -147,6 +130,7 @@ struct demc_handle {
     std::vector<DimTab> h_tab;  // host copy: bounds and priors arrive in separate calls
     DevBuf<DimSeg> dimseg;      // run-length form of the table (kMaxDimSeg entries)
     int n_seg = 0;              // 0: more segments than kMaxDimSeg, the kernels read dimtab
+    bool normal_ref = false;    // the table has a Normal(a, theta[ref]) entry
     int seg_start[kMaxDimSeg] = {0};
     unsigned seg_plain = 0;     // segments with a flat / Normal / Normal(a, theta[ref]) prior
     std::vector<MaskRuns> mask_runs;  // per block sweep: the mask run-length encoded (n = 0: too many runs)
@@ -163,12 +147,9 @@ struct demc_handle {
     std::vector<double> trunc_sd;
     int partial_cap = 64;
     int lpp = 1;
-    int tile_in_lds = 0;
-    size_t k1_lds = 0, k1_tile_bytes = 0, k1_scr_bytes = 0;
-    bool hier_scr = false;  // hierarchical family whose theta' scratch fits in LDS
+    K1Lds k1;  // K1 LDS carve-up for the model and the population (size_k1_lds)
     FormPlan form[N_FORMS];  // the whole-update forms (size_k1_lds plans them; [FORM_PHASE] is not used)
     StreamGeo st;
-    bool tf_cheap_obs = false;  // set_tail_flags' "the likelihood is cheap enough for K1" of the last call (launch_phase reads it)
     // k_frozen_sweep: launch order of the groups per (iteration, block sweep) of the current demc_step call -- groups whose
     // mutation coin fires (main.jl:199-207) first: their workgroups move the whole row and take twice as long, and a slow
     // workgroup that starts last ends the launch.  A hint only: any order gives the same results.
@@ -188,7 +169,6 @@ struct demc_handle {
     bool bracket_open = false;  // timing: between tick(begin) and tick(end) of a bracket whose kernels carry the events
     size_t lr_two_lds = 0;     // long-row kernel: the dynamic LDS size lr_two_fit was asked for
     bool lr_two_fit = false;   // ... two 256-thread workgroups with that much LDS fit on a CU
-    int ainv_lds = 1;
     // update of a subset of the groups (demc_update_groups_async): two device lists used alternately, and the one in force
     // Each call takes the next of kGlistRing slots: a pinned host copy of the list, a device copy, and an event that marks
     // the host copy as consumed.  The device copy is refilled by a copy ON THE HANDLE'S STREAM, i.e. behind every kernel that
@@ -218,7 +198,6 @@ struct demc_handle {
     struct demc_multi* multi = nullptr;
     bool multi_sealed = false;  // the set is built: demc_set_stream is refused from here on
     // which kernel instances the last update launched (demc_last_kernels: lets a test name the instance it compared)
-    enum K2Kind { K2_NONE, K2_CROSS_MFMA, K2_DIRECT_MVN, K2_OBS, K2_LBA_WAVE, K2_HIER, K2_USER, K2_USER_ROW, K2_SIM, K2_ODE };
     struct LastPlan {
         const K1Inst* k1 = nullptr;  // the entry that was launched (its key names it)
         K2Kind k2 = K2_NONE;         // the likelihood kernel behind it (none: fused into K1) ...
@@ -374,7 +353,15 @@ int wgs_per_cu(demc_handle* h, const void* fn, int* cached) {
     return DEMC_OK;
 }
 
-bool is_mvn(int fam);
+// The plain values the geometry rules read (demc_geometry.hpp), gathered from the handle: integers and pointers, built per call.
+Setup setup_of(const demc_handle* h) {
+    Setup s;
+    s.c = &h->c; s.m = &h->m; s.family = h->m.family; s.user_row = h->m.user_row;
+    s.n_seg = h->n_seg; s.seg_start = h->seg_start; s.normal_ref = h->normal_ref; s.has_hist = h->hist.get() != nullptr;
+    s.partial_cap = h->partial_cap; s.geo_groups = h->geo_groups; s.n_cus = h->n_cus; s.lpp = h->lpp; s.k1 = &h->k1;
+    s.replay = h->rp.active; s.subset = h->cur_glist != nullptr;
+    return s;
+}
 
 KParams base_params(demc_handle* h) {
     KParams k;
@@ -389,19 +376,19 @@ KParams base_params(demc_handle* h) {
     k.fitness_kind = c.fitness_kind;
     k.theta = h->theta; k.weight = h->weight; k.id = h->id; k.prop = h->prop; k.prop_prior = h->prop_prior;
     k.prop_adj = h->prop_adj; k.prop_oob = h->prop_oob; k.tr_idx = h->tr_idx; k.tr_w = h->tr_w; k.tr_acc = h->tr_acc;
-    k.dimtab = h->dimtab; k.dimseg = h->dimseg; k.n_seg = h->n_seg; k.ainv_lds = h->ainv_lds; k.mask = nullptr;
+    k.dimtab = h->dimtab; k.dimseg = h->dimseg; k.n_seg = h->n_seg; k.ainv_lds = h->k1.ainv_lds; k.mask = nullptr;
     std::memcpy(k.seg_start, h->seg_start, sizeof k.seg_start);
     k.seg_plain = h->seg_plain;
     std::memset(k.mrun_start, 0, sizeof k.mrun_start);
     k.n_mrun = 1; k.mrun_in = 1u;  // no block mask: one run, inside
     k.hist = h->hist; k.acc_hist = h->acc_hist; k.lp_hist = h->lp_hist; k.id_hist = h->id_hist; k.hist_ld = h->hist_ld;
-    k.P = h->P; k.store_row = -1; k.tile_in_lds = h->tile_in_lds;
+    k.P = h->P; k.store_row = -1; k.tile_in_lds = h->k1.tile_in_lds;
     k.family = h->m.family; k.N = h->m.N; k.d = h->m.d; k.n_acc = h->m.n_acc; k.n_partials = 1;
     k.partial = h->partial; k.aux = h->aux; k.data = h->m.data; k.data2 = h->m.data ? h->m.data + h->m.data2_off : nullptr;
     k.c0 = h->m.c0; k.c1 = h->m.c1; k.c2 = h->m.c2;
     k.direct = (is_mvn(h->m.family) && c.loglike_mode == DEMC_LOGLIKE_DIRECT) ? 1 : 0;
     k.n_split = 1; k.fuse_prep = 0; k.prep_mfma = 0; k.fuse_obs = 0; k.fuse_accept = 0; k.plan = 0;
-    k.scr_doubles = (int)(h->k1_scr_bytes / sizeof(double)); k.write_prop = 1; k.trace = c.trace;
+    k.scr_doubles = (int)(h->k1.scr_bytes / sizeof(double)); k.write_prop = 1; k.trace = c.trace;
     k.Ainv = h->m.Ainv; k.sx = nullptr; k.xbar = h->m.xbar; k.Ypad = h->m.Ypad; k.dpad = h->m.dpad;
     k.rp_group = h->rp.group; k.rp_part = h->rp.part; k.rp_partner = h->rp.partner; k.rp_noise = h->rp.noise;
     k.rp_znoise = h->rp.znoise; k.rp_recomb = h->rp.recomb; k.rp_mig_groups = h->rp.mig_groups;
@@ -483,20 +470,6 @@ extern "C" __global__ __launch_bounds__(256) void k_user_loglike(UserKParams p) 
 }
 )SRC";
 
-// Number of observation chunks for a K2 kernel that is one long uniform loop per workgroup: such a launch takes
-// ceil(workgroups / resident workgroups) rounds of equal length, so among the admissible counts (1..cap) the one that fills
-// the last round best wins; ties go to the larger count while the launch stays within four rounds.
-int chunks_filling_rounds(long long blocks, long long cap, double resident_wgs) {
-    long long best = 1;
-    double best_fill = 0.0;
-    for (long long nc = 1; nc <= cap; ++nc) {
-        const double wgs = (double)blocks * (double)nc;
-        const double fill = wgs / (std::ceil(wgs / resident_wgs) * resident_wgs);
-        if (fill > best_fill + 1e-9 || (fill > best_fill - 1e-9 && wgs <= 4.0 * resident_wgs)) { best = nc; best_fill = fill; }
-    }
-    return (int)best;
-}
-
 // demc_timing_clock: with timing enabled the compute-bound likelihood kernels (k_direct_mvn, k_lba_wave) leave per workgroup
 // {s_memtime, s_memrealtime, CU} as they end; the buffer is zeroed on the stream ahead of the launch (a workgroup whose first wave
 // has no proposal reports nothing) and sized for the launch's grid.  Null when timing is off.
@@ -530,7 +503,7 @@ int launch_sim_loglike(demc_handle* h, KParams& k, long long n_prop) {
     s.prop = k.prop; s.partial = k.partial; s.obs = h->m.data; s.hyper = h->m.user_hyper ? h->m.user_hyper + 1 : nullptr;
     s.logtab = h->m.sim_logtab; s.glist = k.glist; s.k_max = h->m.sim_kmax;
     const size_t lds = h->m.sim_est == EST_KDE_CHOICE ? sim_choice_lds(h->m.sim_n) : (size_t)h->m.sim_n * sizeof(double);
-    h->last.k2 = demc_handle::K2_SIM; h->last.k2_key = InstKey{{h->m.sim_kind, h->m.sim_est}};
+    h->last.k2 = K2_SIM; h->last.k2_key = InstKey{{h->m.sim_kind, h->m.sim_est}};
     if (h->m.sim_kind == SIM_USER) {
         size_t sz = sizeof s;
         void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &s, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
@@ -559,7 +532,7 @@ int launch_ode_loglike(demc_handle* h, KParams& k) {
     o.prop = k.prop; o.partial = k.partial; o.obs = h->m.data; o.glist = k.glist;
     const Inst<OdeFn>* e = nullptr;
     PICK(e, "k_ode_loglike", kOde, ODE_LV);
-    h->last.k2 = demc_handle::K2_ODE; h->last.k2_key = e->key;
+    h->last.k2 = K2_ODE; h->last.k2_key = e->key;
     const size_t lds = (size_t)h->m.N * 2 * sizeof(double);
     tick(h, 2, true);
     LAUNCH_T(h, e->fn, dim3((unsigned)k.n_groups, (unsigned)((k.n_act + 255) / 256)), dim3(256), lds, o);
@@ -567,187 +540,98 @@ int launch_ode_loglike(demc_handle* h, KParams& k) {
     return DEMC_OK;
 }
 
-// K2 dispatch for the active set described by k.  Sets k.n_partials.
+// K2 dispatch for the active set described by k: the plan (demc_geometry.hpp: which kernel, its grid and chunk counts), then the
+// launch.  Sets k.n_partials.
 int launch_loglike(demc_handle* h, KParams& k) {
     const long long n_prop = (long long)k.n_groups * k.n_act;
     if (n_prop == 0) return DEMC_OK;
-    switch (h->m.family) {
-        case FAM_MVN_FULL:
-        case FAM_MVN_ISO: {
-            const bool suff = h->c.loglike_mode == DEMC_LOGLIKE_SUFFSTAT;  // then K1 already formed S
-            k.n_partials = 1;
-            if (k.direct) {
-                // proposal blocks of 256 x observation chunks: enough workgroups for 8 waves per SIMD, chunks no shorter
-                // than 64 observations, at most the partial-sum workspace
-                const long long blocks = (n_prop + 255) / 256;
-                long long cap = h->m.N / 64;
-                if (cap > h->partial_cap) cap = h->partial_cap;
-                if (cap < 1) cap = 1;
-                // The kernel is one long uniform loop per workgroup: the launch takes ceil(workgroups / resident workgroups)
-                // rounds of equal length, so the chunk count is chosen to fill the last round (cfg3: 128 blocks x 48 chunks =
-                // 4 full rounds of 1536 resident workgroups; 32 chunks would leave a third of the chip idle in round 3).
-                const Inst<ChunkFn>* e = nullptr;
-                PICK(e, "k_direct_mvn", kDirect, h->m.dp_direct);
-                if (int rc = wgs_per_cu(h, (const void*)e->fn, &h->m.direct_wgs_per_cu)) return rc;
-                const int n_chunks = chunks_filling_rounds(blocks, cap, (double)h->m.direct_wgs_per_cu * h->n_cus);
-                h->last.k2 = demc_handle::K2_DIRECT_MVN; h->last.k2_key = e->key;
-                // timing on: every workgroup also leaves its shader-clock / reference-clock ticks (demc_timing_clock)
-                unsigned long long* clk = nullptr;
-                if (int rc = clock_buffer(h, (size_t)blocks * (size_t)n_chunks, &clk)) return rc;
-                tick(h, 2, true);
-                LAUNCH_T(h, e->fn, dim3((unsigned)blocks, (unsigned)n_chunks), dim3(256), 0, k, n_chunks, clk);
-                tick(h, 2, false);
-                k.n_partials = n_chunks;
-            } else if (!suff) {
-                const Inst<CrossFn>* e = nullptr;  // (k-steps per pass: the next instance up, demc_set_model keeps them a power of two <= 16)
-                PICK(e, "k_cross_mfma", kCross, h->m.ks_t <= 1 ? 1 : h->m.ks_t <= 2 ? 2 : h->m.ks_t <= 4 ? 4 : h->m.ks_t <= 8 ? 8 : 16, 4);
-                h->last.k2 = demc_handle::K2_CROSS_MFMA; h->last.k2_key = e->key;
-                tick(h, 2, true);
-                // particle tiles of 256 (4 waves x MT=4 x 16) x observation chunks; chunks in multiples of 8 so that
-                // blockIdx % 8 (the XCD a block lands on) selects the chunk it streams
-                const long long n_ptiles = (n_prop + 255) / 256;
-                int n_chunks = 8;
-                while (n_ptiles * n_chunks < 1024 && n_chunks * 2 <= 32 && h->m.n_tiles / (n_chunks * 2) >= 16) n_chunks *= 2;
-                if (h->m.n_tiles < n_chunks) n_chunks = (int)(h->m.n_tiles > 0 ? h->m.n_tiles : 1);
-                const int n_kpass = h->m.n_kpass;
-                if (n_chunks * n_kpass > h->partial_cap) n_chunks = h->partial_cap / n_kpass;
-                if (n_chunks < 1) return fail(h, DEMC_EINVAL, "data dimension too large for the partial-sum workspace");
-                const int grid2 = (int)(n_ptiles * n_chunks);
-                for (int kp = 0; kp < n_kpass; ++kp) {
-                    const int k0 = kp * 4 * h->m.ks_t, part0 = kp * n_chunks;
-                    LAUNCH_T(h, e->fn, dim3(grid2), dim3(256), 0, k, h->m.Ypad.get(), h->m.dpad, k0, h->m.Xf.get(), h->m.n_tiles, n_chunks, part0);
-                }
-                tick(h, 2, false);
-                k.n_partials = n_chunks * n_kpass;
-            }
-        } break;
-        case FAM_GAUSSIAN:
-        case FAM_BINOMIAL:
-        case FAM_LBA:
-        case FAM_LNR:
-        case FAM_RASTRIGIN: {
-            long long cap = h->m.N / 32;
-            if (cap > h->partial_cap) cap = h->partial_cap;
-            if (cap < 1 || h->m.family == FAM_RASTRIGIN) cap = 1;
+    k.n_partials = 1;
+    if (h->m.family == FAM_SIM) return launch_sim_loglike(h, k, n_prop);
+    if (h->m.family == FAM_ODE_LV) return launch_ode_loglike(h, k);
+    const Setup s = setup_of(h);
+    // the occupancy the kernel's chunk rule reads: asked once, kept
+    Occupancy occ;
+    const Inst<ChunkFn>* ec = nullptr;  // k_direct_mvn / k_lba_wave
+    switch (k2_kind(s)) {
+        case K2_DIRECT_MVN:
+            PICK(ec, "k_direct_mvn", kDirect, h->m.dp_direct);
+            if (int rc = wgs_per_cu(h, (const void*)ec->fn, &h->m.direct_wgs_per_cu)) return rc;
+            occ.direct = h->m.direct_wgs_per_cu;
+            break;
+        case K2_OBS:
             if (int rc = wgs_per_cu(h, (const void*)k_obs_loglike, &h->obs_wgs_per_cu)) return rc;
-            int n_chunks = chunks_filling_rounds((n_prop + 255) / 256, cap, (double)h->obs_wgs_per_cu * h->n_cus);
-            if (h->m.family == FAM_LBA) {
-                // a wave per proposal, lanes across the (sorted) trials: k_lba_wave.  Chunks of whole batches (512 trials), at least two a chunk.
-                const Inst<ChunkFn>*e = nullptr, *e3 = nullptr;
-                PICK(e, "k_lba_wave", kLbaWave, h->m.n_acc == 3 ? 3 : h->m.n_acc == 2 ? 2 : 0);
-                PICK(e3, "k_lba_wave", kLbaWave, 3);  // (the occupancy that sizes the chunks is the three-accumulator instance's, whichever runs)
-                if (int rc = wgs_per_cu(h, (const void*)e3->fn, &h->lba_wave_wgs_per_cu)) return rc;
-                long long capw = h->m.N / 1024;
-                if (capw > h->partial_cap) capw = h->partial_cap;
-                if (capw < 1) capw = 1;
-                int nc = chunks_filling_rounds((n_prop + 3) / 4, capw, (double)h->lba_wave_wgs_per_cu * h->n_cus);
-                h->last.k2 = demc_handle::K2_LBA_WAVE;
-                unsigned long long* clk = nullptr;  // timing on: the clock the vector pipe held (demc_timing_clock)
-                if (int rc = clock_buffer(h, (size_t)((n_prop + 3) / 4) * (size_t)nc, &clk)) return rc;
-                tick(h, 2, true);
-                LAUNCH_T(h, e->fn, dim3((unsigned)((n_prop + 3) / 4), (unsigned)nc), dim3(256), 0, k, nc, clk);
-                tick(h, 2, false);
-                k.n_partials = nc;
-                break;
-            }
-            h->last.k2 = demc_handle::K2_OBS;
+            occ.obs = h->obs_wgs_per_cu;
+            break;
+        case K2_LBA_WAVE:
+            PICK(ec, "k_lba_wave", kLbaWave, 3);
+            if (int rc = wgs_per_cu(h, (const void*)ec->fn, &h->lba_wave_wgs_per_cu)) return rc;
+            occ.lba_wave = h->lba_wave_wgs_per_cu;
+            break;
+        default: break;
+    }
+    const LoglikePlan pl = plan_loglike(s, n_prop, occ);
+    if (pl.refused) return fail(h, pl.refused, pl.why);
+    h->last.k2 = pl.kind;
+    const dim3 grid(pl.grid_x, pl.grid_y);
+    switch (pl.kind) {
+        case K2_DIRECT_MVN:
+        case K2_LBA_WAVE: {
+            if (pl.kind == K2_LBA_WAVE) PICK(ec, "k_lba_wave", kLbaWave, pl.key[0]);
+            h->last.k2_key = ec->key;
+            // timing on: every workgroup also leaves its shader-clock / reference-clock ticks (demc_timing_clock)
+            unsigned long long* clk = nullptr;
+            if (int rc = clock_buffer(h, (size_t)pl.grid_x * (size_t)pl.n_chunks, &clk)) return rc;
             tick(h, 2, true);
-            LAUNCH_T(h, k_obs_loglike, dim3((unsigned)((n_prop + 255) / 256), (unsigned)n_chunks), dim3(256), 0,
-                               k, n_chunks);
+            LAUNCH_T(h, ec->fn, grid, dim3(256), 0, k, pl.n_chunks, clk);
             tick(h, 2, false);
-            k.n_partials = n_chunks;
         } break;
-        case FAM_USER: {
-            long long want = (262144 + n_prop - 1) / n_prop;
-            long long cap = h->m.N / 32;
-            if (cap < 1) cap = 1;
-            if (want > cap) want = cap;
-            if (want > h->partial_cap) want = h->partial_cap;
-            if (h->m.user_row) want = 1;
+        case K2_CROSS_MFMA: {
+            const Inst<CrossFn>* e = nullptr;
+            PICK(e, "k_cross_mfma", kCross, pl.key[0], pl.key[1]);
+            h->last.k2_key = e->key;
+            tick(h, 2, true);
+            for (int kp = 0; kp < pl.n_kpass; ++kp)
+                LAUNCH_T(h, e->fn, grid, dim3(256), 0, k, h->m.Ypad.get(), h->m.dpad, kp * pl.k0_stride, h->m.Xf.get(), h->m.n_tiles, pl.n_chunks,
+                         kp * pl.part0_stride);
+            tick(h, 2, false);
+        } break;
+        case K2_OBS:
+            tick(h, 2, true);
+            LAUNCH_T(h, k_obs_loglike, grid, dim3(256), 0, k, pl.n_chunks);
+            tick(h, 2, false);
+            break;
+        case K2_USER:
+        case K2_USER_ROW: {
             UserKParams u;
-            u.n_groups = k.n_groups; u.Np = k.Np; u.D = k.D; u.a_lo = k.a_lo; u.n_act = k.n_act; u.n_chunks = (int)want;
+            u.n_groups = k.n_groups; u.Np = k.Np; u.D = k.D; u.a_lo = k.a_lo; u.n_act = k.n_act; u.n_chunks = pl.n_chunks;
             u.nhyper = h->m.user_nhyper; u.with_prior = h->c.fitness_kind == DEMC_FITNESS_POSTERIOR ? 1 : 0;
             u.N = h->m.N; u.P = h->P; u.prop = k.prop; u.partial = k.partial;
             u.data = h->m.data; u.hyper = h->m.user_hyper; u.dims = h->m.user_dims; u.glist = k.glist; u.ndims = h->m.user_ndims; u.pad = 0;
             size_t sz = sizeof u;
             void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &u, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
-            h->last.k2 = h->m.user_row ? demc_handle::K2_USER_ROW : demc_handle::K2_USER;
             tick(h, 2, true, true);
-            hipError_t e = h->m.user_row
-                ? hipModuleLaunchKernel(h->m.user_kernel, (unsigned)n_prop, 1, 1, 256, 1, 1, 0, h->stream, nullptr, cfg)
-                : hipModuleLaunchKernel(h->m.user_kernel, (unsigned)((n_prop + 255) / 256), (unsigned)want, 1, 256, 1, 1, 0,
-                                        h->stream, nullptr, cfg);
+            const hipError_t e = hipModuleLaunchKernel(h->m.user_kernel, pl.grid_x, pl.grid_y, 1, 256, 1, 1, 0, h->stream, nullptr, cfg);
             tick(h, 2, false, true);
             if (e != hipSuccess) return fail(h, DEMC_EHIP, std::string("hipModuleLaunchKernel: ") + hipGetErrorString(e));
-            k.n_partials = (int)want;
         } break;
-        case FAM_SIM: {
-            if (int rc = launch_sim_loglike(h, k, n_prop)) return rc;
-            k.n_partials = 1;
-        } break;
-        case FAM_ODE_LV: {
-            if (int rc = launch_ode_loglike(h, k)) return rc;
-            k.n_partials = 1;
-        } break;
-        case FAM_HIER_BINOMIAL:
-        case FAM_HIER_GAUSSIAN: {
-            h->last.k2 = demc_handle::K2_HIER;
+        case K2_HIER:
             tick(h, 2, true);
-            LAUNCH_T(h, k_hier_loglike, dim3((unsigned)n_prop), dim3(256), 0, k);
+            LAUNCH_T(h, k_hier_loglike, grid, dim3(256), 0, k);
             tick(h, 2, false);
-            k.n_partials = 1;
-        } break;
-        default:
-            return fail(h, DEMC_EUNSUPPORTED, "model family not set or not registered");
+            break;
+        default: break;  // (MvNormal in SUFFSTAT mode: K1 already formed S)
     }
+    k.n_partials = pl.n_partials;  // (after the launch: K2's own kernarg says one plane, K3 reads them all)
     return DEMC_OK;
 }
 
-bool is_mvn(int fam) { return fam == FAM_MVN_FULL || fam == FAM_MVN_ISO; }
-
-// which tail K1 carries for this model, mode and schedule
-void set_tail_flags(demc_handle* h, KParams& k) {
-    const demc_config& c = h->c;
-    const bool suff = c.loglike_mode == DEMC_LOGLIKE_SUFFSTAT;
-    // K1 tails: MvNormal preparation always; the whole update when the likelihood is O(D^2) given data-only
-    // statistics and a phase writes only rows that no other workgroup reads (two_colour, or the identity pass)
-    k.fuse_prep = is_mvn(h->m.family) ? 1 : 0;
-    k.prep_mfma = (h->m.family == FAM_MVN_FULL && k.lpp >= 4 && k.lpp <= 16 && h->m.d <= 32) ? 1 : 0;
-    k.sx = (k.fuse_prep && suff) ? h->m.sx : nullptr;
-    k.Ainv = (h->m.family == FAM_MVN_FULL) ? h->m.Ainv : nullptr;
-    // small-N scalar-data families: the sub-group of a particle sums the per-observation terms itself
-    // (hierarchical families: one term per subject, i.e. O(D) like the proposal itself; their Gaussian form has p.d
-    // observations behind every subject)
-    const long long obs_work = (h->m.family == FAM_HIER_GAUSSIAN) ? h->m.N * (h->m.d > 0 ? h->m.d : 1) : h->m.N;
-    const bool cheap_obs = ((h->m.family == FAM_GAUSSIAN || h->m.family == FAM_BINOMIAL || h->m.family == FAM_RASTRIGIN) &&
-                            h->m.N / k.lpp <= 512) ||
-                           (h->hier_scr && obs_work / k.lpp <= 4096);
-    // nothing a moving particle reads can move in the same launch: two_colour (partners rest), the identity pass, and the
-    // sequential schedule (one particle per group and launch, handled by that group's only workgroup)
-    // ... and the synchronous schedule when every partner row comes from the HISTORY (resample: rows of earlier iterations,
-    // which this launch does not write) and no base particle is read from the current population (random_gamma reads one
-    // during burn-in only, crossover.jl:156-164): the reference's own parallel-safe scheme runs as ONE kernel
-    const bool hist_private = c.schedule == DEMC_SCHED_SYNCHRONOUS && c.partner_kind == DEMC_PARTNER_HISTORY && k.mode == MODE_STEP &&
-                              !(c.proposal_kind == 0 && k.iter <= c.burnin);
-    const bool phase_private = c.schedule == DEMC_SCHED_TWO_COLOUR || c.schedule == DEMC_SCHED_SEQUENTIAL || k.mode == MODE_IDENT || hist_private;
-    h->tf_cheap_obs = cheap_obs;
-    k.fuse_obs = (cheap_obs && phase_private && c.fuse != 1) ? 1 : 0;
-    k.fuse_accept = (((k.fuse_prep && suff) || k.fuse_obs) && c.fuse != 1 && phase_private) ? 1 : 0;
-    k.write_prop = (!k.fuse_accept || k.trace) ? 1 : 0;
+// the tail K1 carries (tail_flags), copied into the kernarg
+void apply_tail(const demc_handle* h, KParams& k, const TailFlags& t) {
+    k.fuse_prep = t.fuse_prep; k.prep_mfma = t.prep_mfma; k.fuse_obs = t.fuse_obs; k.fuse_accept = t.fuse_accept;
+    k.write_prop = t.write_prop;
+    k.sx = t.pass_sx ? h->m.sx : nullptr;
+    k.Ainv = t.pass_ainv ? h->m.Ainv : nullptr;
 }
-// The default sampler and nothing else, with partners of `partner_kind`: the kernels have instances with every other branch compiled
-// out.  1: the default sampler; 2: + snooker updates / block updates, their own lean instance; 0: anything else -- a trace and a
-// replay among it -- takes the general instance.
-// (DEMC_PARTNER_HISTORY is DE-MC_Z, sample = resample, crossover.jl:113-124: partners are cells of the history, so there is no tile,
-// and the lean instances of the no-tile form serve it -- the reference's own DE-MC_Z runs use theta_snooker = 0.1,
-// test/multivariate_normal_tests.jl:50-59, Examples/Hierarchical_Example.jl:103-114)
-int lean_level(const demc_handle* h, int partner_kind, int mode = MODE_STEP) {
-    const demc_config& c = h->c;
-    const bool base = mode == MODE_STEP && c.proposal_kind == 0 && c.partner_kind == partner_kind && c.update_kind == 0 &&
-                      c.fitness_kind == 0 && c.kappa == 1.0 && !c.trace && !h->rp.active;
-    return !base ? 0 : (c.theta_snooker == 0.0 && c.n_blocks == 0) ? 1 : 2;
-}
-int tail_of(const KParams& k) { return k.prep_mfma ? TAIL_PREP_MFMA : k.fuse_prep ? TAIL_PREP : k.fuse_obs ? TAIL_OBS : TAIL_NONE; }
 
 // one launch in the K1 slot, inside its timing bracket; demc_last_kernels names the instance
 void launch_k1(demc_handle* h, const K1Inst* e, unsigned grid, int wg, size_t lds, const KParams& k) {
@@ -757,299 +641,112 @@ void launch_k1(demc_handle* h, const K1Inst* e, unsigned grid, int wg, size_t ld
     tick(h, 0, false);
 }
 
-// {scalars inside the block, its longest run} of a block mask in run-length form (MaskRuns / KParams::mrun_*)
-struct BlockSpan { int inside = 0, longest = 0; };
-BlockSpan block_span(int n_run, unsigned in, const int* start, int D) {
-    BlockSpan s;
-    for (int r = 0; r < n_run; ++r)
-        if ((in >> r) & 1u) {
-            const int len = (r + 1 < n_run ? start[r + 1] : D) - start[r];
-            s.inside += len;
-            s.longest = std::max(s.longest, len);
-        }
-    return s;
-}
-
-// Whether this configuration can take the frozen-row sweep (k_frozen_sweep) at all: a blocked hierarchical family with long rows,
-// the whole update fused, no trace, no recombination, and enough moving particles -- counted on the geometry's groups, so that a
-// shard takes the form of the whole run -- for two workgroups per CU.  launch_phase refines it per sweep (the block's scalars, the
-// phase's own particle count and pool); plan_frozen_order and plan_snap2 prepare nothing where it says no.
-bool frozen_possible(const demc_handle* h) {
+// The sweep-start snapshot into the proposal buffers (which a fused sweep does not use): the weights, and the rows -- whole, or
+// the columns of the sweep's block only.
+int take_snapshot(demc_handle* h, const KParams& k, bool block_only) {
     const demc_config& c = h->c;
-    const int n_act = c.schedule == DEMC_SCHED_TWO_COLOUR ? c.Np - c.Np / 2 : c.schedule == DEMC_SCHED_SEQUENTIAL ? 1 : c.Np;
-    return (h->m.family == FAM_HIER_BINOMIAL || h->m.family == FAM_HIER_GAUSSIAN) && h->hier_scr && h->lpp > 64 && c.n_blocks >= 1 &&
-           c.fuse == 0 && !c.trace && c.kappa == 1.0 && (long long)h->geo_groups * n_act >= 2LL * h->n_cus;
+    HIPCHK(hipMemcpyAsync(h->prop_prior, h->weight, sizeof(double) * (size_t)h->P, hipMemcpyDeviceToDevice, h->stream));
+    if (!block_only) {
+        HIPCHK(hipMemcpyAsync(h->prop, h->theta, sizeof(double) * (size_t)h->P * c.D, hipMemcpyDeviceToDevice, h->stream));
+        return DEMC_OK;
+    }
+    for (int r = 0; r < k.n_mrun; ++r)  // the columns of the block: a strided copy per run of the mask (a few doubles per row)
+        if ((k.mrun_in >> r) & 1u) {
+            const int lo = k.mrun_start[r], hi = r + 1 < k.n_mrun ? k.mrun_start[r + 1] : c.D;
+            HIPCHK(hipMemcpy2DAsync(h->prop + lo, sizeof(double) * (size_t)c.D, h->theta + lo, sizeof(double) * (size_t)c.D,
+                                    sizeof(double) * (size_t)(hi - lo), (size_t)h->P, hipMemcpyDeviceToDevice, h->stream));
+        }
+    return DEMC_OK;
 }
 
+// whether two 256-thread workgroups of k_longrow with `lds` bytes of dynamic LDS are resident on a CU (asked once per row size)
+int two_longrows_fit(demc_handle* h, size_t lds) {
+    if (h->lr_two_lds != lds) {
+        int nb = 0;
+        const K1Inst* e256 = nullptr;
+        PICK(e256, "k_longrow", kLongrow, 256);
+        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)e256->fn, 256, lds));
+        h->lr_two_lds = lds;
+        h->lr_two_fit = nb >= 2;
+    }
+    return DEMC_OK;
+}
+
+// One sweep and colour phase: the plan (demc_geometry.hpp: kernel, geometry, fuse flags, snapshot), the copies it names, the
+// kernarg, the launch, and the by-product snapshot's bookkeeping.
 // (`k` by value: the frozen-sweep / snapshot overrides below -- glist, base_*, snap_*, the fuse flags -- stay inside this launch;
 // run_sweep reuses its own copy for the second colour phase and for every particle of the sequential schedule)
 int launch_phase(demc_handle* h, KParams k) {
-    const long long n_prop = (long long)k.n_groups * k.n_act;
-    if (n_prop == 0) return DEMC_OK;
+    if ((long long)k.n_groups * k.n_act == 0) return DEMC_OK;
     const demc_config& c = h->c;
-    set_tail_flags(h, k);
-    const int wg = k.lpp > 256 ? 512 : 256;  // K1 workgroup: 512 threads when one particle takes 512 lanes
-    const int ppp = wg / k.lpp, ppp3 = 256 / k.lpp3;
-    const int max_split = (k.n_act + ppp - 1) / ppp;
-    const int target_wgs = 512;
-    int n_split = (target_wgs + k.n_groups - 1) / k.n_groups;
-    if (n_split > max_split) n_split = max_split;
-    if (n_split < 1) n_split = 1;
-    k.n_split = n_split;
-    const bool tile = k.tile_in_lds && c.partner_kind == DEMC_PARTNER_CURRENT && wg == 256;
-    // plan stage (per-particle scalars once per workgroup): 4 doubles + 4 ints per particle of the workgroup's slice
-    const size_t per_split = (size_t)(k.n_act + n_split - 1) / n_split;
-    const size_t plan_bytes = per_split * (4 * sizeof(double) + 4 * sizeof(int));
-    // tile = the partner pool, plus the workgroup's own slice of moving rows when those lie outside the pool
-    k.own_in_pool = (k.a_lo >= k.pool_lo && k.a_lo + k.n_act <= k.pool_lo + k.pool_n) ? 1 : 0;
-    k.tile_rows = k.pool_n + (k.own_in_pool ? 0 : (int)per_split);
-    const size_t lds_tile = h->k1_lds - h->k1_tile_bytes + (size_t)k.tile_rows * c.D * sizeof(double);  // <= k1_lds
-    k.plan = (tile && k.mode == MODE_STEP && k.lpp >= 4 && k.lpp <= 64 && lds_tile + plan_bytes <= kMaxDynLds && !h->rp.active) ? 1 : 0;
-    // long rows of a hierarchical family, whole update fused: the dedicated one-pass kernel (demc_longrow.hpp)
-    const size_t cdf_doubles = k.pool_n > 256 ? (size_t)k.pool_n + ((size_t)k.pool_n + 15) / 16 : 0;
-    const size_t lr_lds = ((((size_t)c.D + 1) & ~(size_t)1) + cdf_doubles) * sizeof(double);
-    const bool lr_shape = k.lpp > 64 && h->hier_scr && k.mode == MODE_STEP && !h->rp.active && c.fuse != 2 && h->n_seg > 0 && lr_lds <= kMaxDynLds;
-    // DE-MC_Z INSIDE burn-in (Examples/Hierarchical_Example.jl:103-114 spends half its run there): random_gamma's base particle
-    // (crossover.jl:156-164) is a row of the current population, which another workgroup of this synchronous launch may be writing,
-    // so set_tail_flags left the sweep unfused (K1 -> k_hier_loglike -> K3 through the proposal buffer: 2.3x the time).  The rows
-    // and weights of the sweep's START are what the synchronous schedule reads anyway: two device-to-device copies (into the
-    // proposal buffers, which a fused sweep does not use) make them a snapshot nobody writes, and the sweep is ONE k_longrow
-    // launch again -- base rows and select_base's weights from the snapshot (KParams::base_theta / base_weight).
-    // The same holds for every family whose update fuses into K1 past burn-in (the general kernel's no-tile form reads its base
-    // rows through the same two pointers): with the snapshot, DE-MC_Z is one launch per sweep inside burn-in as well as past it.
-    const bool suff_mvn = k.fuse_prep && c.loglike_mode == DEMC_LOGLIKE_SUFFSTAT;
-    bool snapshot = false, have_snap2 = false;
-    if (!k.fuse_accept && k.mode == MODE_STEP && c.schedule == DEMC_SCHED_SYNCHRONOUS && c.partner_kind == DEMC_PARTNER_HISTORY &&
-        c.proposal_kind == 0 && k.iter <= c.burnin && (h->tf_cheap_obs || suff_mvn) && c.fuse == 0 && !k.trace && !h->rp.active &&
-        k.theta == h->theta) {
-        // (the copies follow the choice of the kernel: a frozen sweep reads its base row at the block's scalars only)
-        snapshot = true;
+    Phase p;
+    p.n_groups = k.n_groups; p.a_lo = k.a_lo; p.n_act = k.n_act; p.pool_lo = k.pool_lo; p.pool_n = k.pool_n; p.mode = k.mode;
+    p.iter = k.iter; p.sweep = (int)k.sweep; p.lpp = k.lpp; p.lpp3 = k.lpp3;
+    p.tile_in_lds = k.tile_in_lds != 0; p.live = k.theta == h->theta;
+    p.masked = k.mask != nullptr; p.n_mrun = k.n_mrun; p.mrun_in = k.mrun_in; p.mrun_start = k.mrun_start;
+    p.snap2 = h->snap2.get() != nullptr; p.snap2_iter = h->snap2_iter; p.snap2_sweep = h->snap2_sweep;
+    p.frozen_order = h->frozen_order_d.get() != nullptr; p.frozen_iter0 = h->frozen_iter0; p.frozen_iters = h->frozen_iters;
+    int rc_fit = DEMC_OK;
+    const PhasePlan pl = plan_phase(setup_of(h), p, [&](size_t lds) { return (rc_fit = two_longrows_fit(h, lds)) == DEMC_OK && h->lr_two_fit; });
+    if (rc_fit != DEMC_OK) return rc_fit;
+    // the snapshot the base rows are read from
+    if (pl.snap == SNAP_REUSE) {
+        h->snap2_iter = -1;  // (used once: by the sweep it was written for, in the demc_step call that wrote it)
+        k.base_theta = h->snap2; k.base_weight = h->snap2_w;
+    } else if (pl.snap != SNAP_NONE) {
         k.base_theta = h->prop; k.base_weight = h->prop_prior;
-        k.fuse_obs = h->tf_cheap_obs ? 1 : 0; k.fuse_accept = 1; k.write_prop = 0;
-        // ... and when the sweep before this one was a frozen sweep over the whole population, it left this snapshot behind
-        if (h->snap2 && h->snap2_iter == (int64_t)k.iter && h->snap2_sweep == (int)k.sweep && !h->cur_glist) {
-            h->snap2_iter = -1;  // (used once: by the sweep it was written for, in the demc_step call that wrote it)
-            snapshot = false;
-            have_snap2 = true;
-            k.base_theta = h->snap2; k.base_weight = h->snap2_w;
-        }
+        if (int rc = take_snapshot(h, k, pl.snap == SNAP_BLOCK)) return rc;
     }
-    auto take_snapshot = [&](bool block_only) -> int {
-        HIPCHK(hipMemcpyAsync(h->prop_prior, h->weight, sizeof(double) * (size_t)h->P, hipMemcpyDeviceToDevice, h->stream));
-        if (!block_only) {
-            HIPCHK(hipMemcpyAsync(h->prop, h->theta, sizeof(double) * (size_t)h->P * c.D, hipMemcpyDeviceToDevice, h->stream));
-            return DEMC_OK;
-        }
-        for (int r = 0; r < k.n_mrun; ++r)  // the columns of the block: a strided copy per run of the mask (a few doubles per row)
-            if ((k.mrun_in >> r) & 1u) {
-                const int lo = k.mrun_start[r], hi = r + 1 < k.n_mrun ? k.mrun_start[r + 1] : c.D;
-                HIPCHK(hipMemcpy2DAsync(h->prop + lo, sizeof(double) * (size_t)c.D, h->theta + lo, sizeof(double) * (size_t)c.D,
-                                        sizeof(double) * (size_t)(hi - lo), (size_t)h->P, hipMemcpyDeviceToDevice, h->stream));
-            }
-        return DEMC_OK;
-    };
-    // A block sweep that FREEZES the row (the block holds a few hyper-parameters): the sweep reduced to what it is -- one pass
-    // over the particle's own row, partner rows read at the block's scalars only (whole only by the one particle in ten whose
-    // snooker coin fired: its projections run over the row), no LDS row, four workgroups per CU (<256>: 120 registers; three for
-    // <256,big>: 155; demc_frozen.hpp) -- instead of
-    // the subject-sweep machinery of k_longrow at eight waves per CU.  Partners from the population or from the history, the
-    // base row from the sweep-start snapshot when there is one.
-    if (frozen_possible(h) && lr_shape && k.fuse_obs && k.fuse_accept && k.mask && k.n_mrun > 0 && k.pool_n <= 256) {
-        const BlockSpan blk = block_span(k.n_mrun, k.mrun_in, k.mrun_start, c.D);
-        // (enough moving particles for several workgroups per CU, counted on the geometry's groups so that a shard takes the form
-        // of the whole run: with one particle per CU the launch is that particle's dependent prologue whatever follows it --
-        // measured on cfg4's share: no form of this kernel beats k_longrow<512> there, profiles/r05/NOTES.md)
-        // (a long run inside the block -- the subject block -- takes the BIG instance: proposals formed on the fly, four scalars
-        // per thread and round behind 16-byte loads, which the hierarchical Binomial family's even rows allow)
-        const bool big = blk.longest > 256;
-        const bool on = blk.inside >= 1 && (long long)h->geo_groups * k.n_act >= 2LL * h->n_cus &&
-                        (big ? h->m.family == FAM_HIER_BINOMIAL && (c.D & 1) == 0 : blk.inside <= kFrozenMax);
-        if (on) {
-            if (snapshot)
-                if (int rc = take_snapshot(true)) return rc;
-            if (!k.glist && h->frozen_order_d && k.iter >= h->frozen_iter0 && k.iter < h->frozen_iter0 + h->frozen_iters &&
-                (int)k.sweep < c.n_blocks)
-                k.glist = h->frozen_order_d + ((size_t)(k.iter - h->frozen_iter0) * c.n_blocks + k.sweep) * (size_t)c.n_groups;
-            // the next sweep of this iteration will want a snapshot of its start as well: this sweep writes it on its way (every
-            // row passes through the kernel once) -- when it moves the whole population and does not itself read the buffer
-            const int n_sweeps = c.n_blocks > 0 ? c.n_blocks : 1;
-            if (!big && snapshot && !have_snap2 && (int)k.sweep + 1 < n_sweeps && !h->cur_glist && k.a_lo == 0 && k.n_act == c.Np &&
-                k.n_groups == c.n_groups && h->snap2) {  // (allocated at plan time -- plan_snap2 -- never inside an enqueued step)
-                k.snap_theta = h->snap2; k.snap_weight = h->snap2_w;
-                h->snap2_iter = (int64_t)k.iter; h->snap2_sweep = (int)k.sweep + 1;
-            }
-            const K1Inst* e = nullptr;
-            PICK(e, "k_frozen_sweep", kFrozen, 256, 3, 2, big);
-            launch_k1(h, e, (unsigned)n_prop, 256, 0, k);
-            return DEMC_OK;
-        }
+    apply_tail(h, k, pl.t);
+    k.n_split = pl.n_split; k.own_in_pool = pl.own_in_pool; k.tile_rows = pl.tile_rows; k.plan = pl.plan;
+    if (pl.frozen_order)
+        k.glist = h->frozen_order_d + ((size_t)(k.iter - h->frozen_iter0) * c.n_blocks + k.sweep) * (size_t)c.n_groups;
+    if (pl.write_snap2) {
+        k.snap_theta = h->snap2; k.snap_weight = h->snap2_w;
+        h->snap2_iter = (int64_t)k.iter; h->snap2_sweep = (int)k.sweep + 1;
     }
-    if (snapshot)
-        if (int rc = take_snapshot(false)) return rc;
-    if (lr_shape && k.fuse_obs && k.fuse_accept) {
-        // Enough moving particles for two workgroups per CU (counted on the geometry's groups, so that a shard takes the
-        // same form as the whole run): 256 threads each -- one wave per SIMD per workgroup, two particles per CU out of
-        // step, one's prologue and row moves under the other's pass -- when two rows fit in the CU's LDS.
-        if (h->lr_two_lds != lr_lds) {  // (asked once per row size)
-            int nb = 0;
-            const K1Inst* e256 = nullptr;
-            PICK(e256, "k_longrow", kLongrow, 256);
-            HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)e256->fn, 256, lr_lds));
-            h->lr_two_lds = lr_lds;
-            h->lr_two_fit = nb >= 2;
-        }
-        const bool two_per_cu = (long long)h->geo_groups * k.n_act >= 2LL * h->n_cus && h->lr_two_fit;
-        const int wg_lr = two_per_cu ? 256 : 512;
-        const K1Inst* e = nullptr;
-        PICK(e, "k_longrow", kLongrow, wg_lr);
-        // persistent: as many workgroups as are resident at once, each takes particles blockIdx.x, + gridDim.x, ... (the
-        // row moves of one particle then run inside the span loops of the next: demc_longrow.hpp).  A multiple of 8 keeps
-        // a workgroup's particles on its own XCD (the kernel's blockIdx -> group mapping).
-        long long grid_lr = (long long)(wg_lr == 512 ? 1 : 2) * h->n_cus;
-        if (grid_lr > n_prop || grid_lr < 1) grid_lr = n_prop;
-        if ((k.n_groups & 7) == 0 && grid_lr >= 8) grid_lr &= ~7LL;
-        launch_k1(h, e, (unsigned)grid_lr, wg_lr, lr_lds, k);
-        return DEMC_OK;
-    }
-    const size_t lds = tile ? lds_tile + (k.plan ? plan_bytes : 0) : h->k1_lds - h->k1_tile_bytes;
-    // LEAN: the general instance (0), the default sampler (1), + snooker / block updates (2) -- without a tile for partners from the
-    // history (DE-MC_Z); a 512-thread workgroup per particle (very long rows, no tile) has the general instance only
-    const int lean = wg == 256 ? lean_level(h, tile ? DEMC_PARTNER_CURRENT : DEMC_PARTNER_HISTORY, k.mode) : 0;
     const K1Inst* e = nullptr;
-    PICK(e, "k_propose", kPropose, wg, tile, tail_of(k), false, lean);
-    launch_k1(h, e, (unsigned)(k.n_groups * n_split), wg, lds, k);
-    if (k.fuse_accept) return DEMC_OK;
+    switch (pl.kernel) {
+        case K1_FROZEN: PICK(e, "k_frozen_sweep", kFrozen, 256, 3, 2, pl.big); break;
+        case K1_LONGROW: PICK(e, "k_longrow", kLongrow, pl.wg); break;
+        case K1_PROPOSE: PICK(e, "k_propose", kPropose, pl.wg, pl.tile, pl.tail, false, pl.lean); break;
+    }
+    launch_k1(h, e, (unsigned)pl.grid, pl.wg, pl.lds, k);
+    if (!pl.chain) return DEMC_OK;
     int rc = launch_loglike(h, k);
     if (rc != DEMC_OK) return rc;
     h->last.k3 = true;
     tick(h, 3, true);
-    LAUNCH_T(h, k_accept_store, dim3((unsigned)((n_prop + ppp3 - 1) / ppp3)), dim3(256), 0, k);
+    LAUNCH_T(h, k_accept_store, dim3((unsigned)pl.k3_grid), dim3(256), 0, k);
     tick(h, 3, false);
     return DEMC_OK;
 }
 
 // ---- planning the whole-update forms: once per model (size_k1_lds), the lean ones again whenever the prior table changes ----
+// The geometry comes from demc_geometry.hpp (plan_resident, plan_stream, plan_lean); here the instances it names are resolved
+// and the plan is stored.
 
-// lanes per particle of a resident k_propose: as many as let the moving half fill one pass of `budget` threads -- from 4 up to one
-// lane per pair of scalars (fewer than 4 only where the row has fewer pairs)
-int resident_lpp(int n_act, int lpp_max, int budget) {
-    int lpp = 4;
-    while (lpp * 2 <= lpp_max && n_act * lpp * 2 <= budget) lpp *= 2;
-    return lpp > lpp_max ? lpp_max : lpp;
-}
-
-// the prior table has a Normal(a, theta[ref]) entry (hierarchical scale priors), which the lean kernels do not know
-bool has_normal_ref(const demc_handle* h) {
-    for (const DimTab& t : h->h_tab)
-        if (t.kind == PR_NORMAL_REF) return true;
-    return false;
-}
-
-// k_res_mvn's DT: the row length where an instance has it compiled in, else 0.  MvNormal-full: 32 and 8 (cfg3, cfg2) when the prior
-// table is one segment; MvNormal-iso: the row of the reference's own test -- 30 means and sigma -- whose instance reads the table
-// as [one entry for the 30 means | one for sigma]: any other table takes the general row length
-int compiled_row_length(const demc_handle* h) {
-    const int D = h->c.D;
-    if (h->m.family == FAM_MVN_ISO) return (D == 31 && h->n_seg == 2 && h->seg_start[1] == 30) ? 31 : 0;
-    return (h->n_seg == 1 && (D == 32 || D == 8)) ? D : 0;
-}
-
-// FORM_RESIDENT: one workgroup per group, both colour phases of several iterations in one launch.  It needs the fused accept tail
-// (the whole update inside K1), the two_colour schedule (a phase writes only rows nobody reads), partners from the current
-// population, and the whole group + its scratch in LDS.
-int plan_resident(demc_handle* h) {
-    const demc_config& c = h->c;
+int set_resident_form(demc_handle* h) {
     FormPlan& f = h->form[FORM_RESIDENT];
     f = FormPlan();
-    if (c.fuse != 0 || c.schedule != DEMC_SCHED_TWO_COLOUR || c.partner_kind != DEMC_PARTNER_CURRENT || c.Np < 4) return DEMC_OK;
-    const int lpp_max = pow2_ceil((c.D + 1) / 2);
-    if (lpp_max > 64) return DEMC_OK;
-    const int n_act = c.Np - c.Np / 2;
-    const size_t D = (size_t)c.D, Np = (size_t)c.Np, d = (size_t)h->m.d;
-    const bool mvn = is_mvn(h->m.family);
-    // geometry for a thread budget: lanes per particle, workgroup size, LDS bytes; false when the update cannot be fused or the
-    // group does not fit
-    int lpp = 0, wg = 0, tail = TAIL_NONE;
-    size_t bytes = 0, scr_doubles = 0;
-    auto geometry = [&](int budget) -> bool {
-        lpp = resident_lpp(n_act, lpp_max, budget);
-        wg = (n_act * lpp > 256 && budget > 256) ? 512 : 256;
-        KParams k = base_params(h);
-        k.lpp = lpp;
-        k.mode = MODE_STEP;
-        set_tail_flags(h, k);
-        if (!k.fuse_accept) return false;
-        tail = tail_of(k);
-        scr_doubles = (k.fuse_prep || k.fuse_obs) ? (size_t)(wg / lpp) * (D + 2) : 0;
-        const size_t doubles =
-            Np * D + Np + (Np + (Np + 15) / 16) + ((h->m.family == FAM_MVN_FULL && h->ainv_lds) ? d * d : 0) + (mvn ? d : 0) + scr_doubles;
-        bytes = doubles * sizeof(double) + (size_t)n_act * (4 * sizeof(double) + 4 * sizeof(int));
-        return bytes <= kMaxDynLds;
-    };
-    // More groups than CUs: two 256-thread workgroups per CU keep twice as many groups in flight as one of 512 -- when
-    // two of them fit in a CU's LDS (measured at 1024 groups x 64: 0.082 -> see DESIGN.md section 6).
-    const bool two_per_cu = h->geo_groups > 256 && geometry(256) && bytes <= 75 * 1024;
-    if (!two_per_cu && !geometry(512)) return DEMC_OK;
-    for (int lean = 0; lean < 3; ++lean) PICK(f.k1[lean], "k_propose", kPropose, wg, true, tail, true, lean);
-    f.ok = true; f.wg = wg; f.lds = bytes; f.lpp = lpp; f.scr_doubles = (int)scr_doubles;
+    const FormGeo g = plan_resident(setup_of(h));
+    if (!g.ok) return DEMC_OK;
+    for (int lean = 0; lean < 3; ++lean) PICK(f.k1[lean], "k_propose", kPropose, g.wg, true, g.tail, true, lean);
+    static_cast<FormGeo&>(f) = g;
     return DEMC_OK;
 }
 
-// The observation stream inside a resident kernel: the geometry (h->st) and FORM_STREAM, the general kernel around it.
-// 256-thread form: one wave per SIMD, i.e. the whole register file (512 per lane, AGPRs included) behind each wave -- what does
-// not fit the 256 architectural VGPRs spills to AGPRs instead of scratch memory; 512 threads when a colour needs the lanes.
-// It is for populations too small to fill the chip with one K1 -> K2 -> K3 chain per colour phase (launch- and latency-bound):
-// MvNormal family, STREAMING likelihood, two_colour, current-population partners, at most one group per CU, the group and its
-// per-particle scratch in LDS, and a colour phase whose matrix work is in the launch-overhead range.  Large populations keep the
-// per-phase chain, whose k_cross_mfma runs at the matrix peak.
-// (DIRECT: the same geometry -- chunks of the observations per workgroup, hand-over granules -- serves FORM_LEAN_DIRECT only,
-// plan_lean; the general kernel has no such form.)  Nothing is allocated here: alloc_stream follows.
-int plan_stream(demc_handle* h) {
-    const demc_config& c = h->c;
-    StreamGeo& g = h->st;
+// the stream geometry (h->st) and FORM_STREAM, the general kernel around it.  Nothing is allocated here: alloc_stream follows.
+int set_stream_form(demc_handle* h) {
     FormPlan& f = h->form[FORM_STREAM];
-    g.ok = false;
     f = FormPlan();
-    const bool direct = c.loglike_mode == DEMC_LOGLIKE_DIRECT;
-    if (!is_mvn(h->m.family) || (c.loglike_mode != DEMC_LOGLIKE_STREAMING && !direct) || c.fuse != 0 || c.schedule != DEMC_SCHED_TWO_COLOUR ||
-        c.partner_kind != DEMC_PARTNER_CURRENT || c.Np < 4 || h->n_cus < 1 || h->geo_groups > h->n_cus || c.n_groups > h->n_cus ||
-        h->m.dpad > 64 || h->m.n_kpass != 1)
-        return DEMC_OK;
-    // Whether the form applies and into how many chunks C a group's observation tiles are cut is decided from the groups of
-    // the WHOLE population (geometry_groups), not from this shard's: C fixes the summation order of the cross terms, and a
-    // shard must make the choices of the unsharded run to reproduce it bit for bit (demc_create_multi, demc.h).
-    const int gg = h->geo_groups > c.n_groups ? h->geo_groups : c.n_groups;
-    const int nact_max = c.Np - c.Np / 2;
-    if (nact_max > 512) return DEMC_OK;
-    const double phase_flop = 2.0 * (double)nact_max * gg * (double)h->m.N * h->m.dpad;
-    if (phase_flop / 78.6e12 > 300e-6) return DEMC_OK;
-    const int lpp_max = pow2_ceil((c.D + 1) / 2);
-    if (lpp_max > 64) return DEMC_OK;
-    const int lpp = resident_lpp(nact_max, lpp_max, 512);
-    const int wg = nact_max * lpp <= 256 ? 256 : 512, ppp = wg / lpp;
-    const int rows = ((nact_max + ppp - 1) / ppp) * ppp;
-    int C = 1;
-    while (2 * C * gg <= h->n_cus && h->m.n_tiles / (2 * C) >= 8 && 2 * C <= 32) C *= 2;
-    const int chunk = (h->m.n_tiles + C - 1) / C;
-    const size_t D = (size_t)c.D, Np = (size_t)c.Np, d = (size_t)h->m.d;
-    const size_t scr_doubles = (size_t)rows * (D + 6);
-    const size_t doubles = Np * D + Np + (Np + (Np + 15) / 16) + ((h->m.family == FAM_MVN_FULL && h->ainv_lds) ? d * d : 0) + d + scr_doubles +
-                           (size_t)rows * h->m.dpad + (size_t)(wg / 64) * nact_max;
-    size_t bytes = doubles * sizeof(double) + (size_t)nact_max * (4 * sizeof(double) + 4 * sizeof(int)) +
-                   2 * sizeof(unsigned) * (size_t)C * nact_max + 16;
-    if (bytes > kMaxDynLds) return DEMC_OK;
-    const size_t xbytes = (size_t)(chunk + 1) * (h->m.dpad / 4) * 64 * sizeof(double);  // + the all-zero tail tile
-    const int x_lds = (bytes + xbytes <= kMaxDynLds) ? 1 : 0;
-    if (x_lds) bytes += xbytes;
-    if (!direct) {  // (k_propose's streaming form has the two tails an MvNormal model can take: PREP_MFMA, else PREP)
-        KParams k = base_params(h);
-        k.lpp = lpp;
-        set_tail_flags(h, k);
-        const int tail = tail_of(k) == TAIL_PREP_MFMA ? TAIL_PREP_MFMA : TAIL_PREP;
-        for (int lean = 0; lean < 3; ++lean) PICK(f.k1[lean], "k_propose", kPropose, wg, true, tail, true, lean, true);
-        f.ok = true; f.wg = wg; f.lds = bytes; f.lpp = lpp; f.scr_doubles = (int)scr_doubles;
+    static_cast<StreamDims&>(h->st) = StreamDims();
+    const StreamPlan p = plan_stream(setup_of(h));
+    if (p.form.ok) {
+        for (int lean = 0; lean < 3; ++lean) PICK(f.k1[lean], "k_propose", kPropose, p.form.wg, true, p.form.tail, true, lean, true);
+        static_cast<FormGeo&>(f) = p.form;
     }
-    g.ok = true; g.C = C; g.nact_max = nact_max; g.rows = rows; g.x_lds = x_lds; g.chunk_tiles = chunk;
+    static_cast<StreamDims&>(h->st) = p.dims;
     return DEMC_OK;
 }
 
@@ -1068,109 +765,23 @@ void alloc_stream(demc_handle* h) {
     if (!g.ok) h->form[FORM_STREAM].ok = false;
 }
 
-// The lean resident kernels of the default sampler -- whether the SAMPLER is the default one is asked per step (choose_form).  They
-// read the prior table in its run-length form and know no Normal(a, theta[ref]) prior, so this plan follows the table
-// (upload_dimtab); it reads plan_resident's and plan_stream's results and touches no device memory.
-int plan_lean(demc_handle* h) {
-    const demc_config& c = h->c;
-    for (Form f : {FORM_LEAN_SUFFSTAT, FORM_LEAN_STREAMING, FORM_LEAN_DIRECT, FORM_LEAN_OBS, FORM_LEAN_Z}) h->form[f] = FormPlan();
-    if (h->n_seg < 1 || has_normal_ref(h)) return DEMC_OK;  // (the table must fit its run-length form; hierarchical scale priors: the general kernel)
-    const int dt = compiled_row_length(h);
-    const int nact_max = c.Np - c.Np / 2;
-    // FORM_LEAN_OBS (demc_resobs.hpp): Gaussian, Binomial and the LNR with a handful of parameters (a lane per scalar of a
-    // sixteen-lane particle) and few enough observations for sixteen lanes to walk them; the group, its scratch rows and -- LNR --
-    // the log Phi(-z) table in LDS
-    if ((h->m.family == FAM_GAUSSIAN || h->m.family == FAM_BINOMIAL || h->m.family == FAM_LNR) && c.D <= 16 && c.fuse == 0 &&
-        c.schedule == DEMC_SCHED_TWO_COLOUR && c.partner_kind == DEMC_PARTNER_CURRENT && c.Np >= 4 && c.Np <= 512 && h->m.N / 16 <= 512) {
-        const size_t doubles = (size_t)c.Np * c.D + (size_t)c.Np + (size_t)nact_max + (size_t)(256 / 16) * c.D +
-                               (h->m.family == FAM_LNR ? (size_t)kLogPhiRows * kLogPhiRow : 0);
-        if (doubles * sizeof(double) <= kMaxDynLds) {
-            FormPlan& f = h->form[FORM_LEAN_OBS];
-            PICK(f.k1[0], "k_res_obs", kResObs, 256);
-            f.ok = true; f.wg = 256; f.lds = doubles * sizeof(double);
-        }
-    }
-    // FORM_LEAN_Z: DE-MC_Z (history partners, the synchronous schedule) on MvNormal-full in SUFFSTAT mode: the lean body with
-    // partner rows from the history, one launch per iteration -- all it needs in LDS are select_base's cumulative weights and the
-    // centred rows (... and on MvNormal(mu, sigma^2 I) with sigma a parameter, D = d + 1: the ISO instances of the same body)
-    const bool iso = h->m.family == FAM_MVN_ISO;
-    if (((h->m.family == FAM_MVN_FULL && c.D == h->m.d) || (iso && c.D == h->m.d + 1)) && c.D <= 32 && c.fuse == 0 &&
-        c.schedule == DEMC_SCHED_SYNCHRONOUS && c.partner_kind == DEMC_PARTNER_HISTORY && c.loglike_mode == DEMC_LOGLIKE_SUFFSTAT &&
-        c.Np >= 4 && nact_max * 4 <= 512 && h->hist) {
-        FormPlan& f = h->form[FORM_LEAN_Z];
-        f.wg = nact_max * 4 > 256 ? 512 : 256;
-        // cdf | chunk offsets | centred rows | A^-1 fragments [2][8][64] | the first half's held-back rows [wg][8] (+ alignment slack;
-        // the snooker instance parks them) | ISO: xbar and sum_i x~_i [2][32]: demc_resmvn.hpp, pend_l / iso_l
-        f.lds = ((size_t)c.Np + 16 + (size_t)(f.wg / 4) * ((size_t)c.D + 2) + 16 * 64 + 2 + (size_t)f.wg * 8 + 64) * sizeof(double);
-        // HIST: 1 past burn-in, 2 inside it (random_gamma reads a base particle, crossover.jl:164: the instance that loads its
-        // row), 3 with snooker updates
-        for (int hist = 1; hist <= 3; ++hist) PICK(f.k1[hist - 1], "k_res_mvn", kResMvn, f.wg, false, dt, hist, 1, iso);
-        f.ok = true;
-        return DEMC_OK;
-    }
-    // the two_colour forms (demc_resmvn.hpp): MvNormal full Sigma, D = d <= 32, one pass per phase
-    if (h->m.family != FAM_MVN_FULL || c.D != h->m.d || h->m.d > 32 || c.fuse != 0 || c.schedule != DEMC_SCHED_TWO_COLOUR ||
-        c.partner_kind != DEMC_PARTNER_CURRENT || c.Np < 4 || nact_max * 4 > 512)
-        return DEMC_OK;
-    // (DIRECT at D = 8: 512 threads whatever the group's size -- two waves per SIMD for the residual loop, which one wave per SIMD runs
-    // at half the vector pipe's rate: nothing else hides its LDS reads and dependent FP64 pairs)
-    const bool dir = c.loglike_mode == DEMC_LOGLIKE_DIRECT;
-    const bool dir8 = dir && c.D == 8 && nact_max * 4 <= 256;
-    const int wg = (nact_max * 4 > 256 || dir8) ? 512 : 256;
-    const size_t D = (size_t)c.D, Np = (size_t)c.Np;
-    const size_t base = (Np * D + Np + (size_t)nact_max + 16 + (size_t)(wg / 4) * (D + 2)) * sizeof(double);
-    if (c.loglike_mode == DEMC_LOGLIKE_SUFFSTAT) {
-        if (base > kMaxDynLds || !h->form[FORM_RESIDENT].ok) return DEMC_OK;
-        FormPlan& f = h->form[FORM_LEAN_SUFFSTAT];
-        PICK(f.k1[0], "k_res_mvn", kResMvn, wg, false, dt, 0, 1);
-        f.ok = true; f.wg = wg; f.lds = base;
-        return DEMC_OK;
-    }
-    // STREAMING / DIRECT: only where the observation stream applies (plan_stream: small populations), and only with one wave per
-    // SIMD (256 threads: what the observation stage needs beyond 256 VGPRs then lives in AGPRs, not scratch)
-    const StreamGeo& g = h->st;
-    if (!g.ok || (wg != 256 && !dir8)) return DEMC_OK;
-    // (DIRECT: the instances with the row length compiled in, the chunk of whitened rows in LDS)
-    if (dir && !(dt != 0 && h->m.dp_direct == c.D && h->m.dpad == c.D && g.x_lds)) return DEMC_OK;
-    size_t bytes = base + ((size_t)(wg / 4) * h->m.dpad + (size_t)(dir ? wg / 16 : wg / 64) * nact_max) * sizeof(double) + 16;  // (DIRECT: a partial sum per 16-lane row)
-    if (bytes > kMaxDynLds) return DEMC_OK;
-    // (the X chunk rides in LDS exactly when plan_stream found room for it; this kernel's other buffers are no larger)
-    if (g.x_lds) bytes += (size_t)(g.chunk_tiles + 1) * (h->m.dpad / 4) * 64 * sizeof(double);
-    if (bytes > kMaxDynLds) return DEMC_OK;
-    FormPlan& f = h->form[dir ? FORM_LEAN_DIRECT : FORM_LEAN_STREAMING];
-    PICK(f.k1[0], "k_res_mvn", kResMvn, wg, true, dt, 0, 1, false, dir);  // (DIRECT: <512, 8> and <256, 32>, what the tests above leave)
-    f.ok = true; f.wg = wg; f.lds = bytes;
+// The lean resident kernels of the default sampler: the plan follows the prior table (upload_dimtab); it reads set_resident_form's
+// and set_stream_form's results and touches no device memory.
+int set_lean_forms(demc_handle* h) {
+    const Form lean_forms[] = {FORM_LEAN_SUFFSTAT, FORM_LEAN_STREAMING, FORM_LEAN_DIRECT, FORM_LEAN_OBS, FORM_LEAN_Z};
+    for (Form f : lean_forms) h->form[f] = FormPlan();
+    const LeanPlan p = plan_lean(setup_of(h), h->form[FORM_RESIDENT].ok, h->st, (size_t)kLogPhiRows * kLogPhiRow);
+    if (p.form[FORM_LEAN_OBS].ok) PICK(h->form[FORM_LEAN_OBS].k1[0], "k_res_obs", kResObs, 256);
+    if (const FormGeo& g = p.form[FORM_LEAN_Z]; g.ok)
+        for (int hist = 1; hist <= 3; ++hist) PICK(h->form[FORM_LEAN_Z].k1[hist - 1], "k_res_mvn", kResMvn, g.wg, false, p.dt, hist, 1, p.iso);
+    if (const FormGeo& g = p.form[FORM_LEAN_SUFFSTAT]; g.ok) PICK(h->form[FORM_LEAN_SUFFSTAT].k1[0], "k_res_mvn", kResMvn, g.wg, false, p.dt, 0, 1);
+    for (Form f : {FORM_LEAN_STREAMING, FORM_LEAN_DIRECT})
+        if (const FormGeo& g = p.form[f]; g.ok) PICK(h->form[f].k1[0], "k_res_mvn", kResMvn, g.wg, true, p.dt, 0, 1, false, f == FORM_LEAN_DIRECT);
+    for (Form f : lean_forms) static_cast<FormGeo&>(h->form[f]) = p.form[f];
     return DEMC_OK;
 }
 
-// ---- choosing and launching a form ----
-
-// Which form carries the updates of a step call: the ONE place where the plans meet what is known only when a step is asked for --
-// a replay, an update of a subset of the groups (cur_glist), and the sampler around the kernels (lean_level: a trace, snooker
-// updates, blocks).  None of it changes inside a call, and no rule depends on the iteration: inside burn-in FORM_LEAN_Z takes
-// another instance (launch_form), not another form.  First match wins.
-Form choose_form(const demc_handle* h) {
-    const FormPlan* f = h->form;
-    // a replay hands over the caller's draws, which only the per-phase kernels read: no multi-iteration form, no lean DE-MC_Z body
-    if (h->rp.active) return FORM_PHASE;
-    const bool whole = h->cur_glist == nullptr;  // a subset of the groups never takes a spin_waiting form; it may take the others
-    const bool plain = lean_level(h, DEMC_PARTNER_CURRENT) == 1;  // the lean two_colour kernels: no trace, snooker updates or blocks
-    if (f[FORM_LEAN_DIRECT].ok && plain && whole) return FORM_LEAN_DIRECT;  // DIRECT: the one whole-update form it has
-    // STREAMING: the observation stream inside the resident kernel, the lean one where it serves
-    if (f[FORM_STREAM].ok && whole) return (plain && f[FORM_LEAN_STREAMING].ok) ? FORM_LEAN_STREAMING : FORM_STREAM;
-    // SUFFSTAT on MvNormal-full, then the per-observation families: their lean kernel before the general resident one
-    if (f[FORM_LEAN_SUFFSTAT].ok && plain) return FORM_LEAN_SUFFSTAT;
-    if (f[FORM_LEAN_OBS].ok && plain) return FORM_LEAN_OBS;
-    if (f[FORM_RESIDENT].ok) return FORM_RESIDENT;
-    // DE-MC_Z: the lean body has a snooker instance but no block sweeps -- snooker with blocks goes to the per-phase chain
-    const int lean_z = f[FORM_LEAN_Z].ok ? lean_level(h, DEMC_PARTNER_HISTORY) : 0;
-    if (lean_z == 1 || (lean_z == 2 && h->c.n_blocks == 0)) return FORM_LEAN_Z;
-    return FORM_PHASE;
-}
-
-// Iterations one launch carries at most: it stays in the millisecond range whatever the caller asks for, shorter where the grid
-// spins.  (FORM_LEAN_Z: cells of history row t - 1 come from every group, so a launch cannot span iterations.)
-int iterations_per_launch(Form f) { return (f == FORM_PHASE || f == FORM_LEAN_Z) ? 1 : spin_waiting(f) ? 64 : 1024; }
+// ---- launching a form (which one: choose_form, demc_geometry.hpp) ----
 
 // the kernarg fields of the observation stream (st_rows, the general kernel's scratch rows, apart), and its granules reset
 int stream_fields(demc_handle* h, KParams& k) {
@@ -1196,7 +807,7 @@ int launch_form(demc_handle* h, Form form, long long iter0, int n_iters) {
     const K1Inst* e = f.k1[0];
     if (form == FORM_RESIDENT || form == FORM_STREAM) {  // the general kernel: K1's own parameters, the tile being the whole group
         k.lpp = f.lpp;
-        set_tail_flags(h, k);
+        apply_tail(h, k, tail_flags(setup_of(h), k.lpp, k.mode, k.iter));
         k.n_sweeps = c.n_blocks > 0 ? c.n_blocks : 1;
         k.mask = c.n_blocks > 0 ? h->masks : nullptr;
         k.n_split = 1; k.exclude_self = 0; k.own_in_pool = 1; k.tile_rows = c.Np; k.tile_in_lds = 1;
@@ -1206,14 +817,14 @@ int launch_form(demc_handle* h, Form form, long long iter0, int n_iters) {
             k.sx = nullptr; k.fuse_accept = 1; k.write_prop = k.trace ? 1 : 0;
             k.st_rows = h->st.rows;
         }
-        e = f.k1[lean_level(h, DEMC_PARTNER_CURRENT)];
+        e = f.k1[lean_level(c, h->rp.active, DEMC_PARTNER_CURRENT)];
     } else if (form == FORM_LEAN_SUFFSTAT || form == FORM_LEAN_Z)
         k.sx = h->m.sx;
     if (form == FORM_LEAN_Z) {
         // (the HIST instances hold back the first half's stores for ONE iteration's store_row and form the cdf once per launch: the
         // precondition is checked here, and again by the kernel -- its phase loop runs no trip for any other count)
         if (n_iters != 1) return fail(h, DEMC_EINVAL, "lean DE-MC_Z kernel: one iteration per launch");
-        e = f.k1[lean_level(h, DEMC_PARTNER_HISTORY) == 2 ? 2 : iter0 <= c.burnin ? 1 : 0];
+        e = f.k1[lean_level(c, h->rp.active, DEMC_PARTNER_HISTORY) == 2 ? 2 : iter0 <= c.burnin ? 1 : 0];
     }
     unsigned grid = (unsigned)k.n_groups;
     if (spin_waiting(form)) {
@@ -1291,7 +902,7 @@ int evaluate_rows(demc_handle* h, double* theta_dev, double* weight_dev) {
 // memory is not an error (the sweeps copy the population instead); demc_last_error then says so.
 int plan_snap2(demc_handle* h) {
     const demc_config& c = h->c;
-    const bool want = frozen_possible(h) && c.n_blocks > 1 && c.schedule == DEMC_SCHED_SYNCHRONOUS &&
+    const bool want = frozen_possible(setup_of(h)) && c.n_blocks > 1 && c.schedule == DEMC_SCHED_SYNCHRONOUS &&
                       c.partner_kind == DEMC_PARTNER_HISTORY && c.proposal_kind == 0 && c.burnin >= 1;
     if (!want) {
         if (h->snap2 || h->snap2_w) {
@@ -1318,27 +929,10 @@ int raise_dyn_lds(demc_handle* h, const I (&tab)[N]) {
     return DEMC_OK;
 }
 
-// K1 LDS carve-up (must match k_propose): group tile (if it fits) | Np prefix sums | A^-1 [d][d] | theta' scratch
+// K1 LDS carve-up (carve_k1_lds, demc_geometry.hpp), the dynamic-LDS ceiling of every kernel that may ask for it, and the plans of
+// the whole-update forms
 int size_k1_lds(demc_handle* h) {
-    const demc_config& c = h->c;
-    const size_t D = (size_t)c.D;
-    const size_t cdf = ((size_t)c.Np + ((size_t)c.Np + 15) / 16) * sizeof(double);
-    size_t ainv = (h->m.family == FAM_MVN_FULL) ? (size_t)h->m.d * h->m.d * sizeof(double) : 0;
-    h->ainv_lds = ainv <= 40 * 1024 ? 1 : 0;  // d <= 71: beside the tile; wider data read A^-1 from L2
-    if (!h->ainv_lds) ainv = 0;
-    const size_t xb = is_mvn(h->m.family) ? (size_t)h->m.d * sizeof(double) : 0;
-    const size_t scr_rows = (size_t)(h->lpp >= 256 ? 1 : 256 / h->lpp) * (D + 2) * sizeof(double);
-    const bool hier = h->m.family == FAM_HIER_BINOMIAL || h->m.family == FAM_HIER_GAUSSIAN;
-    h->hier_scr = hier && scr_rows <= 96 * 1024;  // theta' of the pass fits in LDS: the subjects can be summed in K1
-    const bool scr_fam = is_mvn(h->m.family) || h->m.family == FAM_GAUSSIAN || h->m.family == FAM_BINOMIAL ||
-                         h->m.family == FAM_RASTRIGIN || h->hier_scr;
-    const size_t scr = scr_fam ? scr_rows : 0;
-    const size_t tile = (size_t)c.Np * D * sizeof(double);
-    h->tile_in_lds = (tile + cdf + ainv + xb + scr <= 96 * 1024) ? 1 : 0;
-    h->k1_tile_bytes = h->tile_in_lds ? tile : 0;
-    h->k1_scr_bytes = scr;
-    h->k1_lds = h->k1_tile_bytes + cdf + ainv + xb + scr;
-    if (h->k1_lds > kMaxDynLds) return fail(h, DEMC_EINVAL, "K1 LDS budget exceeded (Np too large for this D)");
+    if (Refusal r = carve_k1_lds(h->m.family, h->m.d, h->c.Np, h->c.D, h->lpp, h->k1)) return fail(h, r);
     // the attribute is per function, not per handle: always raise it to the same ceiling so that handles of different
     // sizes in one process do not lower each other's limit
     if (int rc = raise_dyn_lds(h, kPropose)) return rc;
@@ -1348,10 +942,10 @@ int size_k1_lds(demc_handle* h) {
     if (int rc = raise_dyn_lds(h, kSim)) return rc;
     if (int rc = raise_dyn_lds(h, kOde)) return rc;
     // the whole-update forms.  Decide, then allocate: the plans compute geometry only, the stream's buffers follow once it is known
-    if (int rc = plan_resident(h)) return rc;
-    if (int rc = plan_stream(h)) return rc;
+    if (int rc = set_resident_form(h)) return rc;
+    if (int rc = set_stream_form(h)) return rc;
     alloc_stream(h);
-    if (int rc = plan_lean(h)) return rc;
+    if (int rc = set_lean_forms(h)) return rc;
     HIPCHK(hipFuncSetAttribute((const void*)k_mig_pack, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynLds));
     return plan_snap2(h);
 }
@@ -1480,24 +1074,7 @@ int32_t demc_create(const demc_config* cfg, demc_handle** out) {
                 HIPCHK(hipMemcpy(h->id_hist + (size_t)r * P, row.data(), P * sizeof(int), hipMemcpyHostToDevice));
         }
     }
-    // lanes per particle: every lane owns dim pairs {2k,2k+1}, k = sl, sl+lpp, ...  Upper end: one pair per lane (or a
-    // whole workgroup per particle for very long rows).  Several pairs per lane give each lane independent work to
-    // overlap and fewer cross-lane reduction steps, so take the FEWEST lanes (>= 4) that still (i) fill every lane of
-    // a pass with a particle and (ii) leave at least two workgroups per CU; small populations keep the widest split
-    // (measured at D = 32: 256x256 particles -> 4, 128x256 -> 8, 64x128 and below -> 16).
-    h->lpp = pow2_ceil((c.D + 1) / 2);
-    if (h->lpp > 64) h->lpp = (c.D >= 4096) ? 512 : (c.D >= 2048) ? 256 : 64;  // a whole workgroup per particle for long rows
-    if (h->lpp <= 64) {
-        // moving particles per group and launch
-        const int n_act = (c.schedule == DEMC_SCHED_TWO_COLOUR) ? c.Np / 2 : (c.schedule == DEMC_SCHED_SEQUENTIAL) ? 1 : c.Np;
-        for (int l = 4; l < h->lpp; l *= 2) {
-            const int ppp = 256 / l;
-            if (ppp <= n_act && (long long)h->geo_groups * ((n_act + ppp - 1) / ppp) >= 512) {
-                h->lpp = l;
-                break;
-            }
-        }
-    }
+    h->lpp = lanes_per_particle(c.D, c.Np, c.schedule, h->geo_groups);  // (the rule and what it was measured on: demc_geometry.hpp)
     int rc_lds = size_k1_lds(h);
     if (rc_lds != DEMC_OK) return rc_lds;
     if (2 * (size_t)c.n_groups_total * sizeof(int) > 48 * 1024) return fail(h, DEMC_EINVAL, "n_groups_total too large");
@@ -1658,12 +1235,13 @@ static int upload_dimtab(demc_handle* h) {
     HIPCHK(hipMemcpy(h->dimtab, h->h_tab.data(), (size_t)h->c.D * sizeof(DimTab), hipMemcpyHostToDevice));
     const SegTable st = encode_segments(h->h_tab);
     h->n_seg = st.n_seg;
+    h->normal_ref = has_normal_ref(h->h_tab);
     std::memcpy(h->seg_start, st.seg_start, sizeof h->seg_start);
     h->seg_plain = st.seg_plain;
     HIPCHK(hipMemcpy(h->dimseg, st.segs, sizeof st.segs, hipMemcpyHostToDevice));
     // the lean resident kernel reads the table in its run-length form and knows no Normal(a, theta[ref]) prior: priors and
     // bounds arrive AFTER demc_set_model in every caller, so its plan is taken again whenever the table changes
-    return h->m.family >= 0 ? plan_lean(h) : DEMC_OK;
+    return h->m.family >= 0 ? set_lean_forms(h) : DEMC_OK;
 }
 
 int32_t demc_set_priors(demc_handle* h, const int32_t* kind, const double* a, const double* b, const int32_t* ref) {
@@ -1980,9 +1558,9 @@ static int exchange_overlapped(demc_handle* h, int64_t iter, int run) {
 static void plan_frozen_order(demc_handle* h, int64_t iter0, int32_t n_iters) {
     const demc_config& c = h->c;
     h->frozen_iters = 0;
-    // nothing to plan where launch_phase cannot take the frozen form at all (frozen_possible; a pool beyond the kernel's), for a
+    // nothing to plan where the phase plan cannot take the frozen form at all (frozen_possible; a pool beyond the kernel's), for a
     // subset of the groups (its own list), without mutation, or under a replay
-    if (!frozen_possible(h) || c.Np > 512 || h->cur_glist || c.beta <= 0.0 || h->rp.active || n_iters < 1) return;
+    if (!frozen_possible(setup_of(h)) || c.Np > 512 || h->cur_glist || c.beta <= 0.0 || h->rp.active || n_iters < 1) return;
     bool any = false;
     std::vector<char> frozen((size_t)c.n_blocks, 0);
     for (int b = 0; b < c.n_blocks && (size_t)b < h->mask_runs.size(); ++b) {
@@ -2037,7 +1615,9 @@ static int step_body(demc_handle* h, int64_t iter0, int32_t n_iters, bool with_m
     const int n_sweeps = c.n_blocks > 0 ? c.n_blocks : 1;  // block_update! main.jl:174-179
     plan_frozen_order(h, iter0, n_iters);
     h->snap2_iter = -1;  // (a by-product snapshot lives inside one call)
-    const Form form = choose_form(h);
+    bool form_ok[N_FORMS];
+    for (int f = 0; f < N_FORMS; ++f) form_ok[f] = h->form[f].ok;
+    const Form form = choose_form(form_ok, c, h->rp.active, h->cur_glist != nullptr);
     const int cap = iterations_per_launch(form);
     for (int64_t iter = iter0; iter < iter0 + n_iters; ++iter) {
         if (with_migration && migration_due_h(h, iter)) {  // main.jl:85
@@ -2677,16 +2257,16 @@ int32_t demc_last_kernels(demc_handle* h, char* out, int32_t nbytes) {
     const demc_handle::LastPlan& L = h->last;
     std::string s = L.k1 ? L.k1->name(L.k1->key) : "";
     switch (L.k2) {
-        case demc_handle::K2_NONE: break;
-        case demc_handle::K2_CROSS_MFMA: s += " + " + name_cross(L.k2_key); break;
-        case demc_handle::K2_DIRECT_MVN: s += " + " + name_direct(L.k2_key); break;
-        case demc_handle::K2_OBS: s += " + k_obs_loglike"; break;
-        case demc_handle::K2_LBA_WAVE: s += " + " + name_lba_wave(L.k2_key); break;
-        case demc_handle::K2_HIER: s += " + k_hier_loglike"; break;
-        case demc_handle::K2_USER: s += " + k_user_loglike"; break;
-        case demc_handle::K2_USER_ROW: s += " + k_user_row"; break;
-        case demc_handle::K2_SIM: s += " + " + name_sim(L.k2_key); break;
-        case demc_handle::K2_ODE: s += " + " + name_ode(L.k2_key); break;
+        case K2_NONE: break;
+        case K2_CROSS_MFMA: s += " + " + name_cross(L.k2_key); break;
+        case K2_DIRECT_MVN: s += " + " + name_direct(L.k2_key); break;
+        case K2_OBS: s += " + k_obs_loglike"; break;
+        case K2_LBA_WAVE: s += " + " + name_lba_wave(L.k2_key); break;
+        case K2_HIER: s += " + k_hier_loglike"; break;
+        case K2_USER: s += " + k_user_loglike"; break;
+        case K2_USER_ROW: s += " + k_user_row"; break;
+        case K2_SIM: s += " + " + name_sim(L.k2_key); break;
+        case K2_ODE: s += " + " + name_ode(L.k2_key); break;
     }
     if (L.k3) s += " + k_accept_store";
     std::snprintf(out, (size_t)nbytes, "%s", s.c_str());

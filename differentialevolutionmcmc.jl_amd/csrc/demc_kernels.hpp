@@ -20,14 +20,9 @@
 #pragma once
 #include <type_traits>
 #include "demc_device.hpp"
+#include "demc_constants.hpp"  // Family, Mode, K1Tail, kFrozenMax, kMaxDynLds: shared with the host-only launch geometry
 
 namespace demc {
-
-enum Family : int {
-    FAM_GAUSSIAN = 0, FAM_MVN_ISO = 1, FAM_MVN_FULL = 2, FAM_BINOMIAL = 3, FAM_HIER_BINOMIAL = 4,
-    FAM_HIER_GAUSSIAN = 5, FAM_LBA = 6, FAM_LNR = 7, FAM_RASTRIGIN = 8, FAM_USER = 100
-};
-enum Mode : int { MODE_STEP = 0, MODE_IDENT = 1 };  // IDENT: theta' = theta, always accepted (init / logpost)
 
 // DimTab, DimSeg, kMaxDimSeg, kMaxMaskRun: demc_dimtab.hpp (through demc_device.hpp)
 
@@ -879,7 +874,6 @@ __device__ inline unsigned long long load_granule(const unsigned long long* g) {
 
 // TAIL selects the fused tail compiled into the instance (the host passes the matching flags in KParams): registers
 // are allocated for the worst path of a kernel, so the tails a model cannot take are kept out of its instance.
-enum K1Tail : int { TAIL_NONE = 0, TAIL_PREP = 1, TAIL_PREP_MFMA = 2, TAIL_OBS = 3 };
 // RES = resident form: ONE workgroup of WG threads owns a group, copies all of its rows and weights into LDS once, and then
 // runs both colour phases of p.n_iters iterations (x p.n_sweeps block sweeps) without leaving the kernel: accepted rows are
 // written to the LDS copy and through to HBM, a workgroup barrier separates the phases.  Groups never interact inside

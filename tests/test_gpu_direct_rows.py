@@ -38,7 +38,7 @@ def kernel_of(d):
 # gridDim.x = 3 is no power of two, which the re-map's j / gridDim.x and j % gridDim.x have not seen before.
 # The chunk cap is min(N / 64, 64), at least 1.  Three blocks x at most 16 chunks are fewer workgroups than one round of resident
 # workgroups on any MI355X (256 CUs), so every admissible count fills the last round equally badly and chunks_filling_rounds
-# (csrc/demc_hip.cpp) returns the cap itself:
+# (csrc/demc_geometry.hpp) returns the cap itself:
 #   N = 1, 63: one chunk shorter than 64 rows;  129: chunks of 65 and 64;  575: 8 chunks of 72 rows, the last of 71, on the
 #   re-mapped branch ((n_chunks & 7) == 0);  1030: 16 chunks of 65 rows, the last of 55, re-mapped.
 LOGPOST_N = [1, 63, 129, 575, 1030]

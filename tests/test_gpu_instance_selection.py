@@ -1,6 +1,6 @@
 """Which kernel instance the runtime picks, by name only: the selector branches that the production and edge-case tests do not
 reach.  Every case builds a tiny engine (2 groups, 64 observations), runs two iterations and compares `last_kernels()` with a
-string written out here, derived by hand from the selection rules of csrc/demc_hip.cpp:
+string written out here, derived by hand from the selection rules of csrc/demc_geometry.hpp:
 
   * workgroup: 256 threads, 512 when the moving half of a group at four lanes a particle needs more, (Np - Np/2) * 4 > 256 --
     Np = 130 is the smallest such group -- or when a particle takes 512 lanes (D >= 4096);

@@ -13,7 +13,7 @@ span loop over a non-plain segment, or turned -Inf - (-Inf) into an accepted mov
 
 Every case is a free run of both engines through test_gpu_production.free_run with that helper's bars: particle ids and accept
 flags bit for bit, theta bit for bit at beta = 0 and to 1e-10 otherwise, log-posteriors to rtol 1e-9 in every
-case.  The instance each case ran is asserted by name; the names were derived by hand from plan_lean / launch_phase / choose_form (csrc/demc_hip.cpp) and are written into the case list.
+case.  The instance each case ran is asserted by name; the names were derived by hand from plan_lean / plan_phase / choose_form (csrc/demc_geometry.hpp) and are written into the case list.
 
 The cases, their tables and shapes live in tests/test_prior_tables_host.py (CASES), which shows on the CPU that each of them
 is evidence: the prior under test changes decisions, the run accepts, the bounds said to bite do.
