@@ -850,6 +850,11 @@ static int32_t select_particle_stable(const double* w, int32_t n, double u) {
     return r;
 }
 
+/* the two stabilised picks as the engines run them, exported for the tests that hold them to the exact rule
+ * (tests/weighted_pick_cases.py) */
+int32_t orc_select_base(const double* w, int32_t n, double u) { return select_base_stable(w, n, u); }
+int32_t orc_select_particle(const double* w, int32_t n, double u) { return select_particle_stable(w, n, u); }
+
 /* samplepair (StatsBase, recalled): i1 = rand(1:m); i2 = rand(1:m-1); i2 == i1 ? m : i2    */
 static inline void pick_pair(uint32_t r0, uint32_t r1, uint32_t m, uint32_t* i1, uint32_t* i2) {
     *i1 = mulhi32(r0, m);

@@ -109,6 +109,8 @@ def lib():
         L.orc_adjust_loglike.restype = C.c_double
         L.orc_select_base_ref.argtypes = [_dp, C.c_int32, C.c_double]
         L.orc_select_particle_ref.argtypes = [_dp, C.c_int32, C.c_double]
+        L.orc_select_base.argtypes = [_dp, C.c_int32, C.c_double]
+        L.orc_select_particle.argtypes = [_dp, C.c_int32, C.c_double]
         L.orc_philox4x32_10.argtypes = [_up, _up, _up]
         L.orc_u53.argtypes = [C.c_uint32, C.c_uint32]
         L.orc_u53.restype = C.c_double

@@ -677,9 +677,74 @@ void check_choose_form() {
     CHECK(iterations_per_launch(FORM_RESIDENT) == 1024 && iterations_per_launch(FORM_LEAN_SUFFSTAT) == 1024 && iterations_per_launch(FORM_LEAN_OBS) == 1024);
 }
 
+// ---- the pool of the weighted pick ------------------------------------------------------------------------------------------------
+
+// select_base's cumulative weights: k_res_obs, k_res_mvn and k_frozen_sweep keep them in ONE wave's registers (wave_cdf<1 / 2 / 4>:
+// 64 lanes x 4) and count the entries below t over sixteen chunks of 16 -- neither has a form for a pool beyond 256 entries.
+// Brute force over every group size up to 1024: no plan hands one of them such a pool (two_colour: the larger colour, Np - Np / 2;
+// the DE-MC_Z body and a synchronous frozen sweep: the whole group), and each reaches the largest pool its rule admits.
+void check_pick_pools() {
+    const int three[kMaxMaskRun] = {0, 3}, long_run[kMaxMaskRun] = {0, 2, 302};
+    int most_obs = 0, most_two_colour = 0, most_z = 0, most_frozen = 0, first_longrow = 0;
+    for (int Np = 4; Np <= 1024; ++Np) {
+        const int colour = Np - Np / 2;
+        {
+            Case k = gaussian(2, Np, DEMC_SCHED_TWO_COLOUR, DEMC_PARTNER_CURRENT);
+            if (plan_lean(k.size(), true, StreamDims(), 3770).form[FORM_LEAN_OBS].ok) {
+                CHECK(colour <= 256);
+                most_obs = std::max(most_obs, colour);
+            }
+        }
+        for (int d : {5, 8, 32})
+            for (int mode : {DEMC_LOGLIKE_SUFFSTAT, DEMC_LOGLIKE_STREAMING, DEMC_LOGLIKE_DIRECT}) {
+                Case k = mvn_full(d, 2, Np, DEMC_SCHED_TWO_COLOUR, DEMC_PARTNER_CURRENT, mode, mode == DEMC_LOGLIKE_SUFFSTAT ? 64 : 4096);
+                k.size();
+                const LeanPlan lean = plan_lean(k.s, true, plan_stream(k.s).dims, 3770);
+                for (int f : {FORM_LEAN_SUFFSTAT, FORM_LEAN_STREAMING, FORM_LEAN_DIRECT})
+                    if (lean.form[f].ok) {
+                        CHECK(colour <= 256);
+                        most_two_colour = std::max(most_two_colour, colour);
+                    }
+                Case z = mvn_full(d, 2, Np, DEMC_SCHED_SYNCHRONOUS, DEMC_PARTNER_HISTORY, mode);
+                if (plan_lean(z.size(), true, StreamDims(), 3770).form[FORM_LEAN_Z].ok) {
+                    CHECK(Np <= 256);
+                    most_z = std::max(most_z, Np);
+                }
+            }
+        for (int sched : {DEMC_SCHED_SYNCHRONOUS, DEMC_SCHED_TWO_COLOUR}) {
+            Case k = hier_binomial(4094, 1024, Np, sched, sched == DEMC_SCHED_SYNCHRONOUS ? DEMC_PARTNER_HISTORY : DEMC_PARTNER_CURRENT);
+            k.c.n_blocks = 1;
+            k.size();
+            for (int ph = 0; ph < (sched == DEMC_SCHED_TWO_COLOUR ? 2 : 1); ++ph)
+                for (int big = 0; big < 2; ++big) {
+                    Phase p = big ? block_phase(k, long_run, 3, 2u) : block_phase(k, three, 2, 1u);
+                    if (sched == DEMC_SCHED_TWO_COLOUR) {
+                        p.a_lo = ph ? Np / 2 : 0; p.n_act = ph ? colour : Np / 2;
+                        p.pool_lo = ph ? 0 : Np / 2; p.pool_n = ph ? Np / 2 : colour;
+                    }
+                    const PhasePlan pl = plan_phase(k.s, p, fit_yes);
+                    CHECK(pl.kernel == K1_FROZEN || pl.kernel == K1_LONGROW);
+                    if (pl.kernel == K1_FROZEN) {
+                        CHECK(p.pool_n <= 256 && pl.big == (big != 0));
+                        most_frozen = std::max(most_frozen, p.pool_n);
+                    } else {
+                        CHECK(p.pool_n > 256);  // (nothing else keeps this configuration from the frozen sweep)
+                        if (!first_longrow) first_longrow = p.pool_n;
+                        CHECK(pl.lds == (4096 + (size_t)p.pool_n + ((size_t)p.pool_n + 15) / 16) * sizeof(double));  // (its LDS form)
+                    }
+                }
+        }
+    }
+    CHECK(most_obs == 256);         // Np = 511 and 512
+    CHECK(most_two_colour == 128);  // four lanes a particle on at most 512 threads
+    CHECK(most_z == 256);           // ... of which the DE-MC_Z body's pool is the whole group
+    CHECK(most_frozen == 256 && first_longrow == 257);
+}
+
 }  // namespace
 
 int main() {
+    check_pick_pools();
     check_chunks();
     check_lanes();
     check_workgroups();
