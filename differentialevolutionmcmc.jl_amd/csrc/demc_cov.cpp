@@ -3,13 +3,8 @@
 #define DEMC_COV_KERNELS
 #include "demc_cov.hpp"
 
-#include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
-
 #include "../../include/demc.h"
-#include "demc_devmem.hpp"  // Scratch, Event
+#include "demc_devmem.hpp"  // Scratch, PassTrace, finish
 
 namespace demc {
 
@@ -22,66 +17,42 @@ void launch_syrk(const CovKParams& p, hipStream_t st) {
 
 }  // namespace
 
-int cov_run(const CovArgs& a, hipStream_t st, const int* cols, int K, double* mean_out, double* cov_out, double* cor_out, std::string& err) {
-    const long long N = (a.row1 - a.row0) * a.P;
-    // geometry (demc_cov.hpp): a chunk is kCovChunk cells, worker b takes the chunks b, b + W, ...
-    const long long chunks = (N + kCovChunk - 1) / kCovChunk;
-    const int NB = (K + 15) / 16;
-
+int cov_run(const HistView& v, const CovPlan& plan, hipStream_t st, double* mean_out, double* cov_out, double* cor_out, std::string& err) {
+    const char* who = "demc_covariance";
+    const int K = plan.K;
     CovKParams p{};
-    p.hist = a.hist + (size_t)a.row0 * a.P * a.ld;
-    p.acc = a.acc + (size_t)a.row0 * a.P;
-    p.lp = a.lp + (size_t)a.row0 * a.P;
-    p.N = N; p.D = a.D; p.ld = a.ld; p.K = K;
-    p.W = (int)std::min<long long>(chunks, kCovMaxWorkers);
-    int table[kCovMaxCols];
-    for (int k = 0; k < kCovMaxCols; ++k) table[k] = k < K ? cols[k] : -1;
+    p.hist = v.hist + (size_t)v.row0 * v.P * v.ld;
+    p.acc = v.acc + (size_t)v.row0 * v.P;
+    p.lp = v.lp + (size_t)v.row0 * v.P;
+    p.N = (v.row1 - v.row0) * v.P; p.D = v.D; p.ld = v.ld; p.K = K;
+    p.W = plan.W;
     Scratch s;
     int* d_cols = nullptr;
-    if (!(s.get(&d_cols, (size_t)kCovMaxCols) && s.get(&p.part1, (size_t)p.W * kCovMaxCols) && s.get(&p.mhat, (size_t)kCovMaxCols) &&
-          s.get(&p.part2, (size_t)p.W * cov_partial(NB)) && s.get(&p.mean, (size_t)K) && s.get(&p.cov, (size_t)K * K) &&
-          s.get(&p.cor, (size_t)K * K))) {
+    if (!(s.get(&d_cols, plan.n_cols) && s.get(&p.part1, plan.n_part1) && s.get(&p.mhat, plan.n_mhat) && s.get(&p.part2, plan.n_part2) &&
+          s.get(&p.mean, plan.n_mean) && s.get(&p.cov, plan.n_mat) && s.get(&p.cor, plan.n_mat))) {
         err = "demc_covariance: out of device memory for the scratch buffers";
         return DEMC_ENOMEM;
     }
     p.cols = d_cols;
-    hipError_t e = hipMemcpyAsync(d_cols, table, sizeof table, hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) { err = std::string("demc_covariance: ") + hipGetErrorString(e); return DEMC_EHIP; }
-    const char* tr = std::getenv("DEMC_COV_TRACE");  // DEMC_COV_TRACE=1: device time of the passes, printed to stderr (tools/cov_bench.py)
-    const bool trace = tr && tr[0] == '1';
-    std::vector<Event> ev;
-    auto mark = [&]() {
-        if (!trace) return true;
-        Event x;
-        if (x.create(hipEventDefault) != hipSuccess) return false;
-        ev.push_back(std::move(x));
-        return hipEventRecord(ev.back(), st) == hipSuccess;
-    };
-    bool ok = mark();
+    if (!hip_ok(who, hipMemcpyAsync(d_cols, plan.table, sizeof plan.table, hipMemcpyHostToDevice, st), err)) return DEMC_EHIP;
+    PassTrace tr;  // (the diagnostic variant: device time of the three passes)
+    bool ok = tr.mark(st);
     hipLaunchKernelGGL(k_cov_mean, dim3((unsigned)p.W), dim3(kCovWG), 0, st, p);
     hipLaunchKernelGGL(k_cov_mean_final, dim3(1), dim3(kCovMaxCols), 0, st, p);
-    ok = ok && mark();
-    switch (NB) {
+    ok = ok && tr.mark(st);
+    switch (plan.NB) {
         case 1: launch_syrk<1>(p, st); break;
         case 2: launch_syrk<2>(p, st); break;
         case 3: launch_syrk<3>(p, st); break;
         default: launch_syrk<4>(p, st); break;
     }
-    ok = ok && mark();
+    ok = ok && tr.mark(st);
     hipLaunchKernelGGL(k_cov_final, dim3(1), dim3(kCovFinalWG), 0, st, p);
-    ok = ok && mark();
+    ok = ok && tr.mark(st);
     if (!ok) { err = "demc_covariance: an event could not be recorded"; return DEMC_EHIP; }
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e == hipSuccess && mean_out) e = hipMemcpy(mean_out, p.mean, (size_t)K * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && cov_out) e = hipMemcpy(cov_out, p.cov, (size_t)K * K * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && cor_out) e = hipMemcpy(cor_out, p.cor, (size_t)K * K * sizeof(double), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) { err = std::string("demc_covariance: ") + hipGetErrorString(e); return DEMC_EHIP; }
-    if (trace) {
-        float ms[3] = {0.f, 0.f, 0.f};
-        for (int i = 0; i < 3; ++i) (void)hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]);
-        std::fprintf(stderr, "demc_covariance pass_ms %.4f %.4f %.4f\n", ms[0], ms[1], ms[2]);
-    }
+    const size_t mat = plan.n_mat * sizeof(double);
+    if (!finish(who, st, {{mean_out, p.mean, plan.n_mean * sizeof(double)}, {cov_out, p.cov, mat}, {cor_out, p.cor, mat}}, err)) return DEMC_EHIP;
+    tr.print(who, 3, 1);
     return DEMC_OK;
 }
 

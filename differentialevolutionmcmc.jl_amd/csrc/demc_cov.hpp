@@ -30,16 +30,9 @@
 #include <cstdint>
 #include <string>
 
+#include "demc_postplan.hpp"  // host-only: the kCov* constants, cov_tiles, cov_partial, HistView, CovPlan
+
 namespace demc {
-
-constexpr int kCovMaxCols = 64;       // DEMC_COV_MAX_COLS: four blocks of 16 columns
-constexpr int kCovWG = 512;           // threads of k_cov_mean and k_cov_syrk: 8 waves
-constexpr int kCovChunk = 512;        // cells of a chunk: 128 k-steps, 16 per wave
-constexpr int kCovMaxWorkers = 512;   // workgroups of a pass: two per CU
-constexpr int kCovFinalWG = 1024;     // threads of k_cov_final
-
-constexpr int cov_tiles(int nb) { return nb * (nb + 1) / 2; }
-constexpr int cov_partial(int nb) { return cov_tiles(nb) * 256 + nb * 16; }  // doubles a worker writes in pass 2
 
 struct CovKParams {
     const double* hist;          // at row row0: [N][ld]
@@ -56,17 +49,8 @@ struct CovKParams {
     double* cor;                 // [K][K]
 };
 
-struct CovArgs {
-    const double* hist;
-    const unsigned char* acc;
-    const double* lp;
-    long long P, row0, row1;
-    int D, ld;
-};
-
-// host: the whole of demc_covariance behind its argument checks, on `stream`; cols[K] are valid, distinct series; 0 or a DEMC_*
-// code with a message
-int cov_run(const CovArgs& a, hipStream_t stream, const int* cols, int K, double* mean_out, double* cov_out, double* cor_out, std::string& err);
+// host: what plan_cov planned for the rows of `v`, on `stream`; 0 or a DEMC_* code with a message
+int cov_run(const HistView& v, const CovPlan& plan, hipStream_t stream, double* mean_out, double* cov_out, double* cor_out, std::string& err);
 
 #ifdef DEMC_COV_KERNELS  // (demc_cov.cpp only: the runtime's unit sees the declarations above and no device code)
 typedef double cov_d4 __attribute__((ext_vector_type(4)));  // C/D fragment of v_mfma_f64_16x16x4_f64

@@ -1,4 +1,6 @@
-// demc_devmem.hpp -- move-only owners of the HIP resources the host runtime holds.  Host code only: no kernel, no device function.
+// demc_devmem.hpp -- move-only owners of the HIP resources the host runtime holds, and on top of them the two things every
+// posterior-statistics call does alike: its end (finish) and the timing of its passes (PassTrace).  Host code only: no kernel, no
+// device function.
 //
 // Each owner holds one resource and releases it exactly once: in its destructor, in reset(), or when another owner is moved
 // over it.  A record of owners (the handle's Model, its Replay) is therefore released by assigning a fresh record over it, and
@@ -9,6 +11,9 @@
 #include <hip/hip_runtime_api.h>
 
 #include <cstddef>
+#include <cstdio>
+#include <initializer_list>
+#include <string>
 #include <utility>
 #include <vector>
 
@@ -80,6 +85,50 @@ struct Scratch {  // device allocations of one call, freed however it ends
         bufs.push_back(std::move(b));
         return true;
     }
+};
+
+// How a call that has launched its kernels ends: their launch errors, the stream, then the copies to the host in order (a null
+// dst was not asked for).  false: `err` is "<who>: <hip error>".
+struct Download { void* dst; const void* src; size_t bytes; };
+inline bool hip_ok(const char* who, hipError_t e, std::string& err) {
+    if (e != hipSuccess) err = std::string(who) + ": " + hipGetErrorString(e);
+    return e == hipSuccess;
+}
+inline bool finish(const char* who, hipStream_t st, std::initializer_list<Download> copies, std::string& err) {
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    for (const Download& c : copies)
+        if (e == hipSuccess && c.dst) e = hipMemcpy(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost);
+    return hip_ok(who, e, err);
+}
+
+// Device time of the passes of a call, between marks on its stream.  Only the diagnostic variant of the library measures
+// (make TRACE=1: -DDEMC_PASS_TRACE; tools/quantile_bench.py, tools/cov_bench.py); in the product both calls are empty.
+struct PassTrace {
+#ifdef DEMC_PASS_TRACE
+    std::vector<Event> ev;
+    bool mark(hipStream_t st) {
+        Event e;
+        if (e.create(hipEventDefault) != hipSuccess) return false;
+        ev.push_back(std::move(e));
+        return hipEventRecord(ev.back(), st) == hipSuccess;
+    }
+    // "<who> pass_ms a b ..." to stderr: pass i ran from mark i * stride to the one after it (the stream has been waited for)
+    void print(const char* who, int passes, int stride) const {
+        std::string line = std::string(who) + " pass_ms";
+        for (int i = 0; i < passes; ++i) {
+            float ms = 0.f;
+            (void)hipEventElapsedTime(&ms, ev[(size_t)i * stride], ev[(size_t)i * stride + 1]);
+            char buf[32];
+            std::snprintf(buf, sizeof buf, " %.4f", ms);
+            line += buf;
+        }
+        std::fprintf(stderr, "%s\n", line.c_str());
+    }
+#else
+    bool mark(hipStream_t) { return true; }
+    void print(const char*, int, int) const {}
+#endif
 };
 
 }  // namespace demc

@@ -53,6 +53,7 @@
 #include "demc_prep.hpp"  // host-only: a model's data and constants, the prior table and its run-length forms, every refusal of those
 #include "demc_instances.hpp"  // one table per templated kernel, built from the lists above: every choice of an instance goes through them
 #include "demc_geometry.hpp"  // host-only: every launch-geometry decision, as plans the launches below carry out
+#include "demc_postplan.hpp"  // host-only: the history window and the plans of demc_summarize, demc_quantiles, demc_covariance
 
 using namespace demc;
 
@@ -1047,12 +1048,8 @@ int32_t demc_create(const demc_config* cfg, demc_handle** out) {
     ALLOC(h->mig_rows, (size_t)c.n_groups_total * (D + 3));
     ALLOC(h->scratch_theta, P * D); ALLOC(h->scratch_w, P);
     if (c.store_history && c.n_rows > 0) {
-        // History cells that partners are GATHERED from (DE-MC_Z: `resample`, crossover.jl:113-124) are padded to whole cache lines --
-        // rows of up to 16 scalars to the next power of two, up to 64 to the next multiple of 16 doubles: a cell of 31 doubles at an
-        // 8-byte boundary touches 2.9 lines of 128 bytes on average (376 B fetched for 248), at a 256-byte boundary exactly two.  Only
-        // then: a history that is only written (partners from the population) stays dense -- padded cells would be partial-line stores.
-        h->hist_ld = (int)D;
-        if (c.partner_kind == DEMC_PARTNER_HISTORY && D <= 64) h->hist_ld = D <= 16 ? pow2_ceil((int)D) : (int)((D + 15) & ~(size_t)15);
+        // (cells that partners are gathered from are padded to whole cache lines: history_cell_stride)
+        h->hist_ld = history_cell_stride(D, c.partner_kind);
         ALLOC(h->hist, (size_t)c.n_rows * P * (size_t)h->hist_ld);
         ALLOC(h->acc_hist, (size_t)c.n_rows * P);
         ALLOC(h->lp_hist, (size_t)c.n_rows * P);
@@ -1318,7 +1315,7 @@ int32_t demc_set_history_rows(demc_handle* h, int64_t row0, int64_t nrows, const
     return guarded(h, [&]() -> int32_t {
     if (!h || !rows) return DEMC_EINVAL;
     USE_DEVICE(h);
-    if (!h->hist) return fail(h, DEMC_EINVAL, "history is not stored on this handle");
+    if (!h->hist) return fail(h, DEMC_EINVAL, kHistoryNotStored);
     if (row0 < 0 || nrows < 0 || row0 + nrows > h->c.n_rows) return fail(h, DEMC_EINVAL, "history rows out of range");
     const size_t D = (size_t)h->c.D, ld = (size_t)h->hist_ld, P = (size_t)h->P;
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -1327,7 +1324,7 @@ int32_t demc_set_history_rows(demc_handle* h, int64_t row0, int64_t nrows, const
         return DEMC_OK;
     }
     // padded cells: the caller's dense rows go through a device staging buffer, a few rows at a time
-    const size_t chunk = std::max<size_t>(1, ((size_t)64 << 20) / (P * D * sizeof(double)));
+    const size_t chunk = history_stage_rows(P, D);
     DevBuf<double> stage;
     ALLOC(stage, std::min<size_t>(chunk, (size_t)nrows) * P * D);
     for (size_t r = 0; r < (size_t)nrows; r += chunk) {
@@ -1345,14 +1342,14 @@ int32_t demc_get_history(demc_handle* h, int64_t row0, int64_t row1, double* th,
     return guarded(h, [&]() -> int32_t {
     if (!h) return DEMC_EINVAL;
     USE_DEVICE(h);
-    if (!h->hist) return fail(h, DEMC_EINVAL, "history is not stored on this handle");
+    if (!h->hist) return fail(h, DEMC_EINVAL, kHistoryNotStored);
     if (row0 < 0 || row1 < row0 || row1 > h->c.n_rows) return fail(h, DEMC_EINVAL, "history rows out of range");
     const size_t P = (size_t)h->P, D = (size_t)h->c.D, n = (size_t)(row1 - row0);
     HIPCHK(hipStreamSynchronize(h->stream));
     const size_t ld = (size_t)h->hist_ld;
     if (th && ld == D) HIPCHK(hipMemcpy(th, h->hist + (size_t)row0 * P * D, n * P * D * sizeof(double), hipMemcpyDeviceToHost));
     else if (th && n > 0) {  // padded cells: packed into a dense staging buffer on the device, a few rows at a time
-        const size_t chunk = std::max<size_t>(1, ((size_t)64 << 20) / (P * D * sizeof(double)));
+        const size_t chunk = history_stage_rows(P, D);
         DevBuf<double> stage;
         ALLOC(stage, std::min(chunk, n) * P * D);
         for (size_t r = 0; r < n; r += chunk) {
@@ -1378,7 +1375,7 @@ int32_t demc_export_chains(demc_handle* h, int64_t row0, int64_t row1, int32_t l
     return guarded(h, [&]() -> int32_t {
     if (!h || !out) return DEMC_EINVAL;
     USE_DEVICE(h);
-    if (!h->hist) return fail(h, DEMC_EINVAL, "history is not stored on this handle");
+    if (!h->hist) return fail(h, DEMC_EINVAL, kHistoryNotStored);
     if (row0 < 0 || row1 < row0 || row1 > h->c.n_rows || (layout != 0 && layout != 1)) return fail(h, DEMC_EINVAL, "bad rows / layout");
     if (h->c.n_groups_total != h->c.n_groups)
         return fail(h, DEMC_EINVAL, "sharded handle: gather demc_get_history from every rank and re-key on the host");
@@ -1399,18 +1396,27 @@ int32_t demc_export_chains(demc_handle* h, int64_t row0, int64_t row1, int32_t l
     });
 }
 
+// The three posterior-statistics calls: the shape of the call, the history window, the plan (demc_postplan.hpp), the run.  What a
+// call has against its own arguments ranks between the row window and the sharded handle, so check_probs / select_columns are
+// asked once here for that order and once more by the planner, which is total.
+static HistView hist_view(const demc_handle* h, int64_t row0, int64_t row1) {
+    return HistView{h->hist, h->acc_hist, h->lp_hist, h->id_hist, h->P, (long long)row0, (long long)row1, (long long)h->c.group_offset * h->c.Np,
+                    h->c.D, h->hist_ld};
+}
+static Refusal check_window(const demc_handle* h, PostCall call, int64_t row0, int64_t row1, Refusal args = Refusal()) {
+    return check_history_window(call, h->hist != nullptr, row0, row1, h->c.n_rows, h->c.n_groups_total != h->c.n_groups, std::move(args));
+}
+
 int32_t demc_summarize(demc_handle* h, int64_t row0, int64_t row1, int32_t max_lag, double* out, double* rho_out, int64_t rho_len) {
     return guarded(h, [&]() -> int32_t {
     if (!h || !out || rho_len < 0 || max_lag < 0) return DEMC_EINVAL;
     USE_DEVICE(h);
-    if (!h->hist) return fail(h, DEMC_EINVAL, "history is not stored on this handle");
-    if (row0 < 0 || row1 - row0 < 1 || row1 > h->c.n_rows) return fail(h, DEMC_EINVAL, "bad rows: demc_summarize needs at least one row of the history");
-    if (h->c.n_groups_total != h->c.n_groups)
-        return fail(h, DEMC_EINVAL, "sharded handle: gather demc_get_history from every rank and summarise on the host");
-    SumArgs a{h->hist, h->acc_hist, h->lp_hist, h->id_hist, h->P, (long long)row0, (long long)row1, (long long)h->c.group_offset * h->c.Np,
-              h->c.D, h->hist_ld, (int)max_lag};
+    if (Refusal r = check_window(h, POST_SUMMARIZE, row0, row1)) return fail(h, r);
+    if (!(rho_out && rho_len > 0)) rho_out = nullptr;
+    const SummaryPlan plan = plan_summary(row1 - row0, h->P, h->c.D, (int)max_lag, (long long)rho_len, rho_out != nullptr);
+    if (plan.refused) return fail(h, plan.refused);
     std::string msg;
-    const int rc = summary_run(a, h->stream, out, rho_out && rho_len > 0 ? rho_out : nullptr, (long long)rho_len, msg);
+    const int rc = summary_run(hist_view(h, row0, row1), plan, h->stream, out, rho_out, (long long)rho_len, msg);
     return rc == DEMC_OK ? DEMC_OK : fail(h, rc, msg);
     });
 }
@@ -1419,16 +1425,11 @@ int32_t demc_quantiles(demc_handle* h, int64_t row0, int64_t row1, const double*
     return guarded(h, [&]() -> int32_t {
     if (!h || !out || !probs) return DEMC_EINVAL;
     USE_DEVICE(h);
-    if (!h->hist) return fail(h, DEMC_EINVAL, "history is not stored on this handle");
-    if (row0 < 0 || row1 - row0 < 1 || row1 > h->c.n_rows) return fail(h, DEMC_EINVAL, "bad rows: demc_quantiles needs at least one row of the history");
-    if (n_probs < 1 || n_probs > DEMC_QUANTILE_MAX_PROBS) return fail(h, DEMC_EINVAL, "demc_quantiles: n_probs must be in 1 .. 16");
-    for (int k = 0; k < n_probs; ++k)
-        if (!(probs[k] >= 0.0 && probs[k] <= 1.0)) return fail(h, DEMC_EINVAL, "demc_quantiles: a prob is outside [0, 1]");
-    if (h->c.n_groups_total != h->c.n_groups)
-        return fail(h, DEMC_EINVAL, "sharded handle: gather demc_get_history from every rank and take the quantiles on the host");
-    QArgs a{h->hist, h->acc_hist, h->lp_hist, h->P, (long long)row0, (long long)row1, h->c.D, h->hist_ld};
+    if (Refusal r = check_window(h, POST_QUANTILES, row0, row1, check_probs(probs, (int)n_probs))) return fail(h, r);
+    const QuantilePlan plan = plan_quantiles((row1 - row0) * h->P, h->c.D, h->hist_ld, probs, (int)n_probs);
+    if (plan.refused) return fail(h, plan.refused);
     std::string msg;
-    const int rc = quantile_run(a, h->stream, probs, (int)n_probs, out, msg);
+    const int rc = quantile_run(hist_view(h, row0, row1), plan, h->stream, out, msg);
     return rc == DEMC_OK ? DEMC_OK : fail(h, rc, msg);
     });
 }
@@ -1439,23 +1440,12 @@ int32_t demc_covariance(demc_handle* h, int64_t row0, int64_t row1, const int32_
     if (!h) return DEMC_EINVAL;
     USE_DEVICE(h);
     if (!mean_out && !cov_out && !cor_out) return fail(h, DEMC_EINVAL, "demc_covariance: mean_out, cov_out and cor_out are all NULL");
-    if (!h->hist) return fail(h, DEMC_EINVAL, "history is not stored on this handle");
-    if (row0 < 0 || row1 - row0 < 1 || row1 > h->c.n_rows) return fail(h, DEMC_EINVAL, "bad rows: demc_covariance needs at least one row of the history");
-    if (n_cols < 1 || n_cols > DEMC_COV_MAX_COLS) return fail(h, DEMC_EINVAL, "demc_covariance: n_cols must be in 1 .. 64");
-    const int D2 = h->c.D + 2;
-    if (!cols && n_cols != D2) return fail(h, DEMC_EINVAL, "demc_covariance: cols == NULL selects all D + 2 series: n_cols must equal D + 2 (at most 64)");
-    int sel[DEMC_COV_MAX_COLS];
-    for (int k = 0; k < n_cols; ++k) {
-        sel[k] = cols ? (int)cols[k] : k;
-        if (sel[k] < 0 || sel[k] >= D2) return fail(h, DEMC_EINVAL, "demc_covariance: a column is outside [0, D + 2)");
-        for (int j = 0; j < k; ++j)
-            if (sel[j] == sel[k]) return fail(h, DEMC_EINVAL, "demc_covariance: a column is repeated");
-    }
-    if (h->c.n_groups_total != h->c.n_groups)
-        return fail(h, DEMC_EINVAL, "sharded handle: gather demc_get_history from every rank and take the covariance on the host");
-    CovArgs a{h->hist, h->acc_hist, h->lp_hist, h->P, (long long)row0, (long long)row1, h->c.D, h->hist_ld};
+    int sel[kCovMaxCols];
+    if (Refusal r = check_window(h, POST_COVARIANCE, row0, row1, select_columns(h->c.D, cols, (int)n_cols, sel))) return fail(h, r);
+    const CovPlan plan = plan_cov((row1 - row0) * h->P, h->c.D, cols, (int)n_cols);
+    if (plan.refused) return fail(h, plan.refused);
     std::string msg;
-    const int rc = cov_run(a, h->stream, sel, (int)n_cols, mean_out, cov_out, cor_out, msg);
+    const int rc = cov_run(hist_view(h, row0, row1), plan, h->stream, mean_out, cov_out, cor_out, msg);
     return rc == DEMC_OK ? DEMC_OK : fail(h, rc, msg);
     });
 }

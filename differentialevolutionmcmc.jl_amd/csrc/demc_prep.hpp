@@ -16,26 +16,14 @@
 #include <vector>
 
 #include "demc_dimtab.hpp"
+#include "demc_hostbase.hpp"  // Refusal, pow2_ceil
 
 namespace demc {
-
-// Why a call is refused: the status code and the message demc_last_error returns.  DEMC_OK: not refused.
-struct Refusal {
-    int code = DEMC_OK;
-    std::string message;
-    explicit operator bool() const { return code != DEMC_OK; }
-};
 
 // The caps the refusals quote.  The kernels' own constants (demc_ode.hpp, demc_simlike.hpp) sit behind the device headers;
 // the runtime asserts that the two agree.
 constexpr int kPrepOdeMaxT = 4096, kPrepOdeMaxSubsteps = 1024;
 constexpr int kPrepSimMaxN = 16384, kPrepSimChoiceMaxN = 15000;
-
-inline int pow2_ceil(int x) {
-    int p = 1;
-    while (p < x) p <<= 1;
-    return p;
-}
 
 // Sigma = L L' (row-major, d x d): Ainv = Sigma^-1, logdet = log det Sigma, Linv = L^-1.  false: Sigma is not positive definite.
 inline bool chol_inv(const double* S, int d, std::vector<double>& Ainv, double& logdet, std::vector<double>* Linv = nullptr) {

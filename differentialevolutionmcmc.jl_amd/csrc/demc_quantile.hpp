@@ -41,15 +41,9 @@
 #include <cstdint>
 #include <string>
 
-namespace demc {
+#include "demc_postplan.hpp"  // host-only: the kQ* constants, QTargets, HistView, QuantilePlan
 
-constexpr int kQBits = 8;                 // bits per digit: 256 bins, 8 passes
-constexpr int kQWG = 512;                 // threads of k_q_hist
-constexpr int kQMaxWG = 512;              // workgroups of k_q_hist: two per CU, all resident
-constexpr int kQSlots = 64;               // LDS tables of 256 32-bit counts (64 KiB); a launch uses a power of two of them
-constexpr int kQProbes = 4;               // slots a group looks at before it counts in the global table
-constexpr int kQMaxTargets = 32;          // two ranks per prob (DEMC_QUANTILE_MAX_PROBS = 16)
-constexpr long long kQMaxChunksPerWG = 1LL << 22;  // * kQWG values < 2^32: the 32-bit counts cannot wrap
+namespace demc {
 
 struct QKParams {
     const double* hist;          // [n_rows][P][ld]
@@ -66,28 +60,10 @@ struct QKParams {
     double* out;                 // [D+2][n_probs]
 };
 
-struct QTargets {  // by value to k_q_init and k_q_final
-    unsigned long long rank[kQMaxTargets];  // 0-based, ascending, distinct
-    double gamma[kQMaxTargets / 2];
-    int ia[kQMaxTargets / 2], ib[kQMaxTargets / 2];  // targets of x_(j) and x_(j+1) of a prob; ia == ib: the pool has one value
-    int n_probs;
-};
-
-struct QArgs {
-    const double* hist;
-    const unsigned char* acc;
-    const double* lp;
-    long long P, row0, row1;
-    int D, ld;
-};
-
-// host: the whole of demc_quantiles behind its argument checks, on `stream`; 0 or a DEMC_* code with a message
-int quantile_run(const QArgs& a, hipStream_t stream, const double* probs, int n_probs, double* out, std::string& err);
+// host: what plan_quantiles planned for the rows of `v`, on `stream`; 0 or a DEMC_* code with a message
+int quantile_run(const HistView& v, const QuantilePlan& plan, hipStream_t stream, double* out, std::string& err);
 
 #ifdef DEMC_QUANTILE_KERNELS  // (demc_quantile.cpp only: the runtime's unit sees the declarations above and no device code)
-constexpr unsigned long long kQKeyNegInf = 0x000FFFFFFFFFFFFFull;  // k(-inf): keys below are NaNs with the sign set
-constexpr unsigned long long kQKeyPosInf = 0xFFF0000000000000ull;  // k(+inf): keys above are NaNs without it
-
 __device__ __forceinline__ unsigned long long q_key(double x) {
     const unsigned long long b = (unsigned long long)__double_as_longlong(x);
     return b ^ ((b >> 63) ? ~0ull : 1ull << 63);

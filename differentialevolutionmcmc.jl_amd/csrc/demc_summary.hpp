@@ -30,15 +30,9 @@
 #include <cstdint>
 #include <string>
 
-namespace demc {
+#include "demc_postplan.hpp"  // host-only: the kSum* constants, HistView, SummaryPlan
 
-constexpr int kSumLagBlock = 64;        // lags per pass = lanes of a wave (pairs never straddle a block)
-constexpr int kSumWG = 256;             // threads of the gathering kernels
-constexpr int kSumMaxJT = 8;            // series per tile: two per wave of the moments kernel
-constexpr int kSumMaxWorkers = 1024;    // chain workers: bounds partial[worker][D+2][64] (17.8 MB at D + 2 = 34)
-constexpr size_t kSumLdsSmall = 64 * 1024;   // preferred LDS per workgroup (two workgroups per CU)
-constexpr size_t kSumLdsMax = 144 * 1024;    // ... and the most one asks for: a single series of up to kSumLdsRows rows
-constexpr size_t kSumGlobalTile = (size_t)64 << 20;  // budget of the global staging tiles of series too long for LDS
+namespace demc {
 
 struct SumKParams {
     const double* hist;          // [n_rows][P][ld]
@@ -66,17 +60,8 @@ struct SumKParams {
     double* out;                 // [D+2][6]
 };
 
-struct SumArgs {
-    const double* hist;
-    const unsigned char* acc;
-    const double* lp;
-    const int* idh;
-    long long P, row0, row1, id0;
-    int D, ld, max_lag;
-};
-
-// host: the whole of demc_summarize behind its argument checks, on `stream`; 0 or a DEMC_* code with a message
-int summary_run(const SumArgs& a, hipStream_t stream, double* out, double* rho_out, long long rho_len, std::string& err);
+// host: what plan_summary planned for the rows of `v`, on `stream`; 0 or a DEMC_* code with a message
+int summary_run(const HistView& v, const SummaryPlan& plan, hipStream_t stream, double* out, double* rho_out, long long rho_len, std::string& err);
 
 #ifdef DEMC_SUMMARY_KERNELS  // (demc_summary.cpp only: the runtime's unit sees the declarations above and no device code)
 // ---- one pass over id_hist: inv[i][id - id0] = slot

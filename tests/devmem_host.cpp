@@ -1,7 +1,12 @@
 // devmem_host.cpp -- the owners of csrc/demc_devmem.hpp on the CPU: the HIP entry points the header calls are counting stubs over
 // malloc / free, so every create and every release is seen, and a release too many or too few is a miscount here and a
 // double free or a leak to the address sanitizer the program is built with (tests/test_devmem_host.py).  No HIP runtime is linked.
+// The end of a call (finish) and the pass timer of the diagnostic variant (PassTrace) run over stubs as well: a stream on which
+// nothing is pending, events that carry the time of their mark.
+#define DEMC_PASS_TRACE  // the variant that measures; without it PassTrace is two empty functions
 #include "demc_devmem.hpp"
+
+#include <cstring>
 
 #include <cstdio>
 #include <cstdlib>
@@ -10,6 +15,10 @@ namespace {
 enum Kind { DEV, PIN, EVT, MOD, N_KINDS };
 int made[N_KINDS], freed[N_KINDS];
 int dev_allocs_left = -1;  // hipMalloc fails once this many have succeeded (-1: never)
+hipError_t launch_error = hipSuccess, sync_error = hipSuccess;  // what hipGetLastError / hipStreamSynchronize answer
+int copies = 0, copies_left = -1;  // hipMemcpy fails once this many have succeeded (-1: never)
+int events_left = -1;              // likewise hipEventCreateWithFlags
+float now_ms = 0.f;                // the time an event records
 
 hipError_t make(Kind k, void** out, size_t bytes) {
     if (k == DEV && dev_allocs_left == 0) return hipErrorOutOfMemory;
@@ -30,7 +39,28 @@ hipError_t hipMalloc(void** p, size_t n) { return make(DEV, p, n); }
 hipError_t hipFree(void* p) { return release(DEV, p); }
 hipError_t hipHostMalloc(void** p, size_t n, unsigned) { return make(PIN, p, n); }
 hipError_t hipHostFree(void* p) { return release(PIN, p); }
-hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { return make(EVT, (void**)e, 1); }
+hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) {
+    if (events_left == 0) return hipErrorOutOfMemory;
+    if (events_left > 0) --events_left;
+    return make(EVT, (void**)e, sizeof(float));
+}
+hipError_t hipEventRecord(hipEvent_t e, hipStream_t) { std::memcpy((void*)e, &now_ms, sizeof now_ms); return hipSuccess; }
+hipError_t hipEventElapsedTime(float* ms, hipEvent_t a, hipEvent_t b) {
+    float ta, tb;
+    std::memcpy(&ta, (void*)a, sizeof ta); std::memcpy(&tb, (void*)b, sizeof tb);
+    *ms = tb - ta;
+    return hipSuccess;
+}
+hipError_t hipGetLastError() { return launch_error; }
+hipError_t hipStreamSynchronize(hipStream_t) { return sync_error; }
+hipError_t hipMemcpy(void* dst, const void* src, size_t n, hipMemcpyKind) {
+    if (copies_left == 0) return hipErrorInvalidValue;
+    if (copies_left > 0) --copies_left;
+    std::memcpy(dst, src, n);
+    ++copies;
+    return hipSuccess;
+}
+const char* hipGetErrorString(hipError_t e) { return e == hipErrorOutOfMemory ? "out of memory" : e == hipErrorInvalidValue ? "invalid argument" : "other"; }
 hipError_t hipEventDestroy(hipEvent_t e) { return release(EVT, (void*)e); }
 hipError_t hipModuleLoadData(hipModule_t* m, const void*) { return make(MOD, (void**)m, 1); }
 hipError_t hipModuleUnload(hipModule_t m) { return release(MOD, (void*)m); }
@@ -158,6 +188,40 @@ void failed_allocations() {
     CHECK(!d && live(DEV) == live0);
     dev_allocs_left = -1;
 }
+
+void call_endings() {
+    const double src[3] = {1.5, 2.5, 3.5};
+    double a[3] = {0, 0, 0}, b[2] = {0, 0};
+    std::string err;
+    CHECK(hip_ok("who", hipSuccess, err) && err.empty());
+    CHECK(!hip_ok("demc_x", hipErrorOutOfMemory, err) && err == "demc_x: out of memory");
+    err.clear();
+    CHECK(finish("demc_x", nullptr, {{a, src, sizeof a}, {nullptr, src, sizeof a}, {b, src + 1, sizeof b}}, err) && err.empty());
+    CHECK(copies == 2 && a[2] == 3.5 && b[0] == 2.5 && b[1] == 3.5);  // in order; the one that was not asked for is skipped
+    // a launch error, a stream error, a failed copy: nothing (more) is copied, and the message names the call
+    launch_error = hipErrorInvalidValue;
+    CHECK(!finish("demc_x", nullptr, {{a, src, sizeof a}}, err) && err == "demc_x: invalid argument" && copies == 2);
+    launch_error = hipSuccess; sync_error = hipErrorOutOfMemory;
+    CHECK(!finish("demc_y", nullptr, {{a, src, sizeof a}}, err) && err == "demc_y: out of memory" && copies == 2);
+    sync_error = hipSuccess; copies_left = 1;
+    CHECK(!finish("demc_z", nullptr, {{a, src, sizeof a}, {b, src, sizeof b}, {a, src, sizeof a}}, err) && err == "demc_z: invalid argument" && copies == 3);
+    copies_left = -1;
+}
+
+void pass_trace() {
+    const int f0 = freed[EVT];
+    {
+        PassTrace tr;  // marks at 1, 3, 6 and 10 ms: passes of 2, 3 and 4 ms between consecutive marks, of 2 and 4 ms between pairs
+        for (float t : {1.f, 3.f, 6.f, 10.f}) { now_ms = t; CHECK(tr.mark(nullptr)); }
+        CHECK(tr.ev.size() == 4 && live(EVT) == 4);
+        tr.print("devmem_host consecutive", 3, 1);
+        tr.print("devmem_host pairs", 2, 2);
+        events_left = 0;
+        CHECK(!tr.mark(nullptr) && tr.ev.size() == 4);  // an event that cannot be created: nothing is kept
+        events_left = -1;
+    }
+    CHECK(freed[EVT] == f0 + 4);
+}
 }  // namespace
 
 int main() {
@@ -165,6 +229,8 @@ int main() {
     moves();
     record_assignment();
     failed_allocations();
+    call_endings();
+    pass_trace();
     for (int k = 0; k < N_KINDS; ++k) {
         CHECK(made[k] > 0);
         CHECK(live((Kind)k) == 0);

@@ -96,8 +96,9 @@ def kat(N, K, seed):
     return x.astype(np.float64).reshape(N, K, 1)
 
 
-# ---- the launch geometry of the device code, restated: csrc/demc_cov.hpp's constants and cov_run's arithmetic.  The GPU cases
-# assert the geometry they were chosen for, so a changed constant fails them instead of moving them to another path.
+# ---- the launch geometry of the device code, restated: the kCov* constants and plan_cov's arithmetic (csrc/demc_postplan.hpp;
+# tests/test_postplan_host.py holds this copy to the planner).  The GPU cases assert the geometry they were chosen for, so a changed
+# constant fails them instead of moving them to another path.
 COV_MAX_COLS, COV_WG, COV_CHUNK, COV_MAX_WORKERS, COV_FINAL_WG = 64, 512, 512, 512, 1024
 
 
@@ -125,12 +126,13 @@ def _root():
 
 
 def test_geometry_constants_are_the_headers():
-    text = open(os.path.join(_root(), "differentialevolutionmcmc.jl_amd", "csrc", "demc_cov.hpp")).read()
-    vals = {name: int(v) for name, v in re.findall(r"constexpr\s+int\s+(kCov[A-Z]\w+)\s*=\s*(\d+)\s*;", text)}
+    from test_postplan_host import constants
+    # (as the compiler sees csrc/demc_postplan.hpp; geometry() itself is held to plan_cov there)
+    vals = {name: v for name, v in constants().items() if name.startswith("kCov")}
     want = dict(kCovMaxCols=COV_MAX_COLS, kCovWG=COV_WG, kCovChunk=COV_CHUNK, kCovMaxWorkers=COV_MAX_WORKERS, kCovFinalWG=COV_FINAL_WG)
     assert vals == want, (vals, want)
     h = open(os.path.join(_root(), "include", "demc_cov.h")).read()
-    assert int(re.search(r"#define DEMC_COV_MAX_COLS (\d+)", h).group(1)) == COV_MAX_COLS
+    assert int(re.search(r"#define DEMC_COV_MAX_COLS (\d+)", h).group(1)) == COV_MAX_COLS == constants()["DEMC_COV_MAX_COLS"]
     assert COV_CHUNK % (4 * (COV_WG // 64)) == 0  # every wave has the same number of k-steps in a full chunk
     # the LDS of k_cov_final: the totals of a worker's partial at K = 64 and the 64 x 64 triangle
     assert 8 * (geometry(1, 1, 62, 62, 64)["partial"] + 64 * 64) <= 64 * 1024

@@ -1,6 +1,7 @@
-"""The move-only owners of csrc/demc_devmem.hpp (DevBuf, PinnedBuf, Event, Module, Scratch) release what they hold exactly once:
-tests/devmem_host.cpp -- a program of its own, HIP stubbed by counters over malloc / free -- is built with the address and
-undefined-behaviour sanitizers and run.  No GPU, no HIP runtime."""
+"""The move-only owners of csrc/demc_devmem.hpp (DevBuf, PinnedBuf, Event, Module, Scratch) release what they hold exactly once,
+and the end of a call (finish) and the pass timer of the diagnostic variant (PassTrace) do what they say: tests/devmem_host.cpp -- a
+program of its own, HIP stubbed by counters over malloc / free -- is built with the address and undefined-behaviour sanitizers and
+run.  No GPU, no HIP runtime."""
 import os
 import shutil
 import subprocess
@@ -23,6 +24,8 @@ def test_owners_release_exactly_once_under_the_sanitizers(tmp_path):
     run = subprocess.run([exe], capture_output=True, text=True, timeout=60)
     assert run.returncode == 0, run.stdout + run.stderr
     assert "devmem owners ok" in run.stdout and "runtime error" not in run.stderr, run.stdout + run.stderr
+    # the pass timer of the diagnostic variant: the line tools/quantile_bench.py and tools/cov_bench.py read
+    assert run.stderr.splitlines() == ["devmem_host consecutive pass_ms 2.0000 3.0000 4.0000", "devmem_host pairs pass_ms 2.0000 4.0000"], run.stderr
 
 
 def test_releases_are_written_in_one_place():

@@ -87,8 +87,9 @@ def same_bits(a, b):
     return np.array_equal(a[ok].view(np.uint64), b[ok].view(np.uint64))
 
 
-# ---- the launch geometry of the device code, restated: csrc/demc_quantile.hpp's constants and quantile_run's arithmetic.  The GPU
-# cases assert the geometry they were chosen for, so a changed constant fails them instead of moving them to another path.
+# ---- the launch geometry of the device code, restated: the kQ* constants and plan_quantiles' arithmetic (csrc/demc_postplan.hpp;
+# tests/test_postplan_host.py holds this copy to the planner).  The GPU cases assert the geometry they were chosen for, so a changed
+# constant fails them instead of moving them to another path.
 Q_BITS, Q_WG, Q_MAX_WG, Q_SLOTS, Q_PROBES, Q_MAX_TARGETS, Q_MAX_CHUNKS_PER_WG = 8, 512, 512, 64, 4, 32, 1 << 22
 
 
@@ -143,17 +144,14 @@ def _root():
 def test_geometry_constants_are_the_headers():
     import os
     import re
-    text = open(os.path.join(_root(), "differentialevolutionmcmc.jl_amd", "csrc", "demc_quantile.hpp")).read()
-    vals = {}
-    for name, expr in re.findall(r"constexpr\s+[\w ]+?\s+(kQ[A-Z]\w+)\s*=\s*([^;]+);", text):
-        expr = expr.replace("LL", "").replace("ull", "")
-        if re.fullmatch(r"[0-9\s*<()+]+", expr):
-            vals[name] = eval(expr)  # (digits, *, <<, + and brackets only)
+    from test_postplan_host import constants
+    vals = constants()  # (as the compiler sees csrc/demc_postplan.hpp; geometry() and targets() are held to plan_quantiles there)
     want = dict(kQBits=Q_BITS, kQWG=Q_WG, kQMaxWG=Q_MAX_WG, kQSlots=Q_SLOTS, kQProbes=Q_PROBES, kQMaxTargets=Q_MAX_TARGETS, kQMaxChunksPerWG=Q_MAX_CHUNKS_PER_WG)
     for name, v in want.items():
         assert vals.get(name) == v, (name, vals.get(name), v)
     h = open(os.path.join(_root(), "include", "demc_quantile.h")).read()
-    assert int(re.search(r"#define DEMC_QUANTILE_MAX_PROBS (\d+)", h).group(1)) * 2 == Q_MAX_TARGETS
+    assert int(re.search(r"#define DEMC_QUANTILE_MAX_PROBS (\d+)", h).group(1)) * 2 == Q_MAX_TARGETS == vals["DEMC_QUANTILE_MAX_PROBS"] * 2
+    assert vals["kQKeyNegInf"] == KEY_NEG_INF and vals["kQKeyPosInf"] == KEY_POS_INF and vals["kQPasses"] * Q_BITS == 64
     # the 32-bit counts: a workgroup counts at most chunks_per_wg_max * Q_WG values of a series per pass
     assert Q_MAX_CHUNKS_PER_WG * Q_WG <= 1 << 32 and 2 * Q_SLOTS * 257 * 4 <= 160 * 1024  # two workgroups per CU
     # ... and the rule, at the sizes DESIGN.md 5.6 names

@@ -171,8 +171,9 @@ def restate_np(x, max_lag=0, rho_len=0):
         return out
 
 
-# ---- the launch geometry of the device code, restated: csrc/demc_summary.hpp's constants and summary_run's arithmetic.  The GPU
-# cases assert the geometry they were chosen for, so a changed constant fails them instead of moving them to another path.
+# ---- the launch geometry of the device code, restated: the kSum* constants and plan_summary's arithmetic (csrc/demc_postplan.hpp;
+# tests/test_postplan_host.py holds this copy to the planner).  The GPU cases assert the geometry they were chosen for, so a changed
+# constant fails them instead of moving them to another path.
 SUM_LAG_BLOCK, SUM_MAX_JT, SUM_MAX_WORKERS = 64, 8, 1024
 SUM_LDS_SMALL, SUM_LDS_MAX, SUM_GLOBAL_TILE = 64 * 1024, 144 * 1024, 64 << 20
 
@@ -331,21 +332,9 @@ def test_vectorised_restatement_equals_the_plain_loops(max_lag):
         assert r["rho"][0] == 1.0 and np.isnan(r["rho"][1:]).all() and restate(x, max_lag, 70)["rho"][0] == 1.0, key
 
 
-def _header_constants():
-    import os
-    import re
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    text = open(os.path.join(root, "differentialevolutionmcmc.jl_amd", "csrc", "demc_summary.hpp")).read()
-    vals = {}
-    for name, expr in re.findall(r"constexpr\s+\w+\s+(kSum\w+)\s*=\s*([^;]+);", text):
-        expr = expr.replace("(size_t)", "")
-        assert re.fullmatch(r"[0-9\s*<()+]+", expr), (name, expr)
-        vals[name] = eval(expr)  # (digits, *, <<, + and brackets only)
-    return vals
-
-
 def test_geometry_constants_are_the_headers():
-    c = _header_constants()
+    from test_postplan_host import constants
+    c = constants()  # (as the compiler sees csrc/demc_postplan.hpp; geometry() itself is held to plan_summary there)
     want = dict(kSumLagBlock=SUM_LAG_BLOCK, kSumMaxJT=SUM_MAX_JT, kSumMaxWorkers=SUM_MAX_WORKERS, kSumLdsSmall=SUM_LDS_SMALL,
                 kSumLdsMax=SUM_LDS_MAX, kSumGlobalTile=SUM_GLOBAL_TILE)
     for name, v in want.items():

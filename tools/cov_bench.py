@@ -8,7 +8,8 @@ demc_export_chains of the same rows and chains.series_cov on the host -- on the 
 Each size runs in a process of its own under a time limit (`--limit` seconds); a size that runs into it is reported as such and the
 other still runs.  Prints one JSON object per size: wall-clock ms of demc_covariance (median / min / max over the repeats, after one
 warm-up call), of the export alone and of series_cov on the exported array, the device time of the three stages (one further call
-with DEMC_COV_TRACE=1: the library brackets pass 1, pass 2 and the final kernel with events and prints the times to stderr), the
+in a process of its own on the diagnostic variant of the library, `make TRACE=1 OUT=../libdemc_hip_trace.so`, which brackets pass 1,
+pass 2 and the final kernel with events and prints the times to stderr; TRACE_PREBUILT=1: the variant is there already), the
 history bytes per second and the FP64 rate of pass 2, the bytes either path moves to the host, and the largest scaled difference
 between the device's matrices and the host function's."""
 import argparse
@@ -25,40 +26,43 @@ sys.path.insert(0, ROOT)
 SIZES = {"gaussian_example": dict(G=4, Np=6, D=2), "mvn_64x64_d32": dict(G=64, Np=64, D=32)}
 
 
-def one(name, rows, repeats):
+def engine(name, rows):
+    """a handle of the size `name` with `rows` rows of history"""
     import demc_amd as D
     from demc_amd import families as F
-    from demc_amd.chains import series_cov
     s = SIZES[name]
     G, Np, d = s["G"], s["Np"], s["D"]
     P = G * Np
     rng = np.random.default_rng(50514)
     e = D.HipEngine(n_groups=G, Np=Np, D=d, n_rows=rows, seed=2024, burnin=0, schedule=2)
+    if name == "gaussian_example":
+        e.set_model(F.FAM_GAUSSIAN, rng.normal(0.0, 1.0, 50), [50])
+        e.set_priors([F.PRIOR_NORMAL, 2], [0.0, 0.0], [1.0, 1.0])
+        e.set_bounds([-np.inf, 0.0], [np.inf, np.inf])
+        e.set_state(np.stack([rng.normal(0, 0.3, P), rng.uniform(0.8, 1.3, P)], 1))
+    else:
+        A = rng.normal(0, 1, (d, d))
+        Sigma = A @ A.T / d + 0.5 * np.eye(d)
+        X = rng.multivariate_normal(rng.normal(0, 1, d), Sigma, 400)
+        e.set_model(F.FAM_MVN_FULL, X, [400, d], Sigma)
+        e.set_priors([F.PRIOR_NORMAL] * d, [0.0] * d, [1.0] * d)
+        e.set_bounds([-np.inf] * d, [np.inf] * d)
+        e.set_state(rng.normal(0, 1, (P, d)))
+    e.step(1, rows)
+    return e
+
+
+def one(name, rows, repeats):
+    from demc_amd.chains import series_cov
+    d, P = SIZES[name]["D"], SIZES[name]["G"] * SIZES[name]["Np"]
+    e = engine(name, rows)
     try:
-        if name == "gaussian_example":
-            e.set_model(F.FAM_GAUSSIAN, rng.normal(0.0, 1.0, 50), [50])
-            e.set_priors([F.PRIOR_NORMAL, 2], [0.0, 0.0], [1.0, 1.0])
-            e.set_bounds([-np.inf, 0.0], [np.inf, np.inf])
-            e.set_state(np.stack([rng.normal(0, 0.3, P), rng.uniform(0.8, 1.3, P)], 1))
-        else:
-            A = rng.normal(0, 1, (d, d))
-            Sigma = A @ A.T / d + 0.5 * np.eye(d)
-            X = rng.multivariate_normal(rng.normal(0, 1, d), Sigma, 400)
-            e.set_model(F.FAM_MVN_FULL, X, [400, d], Sigma)
-            e.set_priors([F.PRIOR_NORMAL] * d, [0.0] * d, [1.0] * d)
-            e.set_bounds([-np.inf] * d, [np.inf] * d)
-            e.set_state(rng.normal(0, 1, (P, d)))
-        e.step(1, rows)
         e.covariance(0, rows)  # warm-up: the first launch of each kernel
         dev = []
         for _ in range(repeats):
             t0 = time.perf_counter()
             out = e.covariance(0, rows)
             dev.append((time.perf_counter() - t0) * 1e3)
-        os.environ["DEMC_COV_TRACE"] = "1"  # one traced call: its stage times go to stderr, where the parent reads them
-        sys.stderr.flush()
-        e.covariance(0, rows)
-        del os.environ["DEMC_COV_TRACE"]
         e.export_chains(0, min(rows, 2))
         exp = []
         for _ in range(repeats):
@@ -88,15 +92,33 @@ def one(name, rows, repeats):
                 method="wall clock around each call (the calls drain the stream), one handle, same rows")
 
 
+def traced(name, rows):
+    """one call on the diagnostic variant of the library: its stage times go to stderr, where the parent reads them"""
+    csrc = os.path.join(ROOT, "differentialevolutionmcmc.jl_amd", "csrc")
+    if os.environ.get("TRACE_PREBUILT") != "1":  # (build here and ship the library to the GPU box: TRACE_PREBUILT=1 skips the make)
+        subprocess.check_call(["make", "-B", "-j8", "-C", csrc, "-s", "TRACE=1", "OUT=../libdemc_hip_trace.so"], stdout=sys.stderr)
+    import demc_amd
+    demc_amd._ffi.LIB_PATH = os.path.join(ROOT, "differentialevolutionmcmc.jl_amd", "libdemc_hip_trace.so")
+    e = engine(name, rows)
+    try:
+        e.covariance(0, rows)
+    finally:
+        e.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--rows", type=int, default=1000)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--limit", type=float, default=300.0, help="seconds each size may take")
     ap.add_argument("--size", choices=sorted(SIZES), help="(internal) run this size in this process")
+    ap.add_argument("--traced", choices=sorted(SIZES), help="(internal) one call of this size on the diagnostic variant, in this process")
     o = ap.parse_args()
     if o.size:
         print(json.dumps(one(o.size, o.rows, o.repeats)))
+        return 0
+    if o.traced:
+        traced(o.traced, o.rows)
         return 0
     for name in SIZES:  # a fresh process per size, each under its own limit; a GPU fault or a time-out ends the run
         try:
@@ -109,6 +131,14 @@ def main():
             print(json.dumps(dict(size=name, error=f"exit status {r.returncode}", stderr=r.stderr[-2000:])))
             return r.returncode
         res = json.loads(r.stdout.strip().splitlines()[-1])
+        try:  # the timed calls above ran on the product library; the variant serves this one call
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--traced", name, "--rows", str(o.rows)], timeout=o.limit, capture_output=True, text=True)
+        except subprocess.TimeoutExpired:
+            print(json.dumps(dict(size=name, error=f"time limit of {o.limit} s (traced call)")))
+            return 124
+        if r.returncode != 0:
+            print(json.dumps(dict(size=name, error=f"exit status {r.returncode} (traced call)", stderr=r.stderr[-2000:])))
+            return r.returncode
         stages = [ln for ln in r.stderr.splitlines() if ln.startswith("demc_covariance pass_ms")]
         if stages:
             ms = [float(x) for x in stages[-1].split()[2:]]
