@@ -1,19 +1,12 @@
-// demc_device.hpp -- device-side building blocks of the gfx950 DE-MCMC path:
-// counter-based Philox4x32-10, draw addressing, and the registered log-densities.
-//
-// RNG contract (DESIGN.md "Randomness"): the reference consumes Julia's task-local Xoshiro
-// stream in a fixed order.  A fused kernel cannot share one sequential
-// stream, so every draw is addressed instead:
-//     Philox4x32-10( key = seed,
-//                    ctr = (block, entity, iteration, stream<<24 | sweep) )
-// entity = global group index or global slot index, so results do not depend on how groups
-// are sharded over GPUs.  One block = 4 x u32 = two 53-bit uniforms.
+// demc_device.hpp -- device-side building blocks of the gfx950 DE-MCMC path: the registered log-densities, and through
+// demc_philox.hpp the counter-based Philox4x32-10 and the draw addressing (shared with the host-only schedule).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <cmath>
 
+#include "demc_philox.hpp"  // Stream, U4, draw_block, u53, u32unit, mulhi32, pick_pair, pick_triple
 #include "demc_dimtab.hpp"  // kLog2Pi / kLogPi / kPi, the PR_* kinds, prior_const: shared with the host-only preparation
 #include "demc_logphi_table.hpp"
 #include "demc_phi_table.hpp"
@@ -24,72 +17,7 @@ namespace demc {
 constexpr double kInvSqrt2 = 0.70710678118654752440;
 constexpr double kInvSqrt2Pi = 0.39894228040143267794;
 
-enum Stream : uint32_t { S_STEP = 1, S_GROUP = 2, S_PART = 3, S_NOISE = 4, S_RECOMB = 5, S_MIG = 6 };
-
-struct U4 {
-    uint32_t x, y, z, w;
-};
-
-__host__ __device__ inline U4 philox4x32_10(U4 c, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c.x;
-        const uint64_t p1 = (uint64_t)0xCD9E8D57u * c.z;
-        U4 n;
-        n.x = (uint32_t)(p1 >> 32) ^ c.y ^ k0;
-        n.y = (uint32_t)p1;
-        n.z = (uint32_t)(p0 >> 32) ^ c.w ^ k1;
-        n.w = (uint32_t)p0;
-        c = n;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return c;
-}
-
-__host__ __device__ inline U4 draw_block(uint64_t seed, uint32_t stream, uint32_t sweep, uint64_t iter, uint32_t entity,
-                                         uint32_t block) {
-    U4 c;
-    c.x = block;
-    c.y = entity;
-    c.z = (uint32_t)iter;
-    c.w = (stream << 24) | (sweep & 0xFFFFu);
-    return philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-}
-
-// 53-bit uniform in [0,1), the resolution of Julia's rand(Float64)
-__host__ __device__ inline double u53(uint32_t lo, uint32_t hi) {
-    const uint64_t x = ((uint64_t)hi << 32) | lo;
-    return (double)(x >> 11) * (1.0 / 9007199254740992.0);
-}
-// 32-bit uniform in (0,1) from ONE word: the per-scalar draws (crossover noise b ~ U(-eps, eps), recombination coins, the
-// Box-Muller inputs of the mutation noise) -- four scalars per Philox block: block m of the NOISE / RECOMB streams covers
-// scalars 4m..4m+3 (word 2(k&1)+e for scalar e of dim pair k).  2^-32 resolution is ample for a jitter of scale eps.
-__host__ __device__ inline double u32unit(uint32_t w) { return ((double)w + 0.5) * (1.0 / 4294967296.0); }
-__host__ __device__ inline uint32_t mulhi32(uint32_t x, uint32_t m) { return (uint32_t)(((uint64_t)x * m) >> 32); }
 __device__ inline uint64_t mulhi64(uint64_t x, uint64_t m) { return __umul64hi(x, m); }
-
-// StatsBase.samplepair: i1 = rand(1:m); i2 = rand(1:m-1); i2 == i1 ? m : i2
-__host__ __device__ inline void pick_pair(uint32_t r0, uint32_t r1, uint32_t m, uint32_t& i1, uint32_t& i2) {
-    i1 = mulhi32(r0, m);
-    uint32_t b = mulhi32(r1, m - 1);
-    if (b == i1) b = m - 1;
-    i2 = b;
-}
-// ordered 3-of-m without replacement (rank shift)
-__host__ __device__ inline void pick_triple(uint32_t r0, uint32_t r1, uint32_t r2, uint32_t m, uint32_t& i1, uint32_t& i2,
-                                            uint32_t& i3) {
-    const uint32_t a = mulhi32(r0, m);
-    uint32_t b = mulhi32(r1, m - 1);
-    if (b >= a) ++b;
-    uint32_t c = mulhi32(r2, m - 2);
-    const uint32_t lo = a < b ? a : b, hi = a < b ? b : a;
-    if (c >= lo) ++c;
-    if (c >= hi) ++c;
-    i1 = a;
-    i2 = b;
-    i3 = c;
-}
 
 // ---- log-densities of the registered family (Distributions.jl forms) ----
 __device__ inline double norm_logpdf(double x, double m, double s) {

@@ -5,7 +5,8 @@
 // Each owner holds one resource and releases it exactly once: in its destructor, in reset(), or when another owner is moved
 // over it.  A record of owners (the handle's Model, its Replay) is therefore released by assigning a fresh record over it, and
 // a handle by `delete`; nothing keeps a list of what to free.  The owners carry no size, no stream and no allocator: whoever
-// frees memory that a stream may still read synchronises that stream first.
+// frees memory that a stream may still read synchronises that stream first.  StagedList, built of three of them, is the one that
+// knows its capacities and is told the stream: a list that reaches the device through pinned memory.
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -73,6 +74,43 @@ struct Event : Owned<hipEvent_t, FreeEvent> {
 };
 struct Module : Owned<hipModule_t, FreeModule> {
     hipError_t load(const void* image) { return make([&](hipModule_t* m) { return hipModuleLoadData(m, image); }); }
+};
+
+// A list staged through pinned memory: a device copy kernels read, a pinned host copy the next content is written into, and an
+// event that says the last copy out of the host buffer has been consumed -- so refilling it is asynchronous for the host too (a
+// pageable source would make the copy wait for everything queued on the stream), and the buffers outlive the call.  A failure
+// leaves the owner empty or unchanged, never with a capacity it does not have.
+template <typename T>
+struct StagedList {
+    DevBuf<T> dev;
+    PinnedBuf<T> pin;
+    Event ev;
+    size_t dev_cap = 0, pin_cap = 0;
+    // The host buffer, with room for n elements on both sides and free to be rewritten (the event has been waited for).  A device
+    // buffer too small is replaced only once `st`, whose kernels may still read it, has been waited for.
+    hipError_t stage(size_t n, hipStream_t st, T** host) {
+        *host = nullptr;
+        hipError_t e = ev ? hipSuccess : ev.create(hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventSynchronize(ev);
+        if (e == hipSuccess && n > dev_cap) {
+            if (dev) e = hipStreamSynchronize(st);
+            if (e == hipSuccess) {
+                dev_cap = 0;
+                if ((e = dev.alloc(n)) == hipSuccess) dev_cap = n;
+            }
+        }
+        if (e == hipSuccess && n > pin_cap) {
+            pin_cap = 0;
+            if ((e = pin.alloc(n, hipHostMallocDefault)) == hipSuccess) pin_cap = n;
+        }
+        if (e == hipSuccess) *host = pin;
+        return e;
+    }
+    // the first n staged elements to the device, on `st`: behind every kernel of it that still reads the previous content
+    hipError_t send(size_t n, hipStream_t st) {
+        const hipError_t e = hipMemcpyAsync(dev, pin, n * sizeof(T), hipMemcpyHostToDevice, st);
+        return e == hipSuccess ? hipEventRecord(ev, st) : e;
+    }
 };
 
 struct Scratch {  // device allocations of one call, freed however it ends

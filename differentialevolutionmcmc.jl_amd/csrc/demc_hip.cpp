@@ -5,12 +5,14 @@
 // step!/update!/block_update!/mutate_or_crossover! (main.jl:84-207) imply:
 //     [migration pack + apply]  then per sweep (block) and per colour phase:  K1 propose -> K2 loglike -> K3 accept/store
 // All per-iteration randomness is addressed by (seed, iteration, entity) inside the kernels, so the host
-// loop needs no device->host traffic: the only host-side draw is the alpha coin (pure function of seed, iter).
+// loop needs no device->host traffic: what the host draws -- the alpha coin, select_groups, the frozen sweeps' mutation coins -- are
+// pure functions of (seed, iteration), re-drawn in demc_schedule.hpp with the kernels' own Philox text (demc_philox.hpp).
 //
 // There is NO CPU fallback in this file: every compute entry point launches HIP kernels or fails.
 //
 // What is launched -- kernel instance, grid, workgroup size, LDS bytes, chunk counts, fuse flags -- is decided in demc_geometry.hpp,
-// host-only code that knows neither HIP nor the handle; what a model's data become before they are uploaded, in demc_prep.hpp.
+// host-only code that knows neither HIP nor the handle; what a model's data become before they are uploaded, in demc_prep.hpp; what a
+// step call does iteration by iteration -- its refusals, its segments, the phases of a sweep, the frozen order --, in demc_schedule.hpp.
 // This file gathers their inputs from the handle, asks the device what only it knows, and does what the plans say.
 #include "../../include/demc.h"
 #include "../../include/demc_summary.h"  // demc_summarize
@@ -54,6 +56,7 @@
 #include "demc_instances.hpp"  // one table per templated kernel, built from the lists above: every choice of an instance goes through them
 #include "demc_geometry.hpp"  // host-only: every launch-geometry decision, as plans the launches below carry out
 #include "demc_postplan.hpp"  // host-only: the history window and the plans of demc_summarize, demc_quantiles, demc_covariance
+#include "demc_schedule.hpp"  // host-only: what a step call does iteration by iteration -- coins, refusals, segments, phases, frozen order
 
 using namespace demc;
 
@@ -151,34 +154,28 @@ struct demc_handle {
     K1Lds k1;  // K1 LDS carve-up for the model and the population (size_k1_lds)
     FormPlan form[N_FORMS];  // the whole-update forms (size_k1_lds plans them; [FORM_PHASE] is not used)
     StreamGeo st;
-    // k_frozen_sweep: launch order of the groups per (iteration, block sweep) of the current demc_step call -- groups whose
-    // mutation coin fires (main.jl:199-207) first: their workgroups move the whole row and take twice as long, and a slow
-    // workgroup that starts last ends the launch.  A hint only: any order gives the same results.
     // by-product snapshot (KParams::snap_theta / snap_weight): the rows and weights a frozen sweep over the whole population ended
     // with, valid as the sweep-start snapshot of sweep `snap2_sweep` of iteration `snap2_iter` (and of nothing else)
     DevBuf<double> snap2, snap2_w;
     int64_t snap2_iter = -1;
     int snap2_sweep = -1;
-    DevBuf<int> frozen_order_d;
-    size_t frozen_order_cap = 0;
-    PinnedBuf<int> frozen_order_pin;        // pinned staging of the table (a truly asynchronous copy: nothing is drained)
-    size_t frozen_order_pin_cap = 0;
-    Event frozen_order_ev;                  // the last copy out of the staging buffer has been consumed
-    long long frozen_iter0 = 0;
-    int frozen_iters = 0;
+    // k_frozen_sweep: launch order of the groups per (iteration, block sweep) of the current demc_step call (fill_frozen_order)
+    struct FrozenOrder {
+        StagedList<int> table;  // (staged through pinned memory: a truly asynchronous copy, nothing is drained)
+        long long iter0 = 0;    // the iterations it covers (none: no table for the current call)
+        int iters = 0;
+    } frozen;
     int n_cus = 0;
     bool bracket_open = false;  // timing: between tick(begin) and tick(end) of a bracket whose kernels carry the events
     size_t lr_two_lds = 0;     // long-row kernel: the dynamic LDS size lr_two_fit was asked for
     bool lr_two_fit = false;   // ... two 256-thread workgroups with that much LDS fit on a CU
-    // update of a subset of the groups (demc_update_groups_async): two device lists used alternately, and the one in force
-    // Each call takes the next of kGlistRing slots: a pinned host copy of the list, a device copy, and an event that marks
-    // the host copy as consumed.  The device copy is refilled by a copy ON THE HANDLE'S STREAM, i.e. behind every kernel that
-    // still reads its previous content.
-    static constexpr int kGlistRing = 8;
-    DevBuf<int> glist_buf[kGlistRing];
-    PinnedBuf<int> glist_pin[kGlistRing];
-    Event glist_ev[kGlistRing];
-    int glist_next = 0;
+    // update of a subset of the groups (demc_update_groups_async): each call takes the next slot of a ring of staged lists
+    // (sized once, at create), and the device list in force
+    struct GroupLists {
+        static constexpr int kRing = 8;
+        StagedList<int> slot[kRing];
+        int next = 0;
+    } glist;
     const int* cur_glist = nullptr;
     int cur_ng = 0;
     std::string err;
@@ -686,7 +683,7 @@ int launch_phase(demc_handle* h, KParams k) {
     p.tile_in_lds = k.tile_in_lds != 0; p.live = k.theta == h->theta;
     p.masked = k.mask != nullptr; p.n_mrun = k.n_mrun; p.mrun_in = k.mrun_in; p.mrun_start = k.mrun_start;
     p.snap2 = h->snap2.get() != nullptr; p.snap2_iter = h->snap2_iter; p.snap2_sweep = h->snap2_sweep;
-    p.frozen_order = h->frozen_order_d.get() != nullptr; p.frozen_iter0 = h->frozen_iter0; p.frozen_iters = h->frozen_iters;
+    p.frozen_order = h->frozen.table.dev.get() != nullptr; p.frozen_iter0 = h->frozen.iter0; p.frozen_iters = h->frozen.iters;
     int rc_fit = DEMC_OK;
     const PhasePlan pl = plan_phase(setup_of(h), p, [&](size_t lds) { return (rc_fit = two_longrows_fit(h, lds)) == DEMC_OK && h->lr_two_fit; });
     if (rc_fit != DEMC_OK) return rc_fit;
@@ -701,7 +698,7 @@ int launch_phase(demc_handle* h, KParams k) {
     apply_tail(h, k, pl.t);
     k.n_split = pl.n_split; k.own_in_pool = pl.own_in_pool; k.tile_rows = pl.tile_rows; k.plan = pl.plan;
     if (pl.frozen_order)
-        k.glist = h->frozen_order_d + ((size_t)(k.iter - h->frozen_iter0) * c.n_blocks + k.sweep) * (size_t)c.n_groups;
+        k.glist = h->frozen.table.dev + ((size_t)(k.iter - h->frozen.iter0) * c.n_blocks + k.sweep) * (size_t)c.n_groups;
     if (pl.write_snap2) {
         k.snap_theta = h->snap2; k.snap_weight = h->snap2_w;
         h->snap2_iter = (int64_t)k.iter; h->snap2_sweep = (int)k.sweep + 1;
@@ -840,7 +837,6 @@ int launch_form(demc_handle* h, Form form, long long iter0, int n_iters) {
 
 // one sweep of every group: mutate_or_crossover! for all groups (main.jl:161-167, 199-207)
 int run_sweep(demc_handle* h, long long iter, unsigned sweep, const unsigned char* mask, long long store_row) {
-    const int Np = h->c.Np;
     KParams k = base_params(h);
     k.iter = iter; k.sweep = sweep; k.mask = mask; k.store_row = store_row;
     if (mask && sweep < h->mask_runs.size()) {
@@ -849,26 +845,12 @@ int run_sweep(demc_handle* h, long long iter, unsigned sweep, const unsigned cha
         std::memcpy(k.mrun_start, mr.start, sizeof k.mrun_start);
     } else if (mask)
         k.n_mrun = 0;
-    if (h->c.schedule == DEMC_SCHED_TWO_COLOUR) {
-        const int half = Np / 2;
-        k.a_lo = 0; k.n_act = half; k.pool_lo = half; k.pool_n = Np - half; k.exclude_self = 0;
-        int rc = launch_phase(h, k);
-        if (rc != DEMC_OK) return rc;
-        k.a_lo = half; k.n_act = Np - half; k.pool_lo = 0; k.pool_n = half;
-        return launch_phase(h, k);
+    for (int i = 0, n = n_colour_phases(h->c); i < n; ++i) {  // who moves against whom: colour_phase, demc_schedule.hpp
+        const ColourPhase ph = colour_phase(h->c, i);
+        k.a_lo = ph.a_lo; k.n_act = ph.n_act; k.pool_lo = ph.pool_lo; k.pool_n = ph.pool_n; k.exclude_self = ph.exclude_self;
+        if (int rc = launch_phase(h, k)) return rc;
     }
-    if (h->c.schedule == DEMC_SCHED_SEQUENTIAL) {
-        // crossover.jl:13-15 / mutation.jl:16: particle pl of every group moves after 0..pl-1 were updated in place;
-        // the groups advance side by side (one task per group in p_update!, main.jl:135-148).  Partners come from the
-        // whole group minus self (setdiff, crossover.jl:158), snooker's three from the whole group (crossover.jl:241).
-        for (int pl = 0; pl < Np; ++pl) {
-            k.a_lo = pl; k.n_act = 1; k.pool_lo = 0; k.pool_n = Np; k.exclude_self = 1;
-            int rc = launch_phase(h, k);
-            if (rc != DEMC_OK) return rc;
-        }
-        return DEMC_OK;
-    }
-    return launch_phase(h, k);
+    return DEMC_OK;
 }
 
 int migration_enqueue(demc_handle* h, long long iter, double* dev_rows, const double* dev_all_rows, bool pack, bool apply) {
@@ -903,9 +885,7 @@ int evaluate_rows(demc_handle* h, double* theta_dev, double* weight_dev) {
 // memory is not an error (the sweeps copy the population instead); demc_last_error then says so.
 int plan_snap2(demc_handle* h) {
     const demc_config& c = h->c;
-    const bool want = frozen_possible(setup_of(h)) && c.n_blocks > 1 && c.schedule == DEMC_SCHED_SYNCHRONOUS &&
-                      c.partner_kind == DEMC_PARTNER_HISTORY && c.proposal_kind == 0 && c.burnin >= 1;
-    if (!want) {
+    if (!snap2_wanted(setup_of(h))) {
         if (h->snap2 || h->snap2_w) {
             HIPCHK(hipStreamSynchronize(h->stream));
             h->snap2.reset(); h->snap2_w.reset(); h->snap2_iter = -1;
@@ -1040,10 +1020,11 @@ int32_t demc_create(const demc_config* cfg, demc_handle** out) {
     ALLOC(h->partial, (size_t)h->partial_cap * P); ALLOC(h->aux, P);
     ALLOC(h->dimtab, D);
     ALLOC(h->dimseg, (size_t)kMaxDimSeg);
-    for (int i = 0; i < demc_handle::kGlistRing; ++i) {
-        ALLOC(h->glist_buf[i], (size_t)c.n_groups);
-        HIPCHK(h->glist_pin[i].alloc((size_t)c.n_groups, hipHostMallocDefault));
-        HIPCHK(h->glist_ev[i].create(hipEventDisableTiming));
+    for (StagedList<int>& s : h->glist.slot) {  // the ring's buffers are sized here, once, for a list of every group
+        int* host = nullptr;
+        const hipError_t e = s.stage((size_t)c.n_groups, h->stream, &host);
+        if (e != hipSuccess && s.ev && !s.dev) return fail(h, DEMC_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));  // (as ALLOC reports it)
+        HIPCHK(e);
     }
     ALLOC(h->mig_rows, (size_t)c.n_groups_total * (D + 3));
     ALLOC(h->scratch_theta, P * D); ALLOC(h->scratch_w, P);
@@ -1450,13 +1431,16 @@ int32_t demc_covariance(demc_handle* h, int64_t row0, int64_t row1, const int32_
     });
 }
 
-// the alpha coin of iteration `iter` as this handle sees it: the replayed uniform while one is set (main.jl:85)
-static bool migration_due_h(demc_handle* h, int64_t iter) {
-    if (h->rp.active && h->rp.has_step) {
-        const int ngt = h->c.n_groups_total > 0 ? h->c.n_groups_total : h->c.n_groups;
-        return h->rp.u_step <= (ngt == 1 ? 0.0 : h->c.alpha);
-    }
-    return demc_migration_due(&h->c, iter) != 0;
+// What next_segment (demc_schedule.hpp) reads of a call [., end) on this handle: the configuration, the form the call takes, and
+// the few facts only the handle knows (its communicator, the overlap switch, a replayed alpha coin).
+static StepCall step_call(const demc_handle* h, int64_t end, bool with_migration, Form form) {
+    StepCall s;
+    s.c = &h->c; s.end = end; s.with_migration = with_migration;
+    s.per_phase = form == FORM_PHASE; s.cap = iterations_per_launch(form);
+    s.sharded = h->c.n_groups_total != h->c.n_groups || (h->comm && h->own_comm);
+    s.overlap = h->comm_overlap;
+    s.replay = h->rp.active; s.replayed_step = h->rp.has_step; s.u_step = h->rp.u_step;
+    return s;
 }
 
 #define NCCLCHK(expr)                                                                                         \
@@ -1494,20 +1478,15 @@ static int step_body(demc_handle* h, int64_t iter0, int32_t n_iters, bool with_m
 // THE HANDLE'S STREAM, i.e. behind every kernel that still reads its previous content.
 static int update_subset(demc_handle* h, int64_t iter0, int32_t n_iters, const int32_t* groups, int32_t n) {
     if (n == 0) return DEMC_OK;
-    if (h->rp.active && h->rp.n_mig > 0)
-        return fail(h, DEMC_EINVAL, "subset updates follow demc_migration_groups, which does not see a replayed migration sub-group");
-    const int G = h->c.n_groups;
-    for (int i = 0; i < n; ++i)
-        if (groups[i] < 0 || groups[i] >= G) return fail(h, DEMC_EINVAL, "group index outside this handle");
-    const int slot = h->glist_next;
-    h->glist_next = (slot + 1) % demc_handle::kGlistRing;
-    int* dev = h->glist_buf[slot];
-    if (hipEventSynchronize(h->glist_ev[slot]) != hipSuccess) return fail(h, DEMC_EHIP, "group-list ring");
-    std::memcpy(h->glist_pin[slot], groups, (size_t)n * sizeof(int));
-    if (hipMemcpyAsync(dev, h->glist_pin[slot], (size_t)n * sizeof(int), hipMemcpyHostToDevice, h->stream) != hipSuccess ||
-        hipEventRecord(h->glist_ev[slot], h->stream) != hipSuccess)
-        return fail(h, DEMC_EHIP, "copying the group list");
-    h->cur_glist = dev;
+    if (Refusal r = refuse_subset(h->c, h->rp.active && h->rp.n_mig > 0, groups, n)) return fail(h, r);
+    // (a list of up to n_groups entries fits the slot as create sized it; a longer one -- repeated indices -- makes it grow)
+    StagedList<int>& list = h->glist.slot[h->glist.next];
+    h->glist.next = (h->glist.next + 1) % demc_handle::GroupLists::kRing;
+    int* host = nullptr;
+    if (list.stage((size_t)n, h->stream, &host) != hipSuccess) return fail(h, DEMC_EHIP, "group-list ring");
+    std::memcpy(host, groups, (size_t)n * sizeof(int));
+    if (list.send((size_t)n, h->stream) != hipSuccess) return fail(h, DEMC_EHIP, "copying the group list");
+    h->cur_glist = list.dev;
     h->cur_ng = n;
     const int rc = step_body(h, iter0, n_iters, false);
     h->cur_glist = nullptr;
@@ -1520,146 +1499,69 @@ static int update_subset(demc_handle* h, int64_t iter0, int32_t n_iters, const i
 // select start their update while the all-gather is in flight on the side stream; only the selected groups wait for it.
 static int exchange_overlapped(demc_handle* h, int64_t iter, int run) {
     const demc_config& c = h->c;
-    std::vector<int32_t> sel((size_t)c.n_groups_total), mine, rest;
-    int32_t n_sel = 0;
-    demc_migration_groups(&c, iter, sel.data(), &n_sel);
-    std::vector<char> picked((size_t)c.n_groups, 0);
-    for (int i = 0; i < n_sel; ++i) {
-        const int gl = sel[(size_t)i] - c.group_offset;
-        if (gl >= 0 && gl < c.n_groups) picked[(size_t)gl] = 1;
-    }
-    for (int g = 0; g < c.n_groups; ++g) (picked[(size_t)g] ? mine : rest).push_back(g);
+    std::vector<int32_t> perm((size_t)groups_total(c)), sel((size_t)groups_total(c)), mine((size_t)c.n_groups), rest((size_t)c.n_groups);
+    const Partition part = exchange_partition(c, iter, perm.data(), sel.data(), mine.data(), rest.data());
     migration_enqueue(h, iter, own_rows(h), nullptr, true, false);
     HIPCHK(hipEventRecord(h->ev_pack, h->stream));
     HIPCHK(hipStreamWaitEvent(h->side, h->ev_pack, 0));
     int rc = gather_enqueue(h, h->side);  // the one collective, off the main stream
     if (rc != DEMC_OK) return rc;
     HIPCHK(hipEventRecord(h->ev_gath, h->side));
-    rc = update_subset(h, iter, run, rest.data(), (int32_t)rest.size());  // overlaps the gather
+    rc = update_subset(h, iter, run, rest.data(), part.n_rest);  // overlaps the gather
     if (rc != DEMC_OK) return rc;
     HIPCHK(hipStreamWaitEvent(h->stream, h->ev_gath, 0));
     migration_enqueue(h, iter, nullptr, h->mig_rows, false, true);
-    return update_subset(h, iter, run, mine.data(), (int32_t)mine.size());
+    return update_subset(h, iter, run, mine.data(), part.n_mine);
 }
 
-// iterations [iter0, iter0 + n_iters) enqueued on the handle's stream; nothing is drained
-// launch order of the groups for the frozen-row sweeps of iterations [iter0, iter0 + n_iters): mutating groups first (the
-// group's coin is addressed Philox -- the host draws what the kernel will draw)
+// launch order of the groups for the frozen-row sweeps of iterations [iter0, iter0 + n_iters): whether a table is built and what
+// goes into it, demc_schedule.hpp; here it is staged and sent.  A table that cannot be built -- no memory, an event that fails --
+// means no hint, not an error.
 static void plan_frozen_order(demc_handle* h, int64_t iter0, int32_t n_iters) {
-    const demc_config& c = h->c;
-    h->frozen_iters = 0;
-    // nothing to plan where the phase plan cannot take the frozen form at all (frozen_possible; a pool beyond the kernel's), for a
-    // subset of the groups (its own list), without mutation, or under a replay
-    if (!frozen_possible(setup_of(h)) || c.Np > 512 || h->cur_glist || c.beta <= 0.0 || h->rp.active || n_iters < 1) return;
-    bool any = false;
-    std::vector<char> frozen((size_t)c.n_blocks, 0);
-    for (int b = 0; b < c.n_blocks && (size_t)b < h->mask_runs.size(); ++b) {
-        const auto& mr = h->mask_runs[(size_t)b];
-        frozen[(size_t)b] = block_span(mr.n, mr.in, mr.start, c.D).inside >= 1;
-        any = any || frozen[(size_t)b];
-    }
-    const size_t need = (size_t)n_iters * c.n_blocks * c.n_groups;
-    if (!any || need > ((size_t)1 << 24)) return;
-    if (need > h->frozen_order_cap) {
-        if (h->frozen_order_d && hipStreamSynchronize(h->stream) != hipSuccess) return;
-        h->frozen_order_cap = 0;
-        if (h->frozen_order_d.alloc(need) != hipSuccess) { (void)hipGetLastError(); return; }
-        h->frozen_order_cap = need;
-    }
-    // PINNED staging owned by the handle, guarded by an event: the copy below is asynchronous for the host too (a pageable source
-    // made it wait for everything already queued on the stream -- step_body's "nothing is drained" was not true for blocked
-    // hierarchical models), and the buffer outlives the call
-    if (!h->frozen_order_ev && h->frozen_order_ev.create(hipEventDisableTiming) != hipSuccess) return;
-    if (h->frozen_order_pin && hipEventSynchronize(h->frozen_order_ev) != hipSuccess) return;  // (the previous table has left the buffer)
-    if (need > h->frozen_order_pin_cap) {
-        h->frozen_order_pin_cap = 0;
-        if (h->frozen_order_pin.alloc(need, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return; }
-        h->frozen_order_pin_cap = need;
-    }
-    int* order = h->frozen_order_pin;
-    std::vector<int> rest;
-    rest.reserve((size_t)c.n_groups);
-    for (int32_t t = 0; t < n_iters; ++t)
-        for (int b = 0; b < c.n_blocks; ++b) {
-            int* o = order + ((size_t)t * c.n_blocks + b) * c.n_groups;
-            int n_front = 0;
-            rest.clear();
-            for (int g = 0; g < c.n_groups; ++g) {
-                bool mut = false;
-                if (frozen[(size_t)b]) {
-                    const U4 r = draw_block(c.seed, S_GROUP, (uint32_t)b, (uint64_t)(iter0 + t), (uint32_t)(c.group_offset + g), 0u);
-                    mut = u53(r.x, r.y) <= c.beta;
-                }
-                if (mut) o[n_front++] = g; else rest.push_back(g);
-            }
-            for (size_t i = 0; i < rest.size(); ++i) o[n_front + (int)i] = rest[i];
-        }
-    // ordered on the handle's stream behind every kernel that still reads the previous call's table
-    if (hipMemcpyAsync(h->frozen_order_d, order, need * sizeof(int), hipMemcpyHostToDevice, h->stream) != hipSuccess) return;
-    if (hipEventRecord(h->frozen_order_ev, h->stream) != hipSuccess) return;
-    h->frozen_iter0 = iter0; h->frozen_iters = n_iters;
+    h->frozen.iters = 0;
+    const size_t need = frozen_order_entries(setup_of(h), h->mask_runs.data(), h->mask_runs.size(), n_iters);
+    if (need == 0) return;
+    int* order = nullptr;
+    if (h->frozen.table.stage(need, h->stream, &order) != hipSuccess) { (void)hipGetLastError(); return; }
+    fill_frozen_order(h->c, h->mask_runs.data(), h->mask_runs.size(), iter0, n_iters, order);
+    if (h->frozen.table.send(need, h->stream) != hipSuccess) return;
+    h->frozen.iter0 = iter0; h->frozen.iters = n_iters;
 }
 
+// iterations [iter0, iter0 + n_iters) enqueued on the handle's stream, segment by segment (next_segment); nothing is drained
 static int step_body(demc_handle* h, int64_t iter0, int32_t n_iters, bool with_migration) {
     const demc_config& c = h->c;
-    const int n_sweeps = c.n_blocks > 0 ? c.n_blocks : 1;  // block_update! main.jl:174-179
     plan_frozen_order(h, iter0, n_iters);
     h->snap2_iter = -1;  // (a by-product snapshot lives inside one call)
     bool form_ok[N_FORMS];
     for (int f = 0; f < N_FORMS; ++f) form_ok[f] = h->form[f].ok;
     const Form form = choose_form(form_ok, c, h->rp.active, h->cur_glist != nullptr);
-    const int cap = iterations_per_launch(form);
-    for (int64_t iter = iter0; iter < iter0 + n_iters; ++iter) {
-        if (with_migration && migration_due_h(h, iter)) {  // main.jl:85
-            if (c.n_groups_total != c.n_groups || (h->comm && h->own_comm)) {  // (a communicator of one rank takes the same path)
-                if (h->multi) return fail(h, DEMC_EINVAL, "shard of a multi-GPU set: step the set with demc_multi_step");
-                if (!h->comm)
-                    return fail(h, DEMC_EINVAL, "sharded handle without a communicator: demc_comm_init, or drive the exchange with "
-                                                "demc_migration_pack/apply + demc_update");
-                // (history partners: the cells of row t - 1 come from EVERY group, so no subset of the groups may run ahead of the
-                // others by an iteration -- the overlapped form, which lets the unselected groups do exactly that, is not taken)
-                if (h->comm_overlap && !h->rp.active && c.partner_kind != DEMC_PARTNER_HISTORY) {
-                    int run = 1;
-                    while (iter + run < iter0 + n_iters && !migration_due_h(h, iter + run)) ++run;
-                    int rc = exchange_overlapped(h, iter, run);
-                    if (rc != DEMC_OK) return rc;
-                    iter += run - 1;
-                    continue;
-                }
-                int rc = exchange_enqueue(h, iter);
-                if (rc != DEMC_OK) return rc;
-            } else
-                migration_enqueue(h, iter, h->mig_rows, h->mig_rows, true, true);
+    const StepCall call = step_call(h, iter0 + n_iters, with_migration, form);
+    for (int64_t iter = iter0; iter < call.end;) {
+        const Segment seg = next_segment(call, iter);
+        if (seg.migrate == MIG_EXCHANGE || seg.migrate == MIG_OVERLAPPED)
+            if (Refusal r = refuse_exchange(h->multi != nullptr, h->comm != nullptr)) return fail(h, r);
+        int rc = DEMC_OK;
+        if (seg.migrate == MIG_OVERLAPPED)
+            rc = exchange_overlapped(h, iter, seg.run);  // the exchange, and the segment's iterations as its two subset updates
+        else {
+            if (seg.migrate == MIG_LOCAL) migration_enqueue(h, iter, h->mig_rows, h->mig_rows, true, true);  // main.jl:85
+            if (seg.migrate == MIG_EXCHANGE) rc = exchange_enqueue(h, iter);
+            if (rc == DEMC_OK && form != FORM_PHASE) rc = launch_form(h, form, iter, seg.run);  // the segment in one launch
+            for (int b = 0; rc == DEMC_OK && form == FORM_PHASE && b < n_sweeps(c); ++b) {        // ... or one iteration, sweep by sweep
+                const unsigned char* mask = c.n_blocks > 0 ? h->masks + (size_t)b * c.D : nullptr;
+                rc = run_sweep(h, iter, (unsigned)b, mask, stored_row(c, h->hist.get() != nullptr, iter, b));
+            }
         }
-        if (form != FORM_PHASE) {  // every iteration up to the next migration, or to the form's cap, in one launch
-            int run = 1;
-            while (run < cap && iter + run < iter0 + n_iters && !(with_migration && migration_due_h(h, iter + run))) ++run;
-            int rc = launch_form(h, form, iter, run);
-            if (rc != DEMC_OK) return rc;
-            iter += run - 1;
-            continue;
-        }
-        for (int b = 0; b < n_sweeps; ++b) {
-            const unsigned char* mask = c.n_blocks > 0 ? h->masks + (size_t)b * c.D : nullptr;
-            const long long row = iter - 1;
-            const long long store_row = (b == n_sweeps - 1 && h->hist && row < c.n_rows) ? row : -1;
-            int rc = run_sweep(h, iter, (unsigned)b, mask, store_row);
-            if (rc != DEMC_OK) return rc;
-        }
+        if (rc != DEMC_OK) return rc;
+        iter += seg.run;
     }
     HIPCHK(hipGetLastError());
     return DEMC_OK;
 }
 
 static int step_checks(demc_handle* h, int64_t iter0, int32_t n_iters) {
-    if (h->m.family < 0) return fail(h, DEMC_EINVAL, "demc_set_model has not been called");
-    if (iter0 < 1 || n_iters < 0) return fail(h, DEMC_EINVAL, "iter0 is 1-based (de.iter, main.jl:34)");
-    if (h->c.partner_kind == DEMC_PARTNER_HISTORY && iter0 < 2)
-        return fail(h, DEMC_EINVAL, "history partners need at least one stored row (n_initial > 0)");
-    // resample draws cells of rows 1:(iter-1) (crossover.jl:116-118): every one of them must lie inside the history buffer
-    if (h->c.partner_kind == DEMC_PARTNER_HISTORY && n_iters > 0 && iter0 + (int64_t)n_iters - 2 > h->c.n_rows)
-        return fail(h, DEMC_EINVAL, "history partners: iteration t reads history rows 1:(t-1), the history holds n_rows rows "
-                                    "(the reference sizes it n_iter + n_initial, utilities.jl:34)");
+    if (Refusal r = refuse_step(h->c, h->m.family >= 0, iter0, n_iters)) return fail(h, r);
     return DEMC_OK;
 }
 
@@ -1707,91 +1609,44 @@ int32_t demc_update_groups_async(demc_handle* h, int64_t iter0, int32_t n_iters,
     USE_DEVICE(h);
     int rc = step_checks(h, iter0, n_iters);
     if (rc != DEMC_OK) return rc;
-    if (h->c.partner_kind == DEMC_PARTNER_HISTORY && n_iters > 1)
-        return fail(h, DEMC_EINVAL, "history partners: a subset of the groups advances one iteration at a time (the cells of a history "
-                                    "row come from every group: update the other groups before the next iteration)");
+    if (Refusal r = refuse_subset_call(h->c, n_iters)) return fail(h, r);
     return update_subset(h, iter0, n_iters, groups, n);
     });
 }
 
 int32_t demc_migration_groups(const demc_config* cfg, int64_t iter, int32_t* sel, int32_t* n_sel) {
     if (!cfg || !sel || !n_sel) return DEMC_EINVAL;
-    // select_groups (migration.jl:31-35) exactly as k_mig_apply draws it: N = rand(2:n_groups), ordered sample without
-    // replacement by a partial Fisher-Yates shuffle, words from the STEP stream
-    const int ng = cfg->n_groups_total > 0 ? cfg->n_groups_total : cfg->n_groups;
     *n_sel = 0;
-    if (ng < 2) return DEMC_OK;
     try {
-        std::vector<int> perm((size_t)ng);
-        for (int i = 0; i < ng; ++i) perm[(size_t)i] = i;
-        const U4 r0 = draw_block(cfg->seed, S_STEP, 0, (uint64_t)iter, 0, 0);
-        const int ns = 2 + (int)mulhi32(r0.z, (uint32_t)(ng - 1));
-        U4 r = r0;
-        for (int i = 0; i < ns; ++i) {
-            if ((i & 3) == 0) r = draw_block(cfg->seed, S_STEP, 0, (uint64_t)iter, 0, 1 + (uint32_t)(i >> 2));
-            const uint32_t w = (i & 3) == 0 ? r.x : (i & 3) == 1 ? r.y : (i & 3) == 2 ? r.z : r.w;
-            const int j = i + (int)mulhi32(w, (uint32_t)(ng - i));
-            std::swap(perm[(size_t)i], perm[(size_t)j]);
-        }
-        for (int i = 0; i < ns; ++i) sel[i] = perm[(size_t)i];
-        *n_sel = ns;
+        std::vector<int> perm((size_t)std::max(groups_total(*cfg), 1));
+        *n_sel = select_groups(*cfg, iter, perm.data(), sel);
     } catch (...) {
         return DEMC_ENOMEM;
     }
     return DEMC_OK;
 }
 
-int32_t demc_migration_due(const demc_config* cfg, int64_t iter) {
-    if (!cfg) return 0;
-    const int ngt = cfg->n_groups_total > 0 ? cfg->n_groups_total : cfg->n_groups;
-    const double alpha = ngt == 1 ? 0.0 : cfg->alpha;
-    const U4 r = draw_block(cfg->seed, S_STEP, 0, (uint64_t)iter, 0, 0);
-    return u53(r.x, r.y) <= alpha ? 1 : 0;
-}
+int32_t demc_migration_due(const demc_config* cfg, int64_t iter) { return cfg && migration_due(*cfg, iter) ? 1 : 0; }
 
-int32_t demc_migration_pack(demc_handle* h, int64_t iter, double* dev_rows) {
+// One half of migration! around the caller's exchange: select_particle into pack_rows (pack), or select_groups + shift_particles!
+// from all_rows, the rows of all groups (apply).  The drained entry points take a null pointer for the handle's own buffer.
+static int32_t migration_half(demc_handle* h, int64_t iter, bool pack, double* pack_rows, const double* all_rows, bool drained) {
     return guarded(h, [&]() -> int32_t {
-    if (!h) return DEMC_EINVAL;
+    if (!h || (!drained && !(pack ? pack_rows : all_rows))) return DEMC_EINVAL;
     USE_DEVICE(h);
-    migration_enqueue(h, iter, dev_rows ? dev_rows : h->mig_rows, nullptr, true, false);
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipGetLastError());
-    return DEMC_OK;
-    });
-}
-
-int32_t demc_migration_apply(demc_handle* h, int64_t iter, const double* dev_all_rows) {
-    return guarded(h, [&]() -> int32_t {
-    if (!h) return DEMC_EINVAL;
-    USE_DEVICE(h);
-    if (!dev_all_rows && h->c.n_groups_total != h->c.n_groups)
+    if (!pack && !all_rows && h->c.n_groups_total != h->c.n_groups)
         return fail(h, DEMC_EINVAL, "sharded handle needs the all-gathered rows");
-    migration_enqueue(h, iter, nullptr, dev_all_rows ? dev_all_rows : h->mig_rows, false, true);
-    HIPCHK(hipStreamSynchronize(h->stream));
+    if (pack) migration_enqueue(h, iter, pack_rows ? pack_rows : h->mig_rows.get(), nullptr, true, false);
+    else migration_enqueue(h, iter, nullptr, all_rows ? all_rows : h->mig_rows.get(), false, true);
+    if (drained) HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipGetLastError());
     return DEMC_OK;
     });
 }
-
-int32_t demc_migration_pack_async(demc_handle* h, int64_t iter, double* dev_rows) {
-    return guarded(h, [&]() -> int32_t {
-    if (!h || !dev_rows) return DEMC_EINVAL;
-    USE_DEVICE(h);
-    migration_enqueue(h, iter, dev_rows, nullptr, true, false);
-    HIPCHK(hipGetLastError());
-    return DEMC_OK;
-    });
-}
-
-int32_t demc_migration_apply_async(demc_handle* h, int64_t iter, const double* dev_all_rows) {
-    return guarded(h, [&]() -> int32_t {
-    if (!h || !dev_all_rows) return DEMC_EINVAL;
-    USE_DEVICE(h);
-    migration_enqueue(h, iter, nullptr, dev_all_rows, false, true);
-    HIPCHK(hipGetLastError());
-    return DEMC_OK;
-    });
-}
+int32_t demc_migration_pack(demc_handle* h, int64_t iter, double* dev_rows) { return migration_half(h, iter, true, dev_rows, nullptr, true); }
+int32_t demc_migration_apply(demc_handle* h, int64_t iter, const double* dev_all_rows) { return migration_half(h, iter, false, nullptr, dev_all_rows, true); }
+int32_t demc_migration_pack_async(demc_handle* h, int64_t iter, double* dev_rows) { return migration_half(h, iter, true, dev_rows, nullptr, false); }
+int32_t demc_migration_apply_async(demc_handle* h, int64_t iter, const double* dev_all_rows) { return migration_half(h, iter, false, nullptr, dev_all_rows, false); }
 
 // ---- the communicator behind the boundary (SURVEY 8b "demc_create_multi / DEMC_ERCCL", 8e) ----
 int32_t demc_comm_unique_id(void* id_out, int32_t nbytes) {
@@ -2084,12 +1939,13 @@ int32_t demc_multi_step(demc_multi* m, int64_t iter0, int32_t n_iters) {
         if (rc != DEMC_OK) return mshard_fail(m, r, rc);
     }
     demc_handle* h0 = m->shard[0];
-    for (int64_t it = iter0; it < iter0 + n_iters;) {
-        // the alpha coin is a pure function of (seed, iteration): every shard sees the same runs (main.jl:85)
-        const bool due = n > 1 && migration_due_h(h0, it);
-        int run = 1;
-        while (it + run < iter0 + n_iters && !(n > 1 && migration_due_h(h0, it + run))) ++run;
-        if (due) {
+    // The set's own segments: the alpha coin is a pure function of (seed, iteration), so every shard sees the same runs
+    // (main.jl:85).  The coins count only between shards, and the segments are uncapped: every shard caps its own launches.
+    const StepCall call = set_call(step_call(h0, iter0 + n_iters, true, FORM_PHASE), n);
+    for (int64_t it = iter0; it < call.end;) {
+        const Segment seg = next_segment(call, it);
+        const int run = seg.run;
+        if (seg.migrate == MIG_EXCHANGE) {
             const int rc = multi_exchange(m, it);
             if (rc != DEMC_OK) return rc;
         }
@@ -2152,7 +2008,7 @@ int32_t demc_logpost(demc_handle* h, const double* theta, int64_t n, double* out
     return guarded(h, [&]() -> int32_t {
     if (!h || !theta || !out || n < 0) return DEMC_EINVAL;
     USE_DEVICE(h);
-    if (h->m.family < 0) return fail(h, DEMC_EINVAL, "demc_set_model has not been called");
+    if (Refusal r = refuse_without_model(h->m.family >= 0)) return fail(h, r);
     const size_t P = (size_t)h->P, D = (size_t)h->c.D;
     std::vector<double> w(P);
     for (int64_t off = 0; off < n; off += (int64_t)P) {

@@ -2,7 +2,7 @@
 // malloc / free, so every create and every release is seen, and a release too many or too few is a miscount here and a
 // double free or a leak to the address sanitizer the program is built with (tests/test_devmem_host.py).  No HIP runtime is linked.
 // The end of a call (finish) and the pass timer of the diagnostic variant (PassTrace) run over stubs as well: a stream on which
-// nothing is pending, events that carry the time of their mark.
+// nothing is pending, events that carry the time of their mark.  StagedList runs over the same stubs, which count its waits.
 #define DEMC_PASS_TRACE  // the variant that measures; without it PassTrace is two empty functions
 #include "demc_devmem.hpp"
 
@@ -19,10 +19,15 @@ hipError_t launch_error = hipSuccess, sync_error = hipSuccess;  // what hipGetLa
 int copies = 0, copies_left = -1;  // hipMemcpy fails once this many have succeeded (-1: never)
 int events_left = -1;              // likewise hipEventCreateWithFlags
 float now_ms = 0.f;                // the time an event records
+int pin_allocs_left = -1;          // likewise hipHostMalloc
+int event_waits = 0, stream_waits = 0, async_copies = 0;  // hipEventSynchronize / hipStreamSynchronize / hipMemcpyAsync calls seen
+hipError_t event_wait_error = hipSuccess;
 
 hipError_t make(Kind k, void** out, size_t bytes) {
     if (k == DEV && dev_allocs_left == 0) return hipErrorOutOfMemory;
     if (k == DEV && dev_allocs_left > 0) --dev_allocs_left;
+    if (k == PIN && pin_allocs_left == 0) return hipErrorOutOfMemory;
+    if (k == PIN && pin_allocs_left > 0) --pin_allocs_left;
     *out = std::malloc(bytes ? bytes : 1);
     ++made[k];
     return hipSuccess;
@@ -52,7 +57,13 @@ hipError_t hipEventElapsedTime(float* ms, hipEvent_t a, hipEvent_t b) {
     return hipSuccess;
 }
 hipError_t hipGetLastError() { return launch_error; }
-hipError_t hipStreamSynchronize(hipStream_t) { return sync_error; }
+hipError_t hipStreamSynchronize(hipStream_t) { ++stream_waits; return sync_error; }
+hipError_t hipEventSynchronize(hipEvent_t) { ++event_waits; return event_wait_error; }
+hipError_t hipMemcpyAsync(void* dst, const void* src, size_t n, hipMemcpyKind, hipStream_t) {
+    std::memcpy(dst, src, n);
+    ++async_copies;
+    return hipSuccess;
+}
 hipError_t hipMemcpy(void* dst, const void* src, size_t n, hipMemcpyKind) {
     if (copies_left == 0) return hipErrorInvalidValue;
     if (copies_left > 0) --copies_left;
@@ -222,6 +233,65 @@ void pass_trace() {
     }
     CHECK(freed[EVT] == f0 + 4);
 }
+
+// StagedList: a device copy, a pinned host copy and the event between them, with their capacities
+void staged_list() {
+    const int dev0 = live(DEV), pin0 = live(PIN), evt0 = live(EVT);
+    {
+        StagedList<int> l;
+        CHECK(!l.dev && !l.pin && !l.ev && l.dev_cap == 0 && l.pin_cap == 0);
+        int* host = nullptr;
+        int waits = event_waits, drains = stream_waits;
+        CHECK(l.stage(4, nullptr, &host) == hipSuccess && host && host == l.pin.get() && l.dev && l.ev && l.dev_cap == 4 && l.pin_cap == 4);
+        CHECK(live(DEV) == dev0 + 1 && live(PIN) == pin0 + 1 && live(EVT) == evt0 + 1);
+        CHECK(event_waits == waits + 1 && stream_waits == drains);  // (no device buffer yet: no kernel to wait for)
+        for (int i = 0; i < 4; ++i) host[i] = 10 + i;
+        const int copied = async_copies;
+        CHECK(l.send(4, nullptr) == hipSuccess && async_copies == copied + 1 && l.dev.get()[3] == 13);
+        // the staging pointer again: the event is waited for before the caller rewrites the host buffer; nothing is allocated
+        const int made_dev = made[DEV], made_pin = made[PIN], made_evt = made[EVT];
+        waits = event_waits;
+        CHECK(l.stage(3, nullptr, &host) == hipSuccess && host == l.pin.get() && event_waits == waits + 1);
+        CHECK(made[DEV] == made_dev && made[PIN] == made_pin && made[EVT] == made_evt && stream_waits == drains && l.dev_cap == 4);
+        // growing: the stream is waited for before the device buffer a kernel may still read goes; each old buffer is released once
+        const int freed_dev = freed[DEV], freed_pin = freed[PIN];
+        CHECK(l.stage(10, nullptr, &host) == hipSuccess && host && l.dev_cap == 10 && l.pin_cap == 10);
+        CHECK(stream_waits == drains + 1 && freed[DEV] == freed_dev + 1 && freed[PIN] == freed_pin + 1 && live(DEV) == dev0 + 1 && live(PIN) == pin0 + 1);
+        host[9] = 99;
+        CHECK(l.send(10, nullptr) == hipSuccess && l.dev.get()[9] == 99);
+        // an event that cannot be waited for, a stream that cannot: reported, nothing changed
+        event_wait_error = hipErrorInvalidValue;
+        CHECK(l.stage(2, nullptr, &host) == hipErrorInvalidValue && host == nullptr && l.dev_cap == 10 && l.pin_cap == 10 && l.dev && l.pin);
+        event_wait_error = hipSuccess; sync_error = hipErrorInvalidValue;
+        CHECK(l.stage(11, nullptr, &host) == hipErrorInvalidValue && host == nullptr && l.dev_cap == 10 && l.pin_cap == 10 && l.dev && l.pin);
+        sync_error = hipSuccess;
+        // a failed hipMalloc: the device side is empty with no capacity, the host side unchanged; the next call allocates again
+        dev_allocs_left = 0;
+        CHECK(l.stage(20, nullptr, &host) == hipErrorOutOfMemory && host == nullptr && !l.dev && l.dev_cap == 0 && l.pin && l.pin_cap == 10);
+        CHECK(live(DEV) == dev0 && live(PIN) == pin0 + 1);
+        dev_allocs_left = -1;
+        drains = stream_waits;
+        CHECK(l.stage(5, nullptr, &host) == hipSuccess && host && l.dev_cap == 5 && l.pin_cap == 10 && stream_waits == drains);
+        // a failed hipHostMalloc: the host side is empty with no capacity, and no pointer is handed out
+        pin_allocs_left = 0;
+        CHECK(l.stage(30, nullptr, &host) == hipErrorOutOfMemory && host == nullptr && l.dev_cap == 30 && !l.pin && l.pin_cap == 0);
+        pin_allocs_left = -1;
+        CHECK(l.stage(30, nullptr, &host) == hipSuccess && host && l.pin_cap == 30 && live(DEV) == dev0 + 1 && live(PIN) == pin0 + 1);
+    }
+    CHECK(live(DEV) == dev0 && live(PIN) == pin0 && live(EVT) == evt0);  // destroyed: everything released
+    {
+        StagedList<int> l;  // an event that cannot be created: nothing is allocated
+        int* host = nullptr;
+        events_left = 0;
+        CHECK(l.stage(4, nullptr, &host) == hipErrorOutOfMemory && host == nullptr && !l.ev && !l.dev && !l.pin && l.dev_cap == 0 && l.pin_cap == 0);
+        events_left = -1;
+        CHECK(live(DEV) == dev0 && live(PIN) == pin0 && live(EVT) == evt0);
+        StagedList<int> ring[3];  // a ring sized once, as the handle's group lists are
+        for (StagedList<int>& r : ring) CHECK(r.stage(7, nullptr, &host) == hipSuccess);
+        CHECK(live(DEV) == dev0 + 3 && live(PIN) == pin0 + 3 && live(EVT) == evt0 + 3);
+    }
+    CHECK(live(DEV) == dev0 && live(PIN) == pin0 && live(EVT) == evt0);
+}
 }  // namespace
 
 int main() {
@@ -231,6 +301,7 @@ int main() {
     failed_allocations();
     call_endings();
     pass_trace();
+    staged_list();
     for (int k = 0; k < N_KINDS; ++k) {
         CHECK(made[k] > 0);
         CHECK(live((Kind)k) == 0);

@@ -18,13 +18,13 @@ from conftest import make_problem, setup_engine
 pytestmark = pytest.mark.gpu
 
 
-def tiny_engine(demc, fam, Np, history=False, blocks=None, **cfg):
-    """2 groups of Np particles on 64 observations, ready to step (with history partners: behind two prior rows, burnin = 3)"""
+def tiny_engine(demc, fam, Np, history=False, blocks=None, n_groups=2, alpha=0.0, **cfg):
+    """n_groups (2) groups of Np particles on 64 observations, ready to step (with history partners: behind two prior rows, burnin = 3)"""
     prob = make_problem(fam[0], np.random.default_rng(17), **fam[1])
-    P = 2 * Np
+    P = n_groups * Np
     if history:
         cfg = dict(schedule=1, partner_kind=1, n_initial=2, burnin=3, **cfg)
-    eng = demc.HipEngine(n_groups=2, Np=Np, D=prob["D"], n_rows=8, seed=11, alpha=0.0, **cfg)
+    eng = demc.HipEngine(n_groups=n_groups, Np=Np, D=prob["D"], n_rows=8, seed=11, alpha=alpha, **cfg)
     setup_engine(eng, prob)
     if blocks is not None:
         eng.set_blocks(blocks)
@@ -160,16 +160,47 @@ def test_trace_on_a_per_observation_family_takes_the_general_resident_kernel(dem
     assert names_of(demc, gauss, 8, trace=1) == ["k_propose<256,true,TAIL_OBS,true,false>"] * 2
 
 
-@pytest.mark.parametrize("cfg,n,cap,kernel", [(dict(loglike_mode=1), 1100, 1024, "k_res_mvn<256,false,8>"),
-                                              (dict(loglike_mode=0, theta_snooker=0.1), 200, 64, "k_propose<256,true,TAIL_PREP_MFMA,true,2,true>")])
-def test_iterations_per_launch_follow_the_form(demc, cfg, n, cap, kernel):
+MVN8_SUFFSTAT, MVN8_STREAM = "k_res_mvn<256,false,8>", "k_propose<256,true,TAIL_PREP_MFMA,true,2,true>"
+
+
+@pytest.mark.parametrize("cfg,n,cap,kernel,alpha", [
+    pytest.param(dict(loglike_mode=1), 1100, 1024, MVN8_SUFFSTAT, 0.0, id=f"cfg0-1100-1024-{MVN8_SUFFSTAT}"),
+    pytest.param(dict(loglike_mode=0, theta_snooker=0.1), 200, 64, MVN8_STREAM, 0.0, id=f"cfg1-200-64-{MVN8_STREAM}"),
+    pytest.param(dict(loglike_mode=1), 200, 1024, MVN8_SUFFSTAT, 0.5, id="cap1024-migrating"),
+    pytest.param(dict(loglike_mode=0, theta_snooker=0.1), 200, 64, MVN8_STREAM, 0.5, id="cap64-migrating"),
+    pytest.param(dict(loglike_mode=1), 200, 1024, MVN8_SUFFSTAT, 0.02, id="cap1024-migrating-rarely"),
+    pytest.param(dict(loglike_mode=0, theta_snooker=0.1), 200, 64, MVN8_STREAM, 0.02, id="cap64-migrating-rarely")])
+def test_iterations_per_launch_follow_the_form(demc, cfg, n, cap, kernel, alpha):
     """one launch carries at most 1024 iterations, 64 where the workgroups of a group wait on each other (the streaming-resident
-    forms): n iterations without a migration are ceil(n / cap) launches"""
-    eng = tiny_engine(demc, mvn(8), 8, **cfg)
+    forms): n iterations without a migration (demc_update, 2 groups) are ceil(n / cap) launches.  With migrations (demc_step,
+    4 groups) the launches are the segments of the call (csrc/demc_schedule.hpp; DESIGN.md "The schedule of a step call"): a launch
+    ends at the form's cap, in front of the next due alpha coin, or with the call.  At alpha = 0.5 the coins end every launch; at
+    alpha = 0.02 (seed 11: four coins, then more than 64 iterations without one) the cap of 64 ends some and that of 1024 none.  The
+    segments are counted here from eng.migration_due by that rule and asked of the host program of the CPU tests (built here
+    without its sanitizers); K1 is launched once per segment and the migration kernels once per due coin."""
+    import test_schedule_host as S
+    migrating = alpha > 0.0
+    eng = tiny_engine(demc, mvn(8), 8, n_groups=4 if migrating else 2, alpha=alpha, **cfg)
+    due = [it for it in range(1, n + 1) if migrating and eng.migration_due(it)]
     eng.timing_enable()
-    eng.update(1, n)
-    launches = eng.timing_read()["propose"]["launches"]
+    (eng.step if migrating else eng.update)(1, n)
+    timing = eng.timing_read()
     name = eng.last_kernels()
     eng.close()
     assert name == kernel
-    assert launches == -(-n // cap)
+    runs, it = [], 1
+    while it <= n:  # up to the cap, to the iteration in front of the next due coin, or to the end
+        run = min([cap, n + 1 - it] + [d - it for d in due if d > it][:1])
+        runs.append((run, S.LOCAL if it in due else S.NONE))
+        it += run
+    if not migrating:
+        assert len(runs) == -(-n // cap)
+    elif alpha == 0.5:
+        assert 60 < len(due) < 140 and len(runs) > len(due) // 2
+    else:  # a migration and the cap in one call: the cap ends a launch exactly where it is 64
+        assert len(due) >= 3 and n - due[-1] > 64
+        assert (max(run for run, _ in runs) == cap) == (cap == 64) and (len(runs) > len(due) + 1) == (cap == 64)
+    assert runs == S.segments(sanitized=False, seed=11, alpha=alpha, n_groups_total=4 if migrating else 2, n_groups=4 if migrating else 2, iter0=1, n_iters=n,
+                              with_migration=migrating, cap=cap)
+    assert timing["propose"]["launches"] == len(runs)
+    assert timing["migration"]["launches"] == len(due)
