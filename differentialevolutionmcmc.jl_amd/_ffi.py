@@ -32,6 +32,9 @@ QUANTILE_EXPORTS = ["demc_quantiles"]  # include/demc_quantile.h: the second tab
 QUANTILE_MAX_PROBS = 16  # DEMC_QUANTILE_MAX_PROBS
 COV_EXPORTS = ["demc_covariance"]  # include/demc_cov.h: cov(chains) / cor(chains)
 COV_MAX_COLS = 64  # DEMC_COV_MAX_COLS
+PW_EXPORTS = ["demc_pointwise_loglik", "demc_waic"]  # include/demc_pointwise.h: per-observation log-densities, WAIC
+WAIC_NTOTAL, WAIC_NPOINT = 8, 4  # DEMC_WAIC_NTOTAL, DEMC_WAIC_NPOINT
+PW_MAX_CELLS = 1 << 27  # DEMC_PW_MAX_CELLS
 COMM_ID_BYTES = 128
 _NOT_STATUS = {"demc_last_error": C.c_char_p, "demc_multi_last_error": C.c_char_p, "demc_multi_shard": C.c_void_p}
 
@@ -149,6 +152,8 @@ def load():
     L.demc_summarize.argtypes = [H, C.c_int64, C.c_int64, C.c_int32, _dp, _dp, C.c_int64]
     L.demc_quantiles.argtypes = [H, C.c_int64, C.c_int64, _dp, C.c_int32, _dp]
     L.demc_covariance.argtypes = [H, C.c_int64, C.c_int64, C.POINTER(C.c_int32), C.c_int32, _dp, _dp, _dp]
+    L.demc_pointwise_loglik.argtypes = [H, _dp, C.c_int64, _dp]
+    L.demc_waic.argtypes = [H, C.c_int64, C.c_int64, _dp, _dp]
     L.demc_step.argtypes = [H, C.c_int64, C.c_int32]
     L.demc_update.argtypes = [H, C.c_int64, C.c_int32]
     L.demc_migration_due.argtypes = [C.POINTER(DemcConfig), C.c_int64]
@@ -181,7 +186,7 @@ def load():
     L.demc_multi_size.argtypes = [H]
     L.demc_multi_shard.argtypes = [H, C.c_int32]
     L.demc_multi_step.argtypes = [H, C.c_int64, C.c_int32]
-    for name in EXPORTS + SUMMARY_EXPORTS + QUANTILE_EXPORTS + COV_EXPORTS:  # every entry point returns an int32 status, except the error strings and the shard accessor
+    for name in EXPORTS + SUMMARY_EXPORTS + QUANTILE_EXPORTS + COV_EXPORTS + PW_EXPORTS:  # every entry point returns an int32 status, except the error strings and the shard accessor
         getattr(L, name).restype = _NOT_STATUS.get(name, C.c_int32)
     _lib = L
     return L
@@ -232,6 +237,8 @@ class HipEngine:
                 warnings.warn(note.decode()[6:], stacklevel=2)
         self.P = self.cfg.n_groups * self.cfg.Np
         self.D = self.cfg.D
+        self.n_obs = 1
+        self.family = None  # the DEMC_FAM_* code of set_model (None: no model, or one set from source / by a simulator)
 
     def close(self):
         if getattr(self, "h", None):
@@ -258,6 +265,8 @@ class HipEngine:
         hyper = None if hyper is None else np.ascontiguousarray(np.asarray(hyper, dtype=np.float64).ravel())
         self._ck(self.L.demc_set_model(self.h, family, _d(data), dims.ctypes.data_as(_lp), dims.size, _d(hyper),
                                        0 if hyper is None else hyper.size))
+        self.n_obs = int(dims[0]) if dims.size else 1  # observations of the model (the per-observation calls size their outputs by it)
+        self.family = int(family)
 
     def set_model_source(self, source, data, dims, hyper=None):
         """user log-density plug-in: HIP source defining demc_user_obs(...) (include/demc.h), JIT-compiled for gfx950"""
@@ -266,6 +275,7 @@ class HipEngine:
         hyper = None if hyper is None else np.ascontiguousarray(np.asarray(hyper, dtype=np.float64).ravel())
         self._ck(self.L.demc_set_model_source(self.h, source.encode(), _d(data), dims.ctypes.data_as(_lp), dims.size,
                                               _d(hyper), 0 if hyper is None else hyper.size))
+        self.family = None
 
     def set_model_source_row(self, source, data, dims, hyper=None, has_prior=False):
         """whole-row plug-in: HIP source defining demc_user_loglike_row(...) [and demc_user_prior_row(...)] (include/demc.h)"""
@@ -274,6 +284,7 @@ class HipEngine:
         hyper = None if hyper is None else np.ascontiguousarray(np.asarray(hyper, dtype=np.float64).ravel())
         self._ck(self.L.demc_set_model_source_row(self.h, source.encode(), _d(data), dims.ctypes.data_as(_lp), dims.size,
                                                   _d(hyper), 0 if hyper is None else hyper.size, 1 if has_prior else 0))
+        self.family = None
 
     def set_model_sim(self, simulator, estimator, n_sim, data, hyper=None, source=None):
         """simulation-based likelihood (demc_set_model_sim, include/demc.h): `simulator` / `estimator` are the DEMC_SIM_* /
@@ -287,6 +298,7 @@ class HipEngine:
         n_obs = data.size // 2 if estimator == 2 else data.size
         self._ck(self.L.demc_set_model_sim(self.h, simulator, estimator, n_sim, None if source is None else source.encode(),
                                            _d(data), n_obs, _d(hyper), 0 if hyper is None else hyper.size))
+        self.family = None
 
     def set_priors(self, kind, a, b, ref=None):
         kind = np.ascontiguousarray(kind, dtype=np.int32)
@@ -380,6 +392,39 @@ class HipEngine:
         mean, cov, cor = np.empty(k), np.empty((k, k)), np.empty((k, k))
         self._ck(self.L.demc_covariance(self.h, row0, row1, cp, K, _d(mean), _d(cov), _d(cor)))
         return mean, cov, cor
+
+    def pointwise_loglik(self, theta):
+        """out[s][i] = log p(y_i | theta[s]) for the rows theta[n][D] (demc_pointwise_loglik of include/demc_pointwise.h, DESIGN.md
+        5.8), observations in the order they were passed to set_model; a row outside the bounds in force is a row of NaN"""
+        theta = np.ascontiguousarray(theta, dtype=np.float64).reshape(-1, self.D)
+        out = np.empty((theta.shape[0], self.n_obs))
+        self._ck(self.L.demc_pointwise_loglik(self.h, _d(theta), theta.shape[0], _d(out)))
+        return out
+
+    def waic_served(self):
+        """what demc_waic would refuse about this handle whatever the rows, asked BEFORE a run (summarize(..., waic=True)): raises the
+        DemcError the call itself would end in -- an unserved family, MvNormal outside DIRECT mode, no observations, a sharded handle.
+        The call remains the judge: this only spares a run whose last step is certain to be refused."""
+        from . import families as F
+        who = "demc_waic: "
+        mvn = self.family in (F.FAM_MVN_ISO, F.FAM_MVN_FULL)
+        if self.family not in (F.FAM_GAUSSIAN, F.FAM_BINOMIAL, F.FAM_LNR, F.FAM_LBA) and not mvn:
+            raise DemcError(EUNSUPPORTED, who + "this model has no per-observation log-density on the device (served: Gaussian, Binomial, LNR, LBA, "
+                                                "MvNormal with loglike_mode = direct)")
+        if mvn and self.cfg.loglike_mode != 2:
+            raise DemcError(EUNSUPPORTED, who + "the MvNormal families answer per observation only with loglike_mode = direct")
+        if self.n_obs < 1:
+            raise DemcError(EINVAL, who + "the model holds no observations (N < 1)")
+        if self.cfg.n_groups_total != self.cfg.n_groups:
+            raise DemcError(EINVAL, who + "sharded handle")
+
+    def waic(self, row0, row1, pointwise=False):
+        """WAIC of history rows [row0,row1) formed on the device (demc_waic of include/demc_pointwise.h), chains
+        pooled -> (totals[8] in the order of chains.WAIC_TOTALS, pointwise[N][4] = lppd_i, p_waic_i, mean_i, elpd_i or None)"""
+        tot = np.empty(WAIC_NTOTAL)
+        pt = np.empty((self.n_obs, WAIC_NPOINT)) if pointwise else None
+        self._ck(self.L.demc_waic(self.h, row0, row1, _d(tot), _d(pt)))
+        return tot, pt
 
     def step(self, iter0, n_iters=1):
         self._ck(self.L.demc_step(self.h, iter0, n_iters))

@@ -2,7 +2,8 @@
 summary statistics the reference's tests read from describe(chains)[1] (:mean, :std, :rhat), plus the effective sample size,
 its Monte-Carlo standard error and the autocorrelation MCMCChains adds to them (DESIGN.md section 5.5 is the definition; the device
 computes the same numbers from the history without exporting it: demc_summarize), the quantile table of describe(chains)
-(demc_quantiles on the device), and cov(chains) / cor(chains) (demc_covariance)."""
+(demc_quantiles on the device), cov(chains) / cor(chains) (demc_covariance), and WAIC from
+the per-observation log-densities (demc_waic)."""
 import math
 
 import numpy as np
@@ -10,16 +11,20 @@ import numpy as np
 SUMMARY_COLS = ("mean", "std", "rhat", "ess", "mcse", "pairs")  # the columns of demc_summarize's out (DEMC_SUMMARY_COLS)
 DEFAULT_QUANTILES = (0.025, 0.25, 0.5, 0.75, 0.975)  # MCMCChains' describe(chains)[2]
 COV_MAX_COLS = 64  # DEMC_COV_MAX_COLS: the series one call of demc_covariance takes
+WAIC_TOTALS = ("elpd_waic", "se_elpd", "p_waic", "lppd", "waic", "dbar", "n_high", "n_nonfinite")  # demc_waic's total_out, in order
+WAIC_POINT = ("lppd", "p_waic", "mean", "elpd")  # the columns of demc_waic's pointwise_out (DEMC_WAIC_NPOINT)
 
 
 class Summary:
     """The summary table of a run: `values[j]` = (mean, std, rhat, ess, mcse, pairs) of series names[j] -- the parameters,
     then acceptance and lp.  `rho` (or None): [series][lags] autocorrelations, NaN beyond the lags that were evaluated.
     `quantiles` (or None): [series][len(probs)] quantiles at `probs`, chains pooled.  `cov_matrix` / `cor_matrix`
-    (or None): the covariance and correlation of the series `cov_names`, chains pooled."""
+    (or None): the covariance and correlation of the series `cov_names`, chains pooled.  `waic` (or None): the Waic
+    record of the same rows."""
 
     def __init__(self, names, values, internals=("acceptance", "lp"), rho=None, quantiles=None, probs=None, cov=None, cor=None,
-                 cov_names=None):
+                 cov_names=None, waic=None):
+        self.waic = waic
         self.names = list(names)
         self.values = np.asarray(values, dtype=np.float64).reshape(len(self.names), len(SUMMARY_COLS))
         self.internals = list(internals)
@@ -56,6 +61,69 @@ class Summary:
         if self.cor_matrix is None:
             raise ValueError("this Summary holds no correlation: summarize(..., cor=True)")
         return list(self.cov_names), self.cor_matrix
+
+
+class Waic:
+    """The eight totals of demc_waic by name (WAIC_TOTALS) and, when it was asked for, the table pointwise[N][4] = (lppd_i, p_waic_i,
+    mean_i, elpd_i) in the caller's observation order."""
+
+    def __init__(self, totals, pointwise=None):
+        totals = np.asarray(totals, dtype=np.float64).reshape(len(WAIC_TOTALS))
+        for nm, v in zip(WAIC_TOTALS, totals):
+            setattr(self, nm, float(v))
+        self.totals = totals
+        self.pointwise = None if pointwise is None else np.asarray(pointwise, dtype=np.float64).reshape(-1, len(WAIC_POINT))
+
+    def __repr__(self):
+        s = (f"Waic(elpd_waic={self.elpd_waic:.2f} (se {self.se_elpd:.2f}), p_waic={self.p_waic:.2f}, lppd={self.lppd:.2f}, "
+             f"waic={self.waic:.2f}, dbar={self.dbar:.2f}")
+        if self.n_high:
+            s += f", {int(self.n_high)} observations with p_waic > 0.4"
+        if self.n_nonfinite:
+            s += f", {int(self.n_nonfinite)} observations not finite"
+        return s + ")"
+
+
+def waic_from_loglik(ll):
+    """DESIGN.md 5.8 on the host: ll[S][N] = log p(y_i | theta_s) -> Waic with its pointwise table.  The sums over the draws and
+    over the observations run in np.longdouble; the results are rounded to float64 at the end."""
+    ll = np.asarray(ll, dtype=np.float64)
+    if ll.ndim != 2 or ll.shape[0] < 1 or ll.shape[1] < 1:
+        raise ValueError("waic_from_loglik needs ll[S][N] with S >= 1 and N >= 1")
+    S, N = ll.shape
+    L = ll.astype(np.longdouble)
+    nan = np.longdouble("nan")
+    with np.errstate(all="ignore"):
+        isnan = np.isnan(L).any(axis=0)
+        bad = isnan | np.isneginf(L).any(axis=0)
+        M = np.where(isnan, nan, np.max(np.where(np.isnan(L), -np.inf, L), axis=0))
+        dead = np.isneginf(M)  # every draw -Inf
+        E = np.exp(np.where(np.isneginf(L), -np.inf, L - np.where(dead | isnan, 0, M))).sum(axis=0)
+        lppd = np.where(dead, -np.inf, M + np.log(E) - np.log(np.longdouble(S)))
+        lppd = np.where(isnan, nan, lppd)
+        mean = L.sum(axis=0) / S
+        p_waic = ((L - mean) ** 2).sum(axis=0) / np.longdouble(S - 1) if S > 1 else np.full(N, nan)
+        mean = np.where(bad, nan, mean)
+        p_waic = np.where(bad, nan, p_waic)
+        elpd = lppd - p_waic
+        ebar = elpd.sum() / N
+        se = np.sqrt(N * (((elpd - ebar) ** 2).sum() / np.longdouble(N - 1))) if N > 1 else nan
+        totals = [elpd.sum(), se, p_waic.sum(), lppd.sum(), -2 * elpd.sum(), -2 * mean.sum(), float((p_waic > 0.4).sum()),
+                  float((~(np.isfinite(lppd) & np.isfinite(p_waic))).sum())]
+    return Waic(np.array(totals, dtype=np.float64), np.stack([lppd, p_waic, mean, elpd], axis=1).astype(np.float64))
+
+
+def compare_waic(a, b):
+    """two Waic records (or pointwise tables [N][4]) over the SAME observations -> dict(elpd_diff = sum_i (elpd_i^a - elpd_i^b),
+    se_diff = sqrt(N var_i(elpd_i^a - elpd_i^b)), N - 1 in the variance): positive elpd_diff favours a"""
+    pa, pb = (np.asarray(x.pointwise if isinstance(x, Waic) else x, dtype=np.float64) for x in (a, b))
+    if pa is None or pb is None or pa.ndim != 2 or pa.shape != pb.shape or pa.shape[1] != len(WAIC_POINT):
+        raise ValueError("compare_waic needs two pointwise tables [N][4] over the same observations (waic(..., pointwise=True))")
+    d = (pa[:, 3] - pb[:, 3]).astype(np.longdouble)
+    N = d.size
+    with np.errstate(all="ignore"):
+        se = float(np.sqrt(N * (((d - d.sum() / N) ** 2).sum() / np.longdouble(N - 1)))) if N > 1 else float("nan")
+    return dict(elpd_diff=float(d.sum()), se_diff=se)
 
 
 _SIGN, _ALL = np.uint64(1 << 63), np.uint64(0xFFFFFFFFFFFFFFFF)

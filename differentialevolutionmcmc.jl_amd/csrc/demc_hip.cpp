@@ -18,6 +18,7 @@
 #include "../../include/demc_summary.h"  // demc_summarize
 #include "../../include/demc_quantile.h"  // demc_quantiles
 #include "../../include/demc_cov.h"  // demc_covariance
+#include "../../include/demc_pointwise.h"  // demc_pointwise_loglik, demc_waic
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -51,11 +52,13 @@
 #include "demc_summary.hpp"  // demc_summarize: its kernels and their launches live in demc_summary.cpp
 #include "demc_quantile.hpp"  // demc_quantiles: likewise, demc_quantile.cpp
 #include "demc_cov.hpp"  // demc_covariance: likewise, demc_cov.cpp
+#include "demc_pointwise.hpp"  // demc_pointwise_loglik, demc_waic: likewise, demc_pointwise.cpp
 #include "demc_devmem.hpp"  // owners of the device memory, pinned memory, events and modules the handle holds
 #include "demc_prep.hpp"  // host-only: a model's data and constants, the prior table and its run-length forms, every refusal of those
 #include "demc_instances.hpp"  // one table per templated kernel, built from the lists above: every choice of an instance goes through them
 #include "demc_geometry.hpp"  // host-only: every launch-geometry decision, as plans the launches below carry out
 #include "demc_postplan.hpp"  // host-only: the history window and the plans of demc_summarize, demc_quantiles, demc_covariance
+#include "demc_pwplan.hpp"  // host-only: the families, refusals and plan of demc_pointwise_loglik and demc_waic
 #include "demc_schedule.hpp"  // host-only: what a step call does iteration by iteration -- coins, refusals, segments, phases, frozen order
 
 using namespace demc;
@@ -63,6 +66,7 @@ using namespace demc;
 #ifndef DEMC_ARCH_STR
 #define DEMC_ARCH_STR "gfx950"  // the Makefile passes its ARCH, so that the JIT-compiled plug-in matches the library
 #endif
+static_assert(kPwFamSim == FAM_SIM, "demc_pwplan.hpp names the simulation likelihood by the runtime's family");
 static_assert(kPrepOdeMaxT == kOdeMaxT && kPrepOdeMaxSubsteps == kOdeMaxSubsteps && kPrepSimMaxN == kSimMaxN && kPrepSimChoiceMaxN == kSimChoiceMaxN,
               "demc_prep.hpp refuses by the kernels' caps");
 
@@ -95,6 +99,7 @@ struct Model : ModelShape {
     int family = -1;
     int direct_wgs_per_cu = 0;  // DIRECT mode: resident workgroups of its kernel per CU (wgs_per_cu: asked once per model)
     DevBuf<double> data, Ainv, Ypad, Xf, sx, xbar;
+    DevBuf<int> order;  // LBA: the caller's index of sorted trial k (the per-observation calls answer in the caller's order)
     // user plug-in (demc_set_model_source): JIT-compiled module, kernel and its hyper-parameters
     Module user_module;
     hipFunction_t user_kernel = nullptr;
@@ -1121,6 +1126,10 @@ int32_t demc_set_model(demc_handle* h, int32_t family, const double* data, const
     if (is_mvn(family)) ALLOC(m.Ypad, (size_t)h->P * m.dpad);
     if (int rc = upload(h, m.Xf, pm.Xf)) return rc;
     if (int rc = upload(h, m.data, pm.data)) return rc;
+    if (!pm.order.empty()) {
+        ALLOC(m.order, pm.order.size());
+        HIPCHK(hipMemcpy(m.order, pm.order.data(), sizeof(int) * pm.order.size(), hipMemcpyHostToDevice));
+    }
     m.family = family;
     return size_k1_lds(h);
     });
@@ -1427,6 +1436,46 @@ int32_t demc_covariance(demc_handle* h, int64_t row0, int64_t row1, const int32_
     if (plan.refused) return fail(h, plan.refused);
     std::string msg;
     const int rc = cov_run(hist_view(h, row0, row1), plan, h->stream, mean_out, cov_out, cor_out, msg);
+    return rc == DEMC_OK ? DEMC_OK : fail(h, rc, msg);
+    });
+}
+
+// The two per-observation calls (include/demc_pointwise.h): the shape of the call, the plan (demc_pwplan.hpp), the run
+// (demc_pointwise.cpp).  What the plan has against the model ranks where a call's own arguments rank in check_history_window.
+static PwModelView pw_model_view(const demc_handle* h) {
+    const Model& m = h->m;
+    PwModelView v{};
+    v.m.family = m.family; v.m.direct = h->c.loglike_mode == DEMC_LOGLIKE_DIRECT; v.m.N = m.N; v.m.n_acc = m.n_acc; v.m.d = m.d; v.m.dp = m.dp_direct;
+    v.data = m.data; v.data2 = m.data ? m.data + m.data2_off : nullptr; v.M = m.Ainv; v.xbar = m.xbar; v.order = m.order;
+    v.c0 = m.family == DEMC_FAM_MVN_FULL ? m.c0 / (double)m.N : m.c0;  // (MVN_FULL: the constant of ONE row; LNR: sigma)
+    return v;
+}
+
+int32_t demc_pointwise_loglik(demc_handle* h, const double* theta, int64_t n, double* out) {
+    return guarded(h, [&]() -> int32_t {
+    if (!h || !theta || !out) return DEMC_EINVAL;
+    USE_DEVICE(h);
+    const PwModelView mv = pw_model_view(h);
+    const PwPlan plan = plan_pointwise(PW_LOGLIK, mv.m, (long long)n, h->c.D);
+    if (plan.refused) return fail(h, plan.refused);
+    std::string msg;
+    const int rc = pw_matrix_run(mv, theta, h->c.D, h->dimtab, plan, h->stream, out, msg);
+    return rc == DEMC_OK ? DEMC_OK : fail(h, rc, msg);
+    });
+}
+
+int32_t demc_waic(demc_handle* h, int64_t row0, int64_t row1, double* total_out, double* pointwise_out) {
+    return guarded(h, [&]() -> int32_t {
+    if (!h) return DEMC_EINVAL;
+    USE_DEVICE(h);
+    const PwModelView mv = pw_model_view(h);
+    const bool window_ok = h->hist != nullptr && row0 >= 0 && row1 - row0 >= 1 && row1 <= h->c.n_rows;
+    const PwPlan plan = plan_pointwise(PW_WAIC, mv.m, window_ok ? (long long)(row1 - row0) * h->P : 1, h->c.D);
+    if (Refusal r = check_pw_window(h->hist != nullptr, row0, row1, h->c.n_rows, h->c.n_groups_total != h->c.n_groups,
+                                    pw_waic_args(plan.refused, total_out || pointwise_out)))
+        return fail(h, r);
+    std::string msg;
+    const int rc = pw_waic_run(mv, hist_view(h, row0, row1), plan, h->stream, total_out, pointwise_out, msg);
     return rc == DEMC_OK ? DEMC_OK : fail(h, rc, msg);
     });
 }

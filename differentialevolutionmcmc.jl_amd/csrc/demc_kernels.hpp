@@ -307,6 +307,7 @@ __device__ __forceinline__ double lba_range_sum(const KParams& p, const double* 
 }
 
 // LNR log-likelihood of the trials i0, i0+stride, ... < i1 for one proposal (lognormal_race_tests.jl:9-12); tab = kLogPhiTable
+// (the trial's expression is written a second time in pw_term of demc_pointwise.cpp, which answers per trial: change both together)
 __device__ __forceinline__ double lnr_range_sum(const KParams& p, const double* th, long long i0, long long i1, int stride, const double* tab) {
     const int na = p.n_acc;
     double nu[8];
@@ -347,6 +348,7 @@ __device__ inline double obs_range_sum(const KParams& p, const double* th, long 
             }
         } break;
         case FAM_BINOMIAL: {  // binomial_tests.jl:15-17; data=[n], data2=[k], then the log binomial coefficients
+            // (the term is written a second time in pw_term of demc_pointwise.cpp, which answers per observation: change both together)
             const double pr = th[0];
             const double lp = log(pr), l1p = log1p(-pr);
             const double* lgc = p.data2 + p.N;

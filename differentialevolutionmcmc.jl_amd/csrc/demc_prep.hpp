@@ -84,6 +84,7 @@ struct PreparedModel : ModelShape {
     std::vector<double> M;         // MVN_FULL, the Ainv slot: Sigma^-1, or (L^-1)' in DIRECT mode
     std::vector<double> sx, xbar;  // MVN: sum of the centred observations, their mean
     std::vector<double> Xf;        // MVN: the centred observations in MFMA fragment order
+    std::vector<int> order;        // LBA: the caller's index of sorted trial k (empty: the data keep the caller's order)
 };
 
 inline Refusal prep_gaussian(PreparedModel& m, int D, const double* data, const long long* dm) {
@@ -156,6 +157,10 @@ inline Refusal prep_race(PreparedModel& m, int family, int D, const double* data
             return data[a] != data[b2] ? data[a] < data[b2] : data[N + a] < data[N + b2];
         });
         for (size_t i = 0; i < N; ++i) { m.data[i] = data[order[i]]; m.data[N + i] = data[N + order[i]]; }
+        // ... and the per-observation calls answer in the caller's (demc_pointwise.hpp): the permutation is kept
+        if (N > 0x7fffffffu) return {DEMC_EINVAL, "too many observations"};
+        m.order.resize(N);
+        for (size_t i = 0; i < N; ++i) m.order[i] = (int)order[i];
     }
     return {};
 }

@@ -280,6 +280,8 @@ include("DEMCHIPSummary.jl")
 include("DEMCHIPQuantile.jl")
 # ... and cov(chains) / cor(chains) (include/demc_cov.h): `covariance`, likewise
 include("DEMCHIPCov.jl")
+# ... and model comparison (include/demc_pointwise.h): `waic`, `pointwise_loglik`, `compare_waic`, likewise
+include("DEMCHIPPointwise.jl")
 
 "final state of the particle objects behind handle `h` (bundle_samples reads accept/lp from them; Θ for completeness)"
 function pull_state!(h, particles, Pl, D, shapes, lens, offs)
