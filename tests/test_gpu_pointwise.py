@@ -10,7 +10,10 @@ the GPU.  Engines are filled by set_history_rows; nothing is stepped unless a te
    1e-3 max_s |l_is|, asserted), totals at 1e-9 of sum |terms|, the two counts exactly.
 3. end to end without the device's terms: numpy closed forms on the raw data and the exported chains, same bars, |l| / sd <= 1e4
    asserted (a few-ulp difference in log / exp then moves the variance by about 1e-11 relative).
-4. the edge rules, 5. the refusals, 6. summarize(..., waic=True)."""
+4. the edge rules, 5. the refusals, 6. summarize(..., waic=True).
+
+tests/test_gpu_pointwise_edges.py goes on from here with references no device kernel produced: every <family, X> instance, observation
+indices past the first tile, the edges of the plan, badly conditioned columns, and non-finite patterns across chunks."""
 import ctypes as C
 import math
 
@@ -25,15 +28,16 @@ BAR = 1e-9
 LBA_BAR = 1e-5
 
 
-def engine(demc, prob, n, P, rows=None, **kw):
-    """one group of P particles with n history rows written by set_history_rows (the draws of the prior's init when rows is None)"""
+def engine(demc, prob, n, P, rows=None, n_groups=1, **kw):
+    """n_groups groups of P particles each with n history rows written by set_history_rows (the draws of the prior's init when rows
+    is None); a row of the history holds the n_groups P cells of all groups"""
     kw.setdefault("schedule", 1 if P < 4 else 2)
-    eng = demc.HipEngine(n_groups=1, Np=P, D=prob["D"], n_rows=n + kw.get("n_initial", 0), seed=1, **kw)
+    eng = demc.HipEngine(n_groups=n_groups, Np=P, D=prob["D"], n_rows=n + kw.get("n_initial", 0), seed=1, **kw)
     setup_engine(eng, prob)
     if rows is None:
-        rows = np.stack([prob["init"](P) for _ in range(n)])
+        rows = np.stack([prob["init"](n_groups * P) for _ in range(n)])
     eng.set_history_rows(kw.get("n_initial", 0), rows)
-    return eng, np.asarray(rows, dtype=np.float64).reshape(n, P, prob["D"])
+    return eng, np.asarray(rows, dtype=np.float64).reshape(n, n_groups * P, prob["D"])
 
 
 def one_observation(prob, i):
@@ -309,7 +313,7 @@ def test_lnr_tau_above_a_decision_time_in_every_draw(demc):
     eng.close()
 
 
-def test_nan_cell_and_unchanged_state_and_equal_bits(demc):
+def test_nan_cell_and_unchanged_state_and_equal_bits(demc, orc):
     prob = make_problem("gaussian", np.random.default_rng(99), N=130)
     n, P = 10, 13
     eng, rows = engine(demc, prob, n, P)
@@ -339,6 +343,22 @@ def test_nan_cell_and_unchanged_state_and_equal_bits(demc):
     th = np.array([[0.1, 1.0], [0.1, -1.0], [np.nan, 1.0], [0.2, 2.0]])
     m = eng.pointwise_loglik(th)
     assert np.isfinite(m[0]).all() and np.isnan(m[1]).all() and np.isnan(m[2]).all() and np.isfinite(m[3]).all()
+    # a row exactly ON a bound is evaluated, not flagged (in_bounds is inclusive), one just beyond it is a row of NaN; the finite / NaN
+    # pattern of the row sum plus the prior is demc_logpost's
+    eng.set_bounds([-0.5, 0.25], [0.5, 3.0])
+    th = np.array([[0.5, 1.0], [-0.5, 0.25], [0.2, 3.0], [np.nextafter(0.5, 1.0), 1.0], [0.2, np.nextafter(0.25, 0.0)], [0.1, 1.0]])
+    m = eng.pointwise_loglik(th)
+    assert np.isfinite(m[[0, 1, 2, 5]]).all() and np.isnan(m[[3, 4]]).all()
+    x = np.asarray(prob["data"])
+    want = -0.5 * ((x[None, :] - th[:3, :1]) / th[:3, 1:]) ** 2 - np.log(th[:3, 1:]) - 0.5 * math.log(2 * math.pi)
+    assert (np.abs(m[:3] - want) <= BAR * np.maximum(1.0, np.abs(want))).all()
+    lp = eng.logpost(th)
+    o = orc.Oracle(n_groups=1, Np=4, D=2)
+    setup_engine(o, prob)
+    total = m.sum(axis=1) + o.prior(th)
+    o.close()
+    assert np.array_equal(np.isfinite(total), np.isfinite(lp)), (total, lp)
+    assert np.isfinite(lp[[0, 1, 2, 5]]).all() and (np.abs(total - lp)[[0, 1, 2, 5]] <= BAR * np.maximum(1.0, np.abs(lp[[0, 1, 2, 5]]))).all()
     eng.close()
 
 
