@@ -358,11 +358,12 @@ inline int chunks_filling_rounds(long long blocks, long long cap, double residen
 enum K2Kind { K2_NONE, K2_CROSS_MFMA, K2_DIRECT_MVN, K2_OBS, K2_LBA_WAVE, K2_HIER, K2_USER, K2_USER_ROW, K2_SIM, K2_ODE };
 
 // resident 256-thread workgroups per CU of k_direct_mvn<DP>, k_obs_loglike and k_lba_wave<3>: only the one the kind reads need be set
-struct Occupancy { int direct = 0, obs = 0, lba_wave = 0; };
+// (direct4: of k_direct_mvn_x4<DP>, 0 where the library has no such instance for the row length)
+struct Occupancy { int direct = 0, obs = 0, lba_wave = 0, direct4 = 0; };
 
 struct LoglikePlan {
     K2Kind kind = K2_NONE;
-    int key[2] = {0, 0};        // the instance: k_direct_mvn<key[0]>, k_cross_mfma<key[0], key[1]>, k_lba_wave<key[0]>
+    int key[2] = {0, 0};        // the instance: k_direct_mvn<key[0]> (key[1] = 4: k_direct_mvn_x4), k_cross_mfma<key[0], key[1]>, k_lba_wave<key[0]>
     unsigned grid_x = 0, grid_y = 1;
     int n_chunks = 1, n_partials = 1;
     int n_kpass = 1, k0_stride = 0, part0_stride = 0;  // k_cross_mfma: pass kp starts at dimension kp * k0_stride, partial plane kp * part0_stride
@@ -407,6 +408,14 @@ inline LoglikePlan plan_loglike(const Setup& s, long long n_prop, const Occupanc
             o.n_chunks = chunks_filling_rounds(blocks, cap, (double)occ.direct * s.n_cus);
             o.grid_x = (unsigned)blocks; o.grid_y = (unsigned)o.n_chunks;
             o.n_partials = o.n_chunks;
+            // The body is chosen AFTER the chunks, which alone fix the sums: four proposals per lane (blocks of 512, occ.direct4
+            // resident workgroups per CU) where half as many workgroups still give every CU its resident count; an under-filled
+            // device keeps the thinner ones.  (cfg3: 64 blocks x 48 chunks = 4 x 768.)
+            const long long blocks4 = (n_prop + 511) / 512;
+            if (m.dp_direct == 32 && occ.direct4 > 0 && blocks4 * o.n_chunks >= (long long)occ.direct4 * s.n_cus) {
+                o.key[1] = 4;
+                o.grid_x = (unsigned)blocks4;
+            }
         } break;
         case K2_CROSS_MFMA: {
             // (k-steps per pass: the next instance up, the model's preparation keeps them a power of two <= 16)

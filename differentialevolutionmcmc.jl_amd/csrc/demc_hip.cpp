@@ -98,6 +98,7 @@ struct StreamGeo : StreamDims {
 struct Model : ModelShape {
     int family = -1;
     int direct_wgs_per_cu = 0;  // DIRECT mode: resident workgroups of its kernel per CU (wgs_per_cu: asked once per model)
+    int direct4_wgs_per_cu = 0;  // ... and of the four-per-lane instance of that row length, where there is one
     DevBuf<double> data, Ainv, Ypad, Xf, sx, xbar;
     DevBuf<int> order;  // LBA: the caller's index of sorted trial k (the per-observation calls answer in the caller's order)
     // user plug-in (demc_set_model_source): JIT-compiled module, kernel and its hyper-parameters
@@ -560,6 +561,10 @@ int launch_loglike(demc_handle* h, KParams& k) {
             PICK(ec, "k_direct_mvn", kDirect, h->m.dp_direct);
             if (int rc = wgs_per_cu(h, (const void*)ec->fn, &h->m.direct_wgs_per_cu)) return rc;
             occ.direct = h->m.direct_wgs_per_cu;
+            if (const Inst<ChunkFn>* e4 = find_inst(kDirect, InstKey{{h->m.dp_direct, 4}})) {
+                if (int rc = wgs_per_cu(h, (const void*)e4->fn, &h->m.direct4_wgs_per_cu)) return rc;
+                occ.direct4 = h->m.direct4_wgs_per_cu;
+            }
             break;
         case K2_OBS:
             if (int rc = wgs_per_cu(h, (const void*)k_obs_loglike, &h->obs_wgs_per_cu)) return rc;
@@ -580,6 +585,7 @@ int launch_loglike(demc_handle* h, KParams& k) {
         case K2_DIRECT_MVN:
         case K2_LBA_WAVE: {
             if (pl.kind == K2_LBA_WAVE) PICK(ec, "k_lba_wave", kLbaWave, pl.key[0]);
+            else PICK(ec, "k_direct_mvn", kDirect, pl.key[0], pl.key[1]);
             h->last.k2_key = ec->key;
             // timing on: every workgroup also leaves its shader-clock / reference-clock ticks (demc_timing_clock)
             unsigned long long* clk = nullptr;

@@ -59,7 +59,9 @@ inline std::string name_frozen(const InstKey& k) { return "k_frozen_sweep<" + st
 inline std::string name_longrow(const InstKey& k) { return "k_longrow<" + int_list(k, 1) + ">"; }
 inline std::string name_res_obs(const InstKey& k) { return "k_res_obs<" + int_list(k, 1) + ">"; }
 inline std::string name_cross(const InstKey& k) { return "k_cross_mfma<" + int_list(k, 2) + ">"; }
-inline std::string name_direct(const InstKey& k) { return "k_direct_mvn<" + int_list(k, 1) + ">"; }
+inline std::string name_direct(const InstKey& k) {  // <DP>, k_direct_mvn_x4<DP> as <DP, 4>: "k_direct_mvn<32>x4"
+    return "k_direct_mvn<" + int_list(k, 1) + ">" + (k.v[1] ? "x" + std::to_string(k.v[1]) : "");
+}
 inline std::string name_lba_wave(const InstKey&) { return "k_lba_wave"; }
 inline std::string name_sim(const InstKey& k) {  // <SIM, EST>; SIM_USER: the instance hiprtc compiled around the caller's simulator
     return std::string("k_sim_loglike<") + (k.v[1] == EST_KDE ? "kde" : k.v[1] == EST_FREQ ? "frequency" : "kde_choice") + "," +
@@ -81,6 +83,7 @@ using OdeFn = void (*)(OdeKParams);
 #define DEMC_E_LONGROW(...) DEMC_ENTRY(k_longrow, name_longrow, __VA_ARGS__)
 #define DEMC_E_RES_OBS(...) DEMC_ENTRY(k_res_obs, name_res_obs, __VA_ARGS__)
 #define DEMC_E_DIRECT(...) DEMC_ENTRY(k_direct_mvn, name_direct, __VA_ARGS__)
+#define DEMC_E_DIRECT_X4(DP) {k_direct_mvn_x4<DP>, {{DP, 4}}, name_direct},  // (a kernel of its own: k_direct_mvn<DP> keeps its symbol)
 #define DEMC_E_CROSS(...) DEMC_ENTRY(k_cross_mfma, name_cross, __VA_ARGS__)
 #define DEMC_E_LBA_WAVE(...) DEMC_ENTRY(k_lba_wave, name_lba_wave, __VA_ARGS__)
 #define DEMC_E_SIM(...) DEMC_ENTRY(k_sim_loglike, name_sim, __VA_ARGS__)
@@ -91,7 +94,7 @@ constexpr K1Inst kResMvn[] = {DEMC_RESMVN_INSTANCES(DEMC_E_RES_MVN) DEMC_RESMVN_
 constexpr K1Inst kFrozen[] = {DEMC_FROZEN_INSTANCES(DEMC_E_FROZEN)};
 constexpr K1Inst kLongrow[] = {DEMC_LONGROW_INSTANCES(DEMC_E_LONGROW)};
 constexpr K1Inst kResObs[] = {DEMC_RESOBS_INSTANCES(DEMC_E_RES_OBS)};
-constexpr Inst<ChunkFn> kDirect[] = {DEMC_DIRECT_INSTANCES(DEMC_E_DIRECT)};
+constexpr Inst<ChunkFn> kDirect[] = {DEMC_DIRECT_INSTANCES(DEMC_E_DIRECT) DEMC_DIRECT_X4_INSTANCES(DEMC_E_DIRECT_X4)};
 constexpr Inst<CrossFn> kCross[] = {DEMC_CROSS_INSTANCES(DEMC_E_CROSS)};
 constexpr Inst<ChunkFn> kLbaWave[] = {DEMC_LBA_WAVE_INSTANCES(DEMC_E_LBA_WAVE)};
 constexpr Inst<SimFn> kSim[] = {DEMC_SIM_INSTANCES(DEMC_E_SIM) DEMC_SIM_CHOICE_INSTANCES(DEMC_E_SIM_CHOICE)};

@@ -2055,7 +2055,7 @@ __global__ __launch_bounds__(256, 2) void k_cross_mfma(KParams p, const double* 
 // observation, dimension) one v_add_f64 and one v_fma_f64.  DP = padded row length (host pads z rows and m with zeros).
 // grid = (proposal blocks of 256, observation chunks); a workgroup is 256 proposals x one chunk in both bodies below:
 // DP = 32 (the headline) splits a row over wave pairs and prefetches it (direct_mvn_slices), the other lengths hold whole
-// rows, thread per proposal (direct_mvn_rows).
+// rows, thread per proposal (direct_mvn_rows).  (k_direct_mvn_x4<32>: the sliced body on blocks of 512, four proposals per lane.)
 // ------------------------------------------------------------------------------------------------
 // The whole-row body (DP = 8, 16, 64): thread per proposal, the DP values of m in registers, a row of z per trip.  The
 // s_load_dwordx16 of a row sit at the top of the trip with s_waitcnt lgkmcnt(0) right behind them: the wait is exposed per wave and
@@ -2100,6 +2100,10 @@ __device__ __forceinline__ void direct_mvn_rows(const KParams& p, int pblock, in
 // leaves no load in flight when the loop's results are used.  The two slices' sums meet in LDS: slice 0 stores own + other, one
 // partial per (chunk, proposal) in a fixed order.  Nothing but the LDS index of the lane stays in vector registers over the row
 // loop for the stores behind it (profiles/r06/NOTES.md 9).
+// With Q = 4 proposals per lane instead of 2 (a block of 512) the same loop is
+//     wait(A) . ask B . 128 FP64 on A . wait(B) . ask A . 128 FP64 on B
+// -- per FP64 instruction half the scalar loads, waits and loop control, a z operand serves four subtractions, and every square
+// is four instructions behind its subtraction (profiles/r06/NOTES.md 10).
 typedef int zs16 __attribute__((ext_vector_type(16)));
 typedef double zd8 __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ void zslice_ask(zs16& lo, zs16& hi, const double* row) {  // row: wave-uniform, 16 doubles
@@ -2110,46 +2114,60 @@ __device__ __forceinline__ void zslice_wait(zs16& lo, zs16& hi) {
     asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(lo), "+s"(hi));
     __builtin_amdgcn_sched_barrier(0);
 }
-__device__ __forceinline__ void zslice_fma(const zs16& lo, const zs16& hi, const double (&m0)[16], const double (&m1)[16],
-                                           double (&a0)[2], double (&a1)[2]) {
+template <int Q>
+__device__ __forceinline__ void zslice_fma(const zs16& lo, const zs16& hi, const double (&m)[Q][16], double (&a)[Q][2]) {
     const zd8 zl = __builtin_bit_cast(zd8, lo), zh = __builtin_bit_cast(zd8, hi);
 #pragma unroll
-    for (int k = 0; k < 16; ++k) {  // two chains per proposal, four per lane
+    for (int k = 0; k < 16; ++k) {  // two chains per proposal, 2 Q per lane: Q subtractions, then their Q squares
         const double z = k < 8 ? zl[k & 7] : zh[k & 7];
-        const double r0 = z - m0[k], r1 = z - m1[k];
-        a0[k & 1] = fma(r0, r0, a0[k & 1]);
-        a1[k & 1] = fma(r1, r1, a1[k & 1]);
+        double r[Q];
+#pragma unroll
+        for (int j = 0; j < Q; ++j) r[j] = z - m[j][k];
+#pragma unroll
+        for (int j = 0; j < Q; ++j) a[j][k & 1] = fma(r[j], r[j], a[j][k & 1]);
     }
 }
+// Q proposals per lane: 2 (a workgroup is 256 proposals: k_direct_mvn<32>) or 4 (512: k_direct_mvn_x4<32>).  Wave w: slice
+// s = w >> 1, half h = w & 1 of the block's 128 Q proposals; the lane's proposals within the block are h * 64 Q + 64 j + lane.
+template <int Q>
 __device__ __forceinline__ void direct_mvn_slices(const KParams& p, int pblock, int chunk, int n_chunks) {
-    __shared__ double s_other[256];  // slice 1's sums, by proposal of the block
-    // The lane's two slots are needed again only behind the row loop: they wait in LDS, not in registers (as 32-bit values: a slot is
+    constexpr int B = 128 * Q;     // proposals of a block
+    __shared__ double s_other[B];  // slice 1's sums, by proposal of the block
+    // The lane's slots are needed again only behind the row loop: they wait in LDS, not in registers (as 32-bit values: a slot is
     // slot_of's int; kNoSlot: no such proposal), written and read by the SAME lane of a slice-0 wave, so no barrier is theirs.
-    __shared__ int s_slot[256];
+    __shared__ int s_slot[B];
     constexpr int kNoSlot = -1;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int s = wave >> 1, h = wave & 1;
     const int n_prop = p.n_groups * p.n_act;
-    const int t0 = h * 128 + lane, t1 = t0 + 64;  // the lane's two proposals within the block
-    double m0[16], m1[16];
+    const int t0 = h * (B / 2) + lane;  // the lane's first proposal within the block; the others follow 64 apart
+    double m[Q][16];
     {
-        const bool ok0 = pblock * 256 + t0 < n_prop, ok1 = pblock * 256 + t1 < n_prop;
-        const int slot0 = ok0 ? slot_of(p, pblock * 256 + t0) : 0, slot1 = ok1 ? slot_of(p, pblock * 256 + t1) : 0;
+        bool ok[Q];
+        int slot[Q];
+#pragma unroll
+        for (int j = 0; j < Q; ++j) ok[j] = pblock * B + t0 + 64 * j < n_prop;
+#pragma unroll
+        for (int j = 0; j < Q; ++j) slot[j] = ok[j] ? slot_of(p, pblock * B + t0 + 64 * j) : 0;
         if (s == 0) {
-            s_slot[t0] = ok0 ? slot0 : kNoSlot;
-            s_slot[t1] = ok1 ? slot1 : kNoSlot;
+#pragma unroll
+            for (int j = 0; j < Q; ++j) s_slot[t0 + 64 * j] = ok[j] ? slot[j] : kNoSlot;
         }
-        const double *mrow0 = p.Ypad + (size_t)slot0 * p.dpad + 16 * s, *mrow1 = p.Ypad + (size_t)slot1 * p.dpad + 16 * s;
+        const double* mrow[Q];
+#pragma unroll
+        for (int j = 0; j < Q; ++j) mrow[j] = p.Ypad + (size_t)slot[j] * p.dpad + 16 * s;
 #pragma unroll
         for (int k = 0; k < 16; ++k) {
-            m0[k] = (ok0 && 16 * s + k < p.d) ? mrow0[k] : 0.0;
-            m1[k] = (ok1 && 16 * s + k < p.d) ? mrow1[k] : 0.0;
+#pragma unroll
+            for (int j = 0; j < Q; ++j) m[j][k] = (ok[j] && 16 * s + k < p.d) ? mrow[j][k] : 0.0;
         }
     }
     const long long per = (p.N + n_chunks - 1) / n_chunks;
     const long long i0 = chunk * per, i1 = (i0 + per < p.N) ? i0 + per : p.N;
     const int n = (int)(i1 - i0);  // rows of the chunk (32-bit, so that the loop control stays on the scalar unit: 2^31 rows are 512 GB)
-    double a0[2] = {0.0, 0.0}, a1[2] = {0.0, 0.0};
+    double a[Q][2];
+#pragma unroll
+    for (int j = 0; j < Q; ++j) a[j][0] = a[j][1] = 0.0;
     if (n > 0) {
         const double* z = p.data + i0 * 32 + 16 * s;
         zs16 alo, ahi, blo, bhi;
@@ -2157,25 +2175,29 @@ __device__ __forceinline__ void direct_mvn_slices(const KParams& p, int pblock, 
         for (int left = n; left >= 2; left -= 2, z += 64) {
             zslice_wait(alo, ahi);
             zslice_ask(blo, bhi, z + 32);
-            zslice_fma(alo, ahi, m0, m1, a0, a1);
+            zslice_fma<Q>(alo, ahi, m, a);
             zslice_wait(blo, bhi);
             zslice_ask(alo, ahi, left > 2 ? z + 64 : z + 32);  // never past the chunk's last row
-            zslice_fma(blo, bhi, m0, m1, a0, a1);
+            zslice_fma<Q>(blo, bhi, m, a);
         }
         zslice_wait(alo, ahi);  // nothing in flight from here on
-        if (n & 1) zslice_fma(alo, ahi, m0, m1, a0, a1);  // the odd last row
+        if (n & 1) zslice_fma<Q>(alo, ahi, m, a);  // the odd last row
     }
-    const double sum0 = a0[0] + a0[1], sum1 = a1[0] + a1[1];
+    double sum[Q];
+#pragma unroll
+    for (int j = 0; j < Q; ++j) sum[j] = a[j][0] + a[j][1];
     if (s == 1) {
-        s_other[t0] = sum0;
-        s_other[t1] = sum1;
+#pragma unroll
+        for (int j = 0; j < Q; ++j) s_other[t0 + 64 * j] = sum[j];
     }
     __syncthreads();
     if (s == 0) {
         double* part = p.partial + (size_t)chunk * p.P;  // the chunk's row of partials
-        const int slot0 = s_slot[t0], slot1 = s_slot[t1];
-        if (slot0 != kNoSlot) part[slot0] = sum0 + s_other[t0];
-        if (slot1 != kNoSlot) part[slot1] = sum1 + s_other[t1];
+#pragma unroll
+        for (int j = 0; j < Q; ++j) {
+            const int slot = s_slot[t0 + 64 * j];
+            if (slot != kNoSlot) part[slot] = sum[j] + s_other[t0 + 64 * j];
+        }
     }
 }
 
@@ -2186,9 +2208,10 @@ __device__ __forceinline__ void direct_mvn_slices(const KParams& p, int pblock, 
 // (MI355X_MICROARCH.md, "DVFS give-back" items 5 and 6), and a VALU-bound rate scales with it.  No stamp BEFORE the loop: the
 // compiler treats s_memtime as a memory clobber, and a clobber ahead of the loop turns the wave-uniform z-row loads from scalar
 // loads (s_load_dwordx16, SGPR operands) into vector loads -- the first form of this probe cost the kernel a factor of 3.3.
-template <int DP>
-__global__ __launch_bounds__(256) void k_direct_mvn(KParams p, int n_chunks, unsigned long long* __restrict__ clk) {
-    // workgroup -> (block of 256 proposals, observation chunk).  Workgroups are dealt to the eight XCDs in turn (linear id mod 8) and
+// Q: proposals per lane of the sliced body (0: the whole-row body)
+template <int DP, int Q>
+__device__ __forceinline__ void direct_mvn_workgroup(const KParams& p, int n_chunks, unsigned long long* __restrict__ clk) {
+    // workgroup -> (block of 256 proposals, 512 at Q = 4; observation chunk).  Workgroups are dealt to the eight XCDs in turn (linear id mod 8) and
     // every XCD has an L2 of its own: with the chunk count a multiple of 8, XCD x takes the chunks x, x + 8, ... and all proposal
     // blocks of one chunk before the next, so a chunk of whitened rows is fetched by ONE XCD, once (k_cross_mfma's rule).  With
     // (block, chunk) = (blockIdx.x, blockIdx.y) every XCD held a share of twelve chunks at a time -- 6.4 MB of rows behind a 4 MB
@@ -2199,8 +2222,8 @@ __global__ __launch_bounds__(256) void k_direct_mvn(KParams p, int n_chunks, uns
         chunk = (int)((j / gridDim.x) * 8u + xcd);
         pblock = (int)(j % gridDim.x);
     }
-    if constexpr (DP == 32)
-        direct_mvn_slices(p, pblock, chunk, n_chunks);
+    if constexpr (Q != 0)
+        direct_mvn_slices<Q>(p, pblock, chunk, n_chunks);
     else
         direct_mvn_rows<DP>(p, pblock, chunk, n_chunks);
     if (clk) {
@@ -2215,7 +2238,21 @@ __global__ __launch_bounds__(256) void k_direct_mvn(KParams p, int n_chunks, uns
         }
     }
 }
+template <int DP>
+__global__ __launch_bounds__(256) void k_direct_mvn(KParams p, int n_chunks, unsigned long long* __restrict__ clk) {
+    direct_mvn_workgroup<DP, DP == 32 ? 2 : 0>(p, n_chunks, clk);
+}
 #define DEMC_DIRECT_INSTANCES(X) X(8) X(16) X(32) X(64)  // <DP>
+// Four proposals per lane (DP = 32 only): per FP64 instruction half the scalar loads, waits, loop control and scalar-cache traffic
+// of k_direct_mvn<32>, a z operand serves four subtractions, and a square is four instructions behind its subtraction -- for 156
+// registers, three waves per SIMD, and half as many, fatter workgroups: plan_loglike (demc_geometry.hpp) takes it where those
+// still fill the chip.  Chunks, row order and the two chains per proposal are k_direct_mvn<32>'s: the partials are bit-equal.
+template <int DP>
+__global__ __launch_bounds__(256) void k_direct_mvn_x4(KParams p, int n_chunks, unsigned long long* __restrict__ clk) {
+    static_assert(DP == 32, "the sliced body is DP = 32's");
+    direct_mvn_workgroup<DP, 4>(p, n_chunks, clk);
+}
+#define DEMC_DIRECT_X4_INSTANCES(X) X(32)  // <DP>
 
 // ------------------------------------------------------------------------------------------------
 // K2 (scalar-data families): thread-per-proposal streaming likelihoods.  All lanes of a wave visit the same observation,
