@@ -35,6 +35,9 @@ COV_MAX_COLS = 64  # DEMC_COV_MAX_COLS
 PW_EXPORTS = ["demc_pointwise_loglik", "demc_waic"]  # include/demc_pointwise.h: per-observation log-densities, WAIC
 WAIC_NTOTAL, WAIC_NPOINT = 8, 4  # DEMC_WAIC_NTOTAL, DEMC_WAIC_NPOINT
 PW_MAX_CELLS = 1 << 27  # DEMC_PW_MAX_CELLS
+LOO_EXPORTS = ["demc_loo"]  # include/demc_loo.h: PSIS-LOO over the history
+LOO_NTOTAL, LOO_NPOINT = 8, 6  # DEMC_LOO_NTOTAL, DEMC_LOO_NPOINT
+LOO_MAX_DRAWS = 1 << 22  # DEMC_LOO_MAX_DRAWS
 COMM_ID_BYTES = 128
 _NOT_STATUS = {"demc_last_error": C.c_char_p, "demc_multi_last_error": C.c_char_p, "demc_multi_shard": C.c_void_p}
 
@@ -154,6 +157,7 @@ def load():
     L.demc_covariance.argtypes = [H, C.c_int64, C.c_int64, C.POINTER(C.c_int32), C.c_int32, _dp, _dp, _dp]
     L.demc_pointwise_loglik.argtypes = [H, _dp, C.c_int64, _dp]
     L.demc_waic.argtypes = [H, C.c_int64, C.c_int64, _dp, _dp]
+    L.demc_loo.argtypes = [H, C.c_int64, C.c_int64, _dp, _dp]
     L.demc_step.argtypes = [H, C.c_int64, C.c_int32]
     L.demc_update.argtypes = [H, C.c_int64, C.c_int32]
     L.demc_migration_due.argtypes = [C.POINTER(DemcConfig), C.c_int64]
@@ -186,7 +190,7 @@ def load():
     L.demc_multi_size.argtypes = [H]
     L.demc_multi_shard.argtypes = [H, C.c_int32]
     L.demc_multi_step.argtypes = [H, C.c_int64, C.c_int32]
-    for name in EXPORTS + SUMMARY_EXPORTS + QUANTILE_EXPORTS + COV_EXPORTS + PW_EXPORTS:  # every entry point returns an int32 status, except the error strings and the shard accessor
+    for name in EXPORTS + SUMMARY_EXPORTS + QUANTILE_EXPORTS + COV_EXPORTS + PW_EXPORTS + LOO_EXPORTS:  # every entry point returns an int32 status, except the error strings and the shard accessor
         getattr(L, name).restype = _NOT_STATUS.get(name, C.c_int32)
     _lib = L
     return L
@@ -405,8 +409,14 @@ class HipEngine:
         """what demc_waic would refuse about this handle whatever the rows, asked BEFORE a run (summarize(..., waic=True)): raises the
         DemcError the call itself would end in -- an unserved family, MvNormal outside DIRECT mode, no observations, a sharded handle.
         The call remains the judge: this only spares a run whose last step is certain to be refused."""
+        self._pw_served("demc_waic: ")
+
+    def loo_served(self):
+        """waic_served for demc_loo (summarize(..., loo=True)): the two calls serve the same families and handles"""
+        self._pw_served("demc_loo: ")
+
+    def _pw_served(self, who):
         from . import families as F
-        who = "demc_waic: "
         mvn = self.family in (F.FAM_MVN_ISO, F.FAM_MVN_FULL)
         if self.family not in (F.FAM_GAUSSIAN, F.FAM_BINOMIAL, F.FAM_LNR, F.FAM_LBA) and not mvn:
             raise DemcError(EUNSUPPORTED, who + "this model has no per-observation log-density on the device (served: Gaussian, Binomial, LNR, LBA, "
@@ -424,6 +434,15 @@ class HipEngine:
         tot = np.empty(WAIC_NTOTAL)
         pt = np.empty((self.n_obs, WAIC_NPOINT)) if pointwise else None
         self._ck(self.L.demc_waic(self.h, row0, row1, _d(tot), _d(pt)))
+        return tot, pt
+
+    def loo(self, row0, row1, pointwise=False):
+        """PSIS-LOO of history rows [row0,row1) formed on the device (demc_loo of include/demc_loo.h), chains pooled
+        -> (totals[8] in the order of chains.LOO_TOTALS, pointwise[N][6] = elpd_loo_i, p_loo_i, khat_i, lppd_i, n_tail_i, l_cut_i
+        or None)"""
+        tot = np.empty(LOO_NTOTAL)
+        pt = np.empty((self.n_obs, LOO_NPOINT)) if pointwise else None
+        self._ck(self.L.demc_loo(self.h, row0, row1, _d(tot), _d(pt)))
         return tot, pt
 
     def step(self, iter0, n_iters=1):

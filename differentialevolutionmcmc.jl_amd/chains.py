@@ -3,7 +3,7 @@ summary statistics the reference's tests read from describe(chains)[1] (:mean, :
 its Monte-Carlo standard error and the autocorrelation MCMCChains adds to them (DESIGN.md section 5.5 is the definition; the device
 computes the same numbers from the history without exporting it: demc_summarize), the quantile table of describe(chains)
 (demc_quantiles on the device), cov(chains) / cor(chains) (demc_covariance), and WAIC from
-the per-observation log-densities (demc_waic)."""
+the per-observation log-densities (demc_waic), and PSIS-LOO from the same terms (demc_loo)."""
 import math
 
 import numpy as np
@@ -20,11 +20,12 @@ class Summary:
     then acceptance and lp.  `rho` (or None): [series][lags] autocorrelations, NaN beyond the lags that were evaluated.
     `quantiles` (or None): [series][len(probs)] quantiles at `probs`, chains pooled.  `cov_matrix` / `cor_matrix`
     (or None): the covariance and correlation of the series `cov_names`, chains pooled.  `waic` (or None): the Waic
-    record of the same rows."""
+    record of the same rows.  `loo` (or None): the Loo record of the same rows."""
 
     def __init__(self, names, values, internals=("acceptance", "lp"), rho=None, quantiles=None, probs=None, cov=None, cor=None,
-                 cov_names=None, waic=None):
+                 cov_names=None, waic=None, loo=None):
         self.waic = waic
+        self.loo = loo
         self.names = list(names)
         self.values = np.asarray(values, dtype=np.float64).reshape(len(self.names), len(SUMMARY_COLS))
         self.internals = list(internals)
@@ -321,3 +322,146 @@ class Chains:
             rows.append(vals)
             rhos.append(rho)
         return Summary(self.names, rows, self.internals, np.stack(rhos) if rho_len > 0 else None)
+
+
+# ---- PSIS-LOO (demc_loo on the device) ------------------------------------------------------------------
+
+LOO_TOTALS = ("elpd_loo", "se_elpd", "p_loo", "lppd", "looic", "n_k_high", "n_k_bad", "n_nonfinite")  # demc_loo's total_out, in order
+LOO_POINT = ("elpd_loo", "p_loo", "khat", "lppd", "n_tail", "l_cut")  # the columns of demc_loo's pointwise_out (DEMC_LOO_NPOINT)
+LOO_LOG_MIN = -708.3964185322641  # log(DBL_MIN) rounded to FP64: the floor of a shifted log ratio
+
+
+class Loo:
+    """The eight totals of demc_loo by name (LOO_TOTALS) and, when it was asked for, the table pointwise[N][6] = (elpd_loo_i, p_loo_i,
+    khat_i, lppd_i, n_tail_i, l_cut_i) in the caller's observation order."""
+
+    def __init__(self, totals, pointwise=None):
+        totals = np.asarray(totals, dtype=np.float64).reshape(len(LOO_TOTALS))
+        for nm, v in zip(LOO_TOTALS, totals):
+            setattr(self, nm, float(v))
+        self.totals = totals
+        self.pointwise = None if pointwise is None else np.asarray(pointwise, dtype=np.float64).reshape(-1, len(LOO_POINT))
+
+    def __repr__(self):
+        s = (f"Loo(elpd_loo={self.elpd_loo:.2f} (se {self.se_elpd:.2f}), p_loo={self.p_loo:.2f}, lppd={self.lppd:.2f}, "
+             f"looic={self.looic:.2f}")
+        if self.n_k_high:
+            s += f", {int(self.n_k_high)} observations with khat > 0.7 ({int(self.n_k_bad)} above 1)"
+        if self.n_nonfinite:
+            s += f", {int(self.n_nonfinite)} observations not finite"
+        return s + ")"
+
+
+def loo_tail_len(S):
+    """M = ceil(min(0.2 S, 3 sqrt(S))) in FP64 as written"""
+    return int(math.ceil(min(0.2 * float(S), 3.0 * math.sqrt(float(S)))))
+
+
+def psis_fit(e):
+    """the Zhang-Stephens profile fit of DESIGN.md 5.9: e_(1) <= ... <= e_(n), n > 4 and e_(q) > 0 -> (khat, sigma); the sums over
+    the tail and over the profile points run in np.longdouble"""
+    e = np.asarray(e, dtype=np.float64)
+    n = e.size
+    m = 30 + int(math.floor(math.sqrt(float(n))))
+    q = int(math.floor(n / 4.0 + 0.5))
+    j = np.arange(1, m + 1, dtype=np.float64)
+    b = (1.0 - np.sqrt(float(m) / (j - 0.5))) / (3.0 * e[q - 1]) + 1.0 / e[n - 1]
+    L_ = e.astype(np.longdouble)
+    with np.errstate(all="ignore"):
+        k = np.array([np.log1p(-np.longdouble(bj) * L_).sum() / n for bj in b], dtype=np.longdouble)
+        Lj = n * (np.log(-b.astype(np.longdouble) / k) - k - 1)
+        w = np.array([1 / np.exp(Lj - Lj[i]).sum() for i in range(m)], dtype=np.longdouble)
+        bhat = (b.astype(np.longdouble) * w).sum()
+        kk = np.log1p(-bhat * L_).sum() / n
+        sigma = -kk / bhat
+        khat = (n * kk + 5) / (n + 10)
+    return float(khat), float(sigma)
+
+
+def psis_smooth(khat, sigma, n, exc):
+    """the smoothed shifted log weights of a fitted tail: x~_(t) = min(log(g_t + exc), 0), g_t the generalised Pareto quantile at
+    p_t = (t - 0.5) / n (khat == 0: the exponential limit), exc = exp(x_cut)"""
+    p = (np.arange(1, n + 1, dtype=np.float64) - 0.5) / float(n)
+    with np.errstate(all="ignore"):
+        lq = np.log1p(-p)
+        g = -sigma * lq if khat == 0.0 else sigma * np.expm1(-khat * lq) / khat
+        return np.minimum(np.log(g + exc), 0.0)
+
+
+def _loo_column(l):
+    """one observation: l[S] float64 without NaN, +Inf or -Inf -> (elpd_loo, khat, n_tail, l_cut)"""
+    S = l.size
+    nan, inf = float("nan"), float("inf")
+    b = l.view(np.uint64)
+    order = np.argsort(b ^ np.where(b >> np.uint64(63) != 0, _ALL, _SIGN), kind="stable")  # the key order of section 5.6
+    ls = l[order]
+    lmin = ls[0]
+    x = lmin - ls  # descending from 0
+    n2, l_cut, khat = 0, nan, inf
+    xt = np.empty(0)
+    if S > 20:
+        M = loo_tail_len(S)
+        l_cut = ls[M]
+        x_cut = max(lmin - l_cut, LOO_LOG_MIN)
+        n2 = int((x > x_cut).sum())  # a prefix of the ordered terms: ties at the cutoff and floored ratios stay outside
+        xt = x[:n2][::-1].copy()  # x ascending
+        if n2 > 4:
+            with np.errstate(all="ignore"):
+                exc = np.exp(x_cut)
+                e = np.exp(xt) - exc
+            if e[int(math.floor(n2 / 4.0 + 0.5)) - 1] > 0.0:
+                khat, sigma = psis_fit(e)
+                xt = psis_smooth(khat, sigma, n2, exc)
+    lt = ls[:n2][::-1]
+    xo, lo = x[n2:].astype(np.longdouble), ls[n2:].astype(np.longdouble)
+    v = xt.astype(np.longdouble) + lt.astype(np.longdouble)
+    shift = max(np.longdouble(lmin), v.max()) if n2 else np.longdouble(lmin)
+    with np.errstate(all="ignore"):
+        num = np.exp((xo + lo) - shift).sum() + np.exp(v - shift).sum()
+        den = np.exp(xo).sum() + np.exp(xt.astype(np.longdouble)).sum()
+        elpd = shift + (np.log(num) - np.log(den))
+    return float(elpd), khat, n2, float(l_cut)
+
+
+def loo_from_loglik(ll):
+    """DESIGN.md 5.9 on the host: ll[S][N] = log p(y_i | theta_s) -> Loo with its pointwise table.  The selection is exact (a sort by
+    the keys of section 5.6); the sums over the draws, the tail and the observations run in np.longdouble, and the results are
+    rounded to float64 at the end."""
+    ll = np.asarray(ll, dtype=np.float64)
+    if ll.ndim != 2 or ll.shape[0] < 1 or ll.shape[1] < 1:
+        raise ValueError("loo_from_loglik needs ll[S][N] with S >= 1 and N >= 1")
+    S, N = ll.shape
+    nan, inf = float("nan"), float("inf")
+    lppd = waic_from_loglik(np.where(np.isposinf(ll), nan, ll)).pointwise[:, 0]
+    pt = np.empty((N, len(LOO_POINT)))
+    with np.errstate(all="ignore"):
+        for i in range(N):
+            col = np.ascontiguousarray(ll[:, i])
+            if np.isnan(col).any() or np.isposinf(col).any():
+                pt[i] = nan
+            elif np.isneginf(col).any():
+                pt[i] = (-inf, np.float64(lppd[i]) - np.float64(-inf), inf, lppd[i], 0.0, -inf)
+            else:
+                elpd, khat, n2, l_cut = _loo_column(col)
+                pt[i] = (elpd, np.float64(lppd[i]) - np.float64(elpd), khat, lppd[i], float(n2), l_cut)
+        e = pt[:, 0].astype(np.longdouble)
+        se = float(np.sqrt(N * (((e - e.sum() / N) ** 2).sum() / np.longdouble(N - 1)))) if N > 1 else nan
+        totals = [float(e.sum()), se, float(pt[:, 1].astype(np.longdouble).sum()), float(pt[:, 3].astype(np.longdouble).sum()), float(-2 * e.sum()),
+                  float((pt[:, 2] > 0.7).sum()), float((pt[:, 2] > 1.0).sum()), float((~(np.isfinite(pt[:, 0]) & np.isfinite(pt[:, 3]))).sum())]
+    return Loo(np.array(totals, dtype=np.float64), pt)
+
+
+def compare_loo(a, b):
+    """two Loo records (or pointwise tables [N][6]) over the SAME observations -> dict(elpd_diff = sum_i (elpd_loo_i^a - elpd_loo_i^b),
+    se_diff = sqrt(N var_i(elpd_loo_i^a - elpd_loo_i^b)), N - 1 in the variance): positive elpd_diff favours a"""
+    pa, pb = (x.pointwise if isinstance(x, Loo) else x for x in (a, b))
+    if pa is None or pb is None:
+        raise ValueError("compare_loo needs two pointwise tables [N][6] over the same observations (loo(..., pointwise=True))")
+    pa, pb = np.asarray(pa, dtype=np.float64), np.asarray(pb, dtype=np.float64)
+    if pa.ndim != 2 or pa.shape != pb.shape or pa.shape[1] != len(LOO_POINT):
+        raise ValueError("compare_loo needs two pointwise tables [N][6] over the same observations (loo(..., pointwise=True))")
+    d = (pa[:, 0] - pb[:, 0]).astype(np.longdouble)
+    N = d.size
+    with np.errstate(all="ignore"):
+        se = float(np.sqrt(N * (((d - d.sum() / N) ** 2).sum() / np.longdouble(N - 1)))) if N > 1 else float("nan")
+    return dict(elpd_diff=float(d.sum()), se_diff=se)

@@ -19,6 +19,7 @@
 #include "../../include/demc_quantile.h"  // demc_quantiles
 #include "../../include/demc_cov.h"  // demc_covariance
 #include "../../include/demc_pointwise.h"  // demc_pointwise_loglik, demc_waic
+#include "../../include/demc_loo.h"  // demc_loo
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -53,6 +54,7 @@
 #include "demc_quantile.hpp"  // demc_quantiles: likewise, demc_quantile.cpp
 #include "demc_cov.hpp"  // demc_covariance: likewise, demc_cov.cpp
 #include "demc_pointwise.hpp"  // demc_pointwise_loglik, demc_waic: likewise, demc_pointwise.cpp
+#include "demc_loo.hpp"  // demc_loo: likewise, demc_loo.cpp (with its host-only plan, demc_looplan.hpp)
 #include "demc_devmem.hpp"  // owners of the device memory, pinned memory, events and modules the handle holds
 #include "demc_prep.hpp"  // host-only: a model's data and constants, the prior table and its run-length forms, every refusal of those
 #include "demc_instances.hpp"  // one table per templated kernel, built from the lists above: every choice of an instance goes through them
@@ -1482,6 +1484,25 @@ int32_t demc_waic(demc_handle* h, int64_t row0, int64_t row1, double* total_out,
         return fail(h, r);
     std::string msg;
     const int rc = pw_waic_run(mv, hist_view(h, row0, row1), plan, h->stream, total_out, pointwise_out, msg);
+    return rc == DEMC_OK ? DEMC_OK : fail(h, rc, msg);
+    });
+}
+
+// PSIS-LOO (include/demc_loo.h): demc_waic's window and families under its own name, then the plan (demc_looplan.hpp) and the run
+// (demc_loo.cpp).  The cap on the draws is the call's own refusal and ranks last.
+int32_t demc_loo(demc_handle* h, int64_t row0, int64_t row1, double* total_out, double* pointwise_out) {
+    return guarded(h, [&]() -> int32_t {
+    if (!h) return DEMC_EINVAL;
+    USE_DEVICE(h);
+    const PwModelView mv = pw_model_view(h);
+    const bool window_ok = h->hist != nullptr && row0 >= 0 && row1 - row0 >= 1 && row1 <= h->c.n_rows;
+    const LooPlan plan = plan_loo(mv.m, window_ok ? (long long)(row1 - row0) * h->P : 1);
+    if (Refusal r = check_pw_window(h->hist != nullptr, row0, row1, h->c.n_rows, h->c.n_groups_total != h->c.n_groups,
+                                    loo_args(plan.model, total_out || pointwise_out), kLooBadRows, kLooSharded))
+        return fail(h, r);
+    if (plan.refused) return fail(h, plan.refused);
+    std::string msg;
+    const int rc = loo_run(mv, hist_view(h, row0, row1), plan, h->stream, total_out, pointwise_out, msg);
     return rc == DEMC_OK ? DEMC_OK : fail(h, rc, msg);
     });
 }

@@ -30,8 +30,8 @@ constexpr long long kPwMaxDraws = 1LL << 40;          // S of either call: far b
 
 // the families as the kernels are instantiated (the handle's family and likelihood mode decide: pw_family)
 enum PwFamily : int { PW_NONE = -1, PW_GAUSSIAN = 0, PW_BINOMIAL = 1, PW_LNR = 2, PW_LBA = 3, PW_MVN_ISO = 4, PW_MVN_FULL = 5 };
-enum PwCall : int { PW_LOGLIK = 0, PW_WAIC = 1 };
-constexpr const char* kPwWho[2] = {"demc_pointwise_loglik", "demc_waic"};
+enum PwCall : int { PW_LOGLIK = 0, PW_WAIC = 1, PW_LOO = 2 };  // (PW_LOO: demc_loo of demc_looplan.hpp borrows pw_family and the window check)
+constexpr const char* kPwWho[3] = {"demc_pointwise_loglik", "demc_waic", "demc_loo"};
 
 constexpr int kPwFamSim = 101;  // the runtime's internal family of a simulation likelihood (FAM_SIM of demc_simlike.hpp: the runtime asserts that they agree)
 
@@ -109,11 +109,12 @@ inline Refusal pw_waic_args(const Refusal& model, bool any_output) {
     if (model) return model;
     return any_output ? Refusal() : Refusal{DEMC_EINVAL, kPwNoOutput};
 }
-inline Refusal check_pw_window(bool stored, long long row0, long long row1, long long n_rows, bool sharded, Refusal args = Refusal()) {
+inline Refusal check_pw_window(bool stored, long long row0, long long row1, long long n_rows, bool sharded, Refusal args = Refusal(),
+                               const char* bad_rows = kPwBadRows, const char* sharded_text = kPwSharded) {
     if (!stored) return Refusal{DEMC_EINVAL, kHistoryNotStored};
-    if (row0 < 0 || row1 - row0 < 1 || row1 > n_rows) return Refusal{DEMC_EINVAL, kPwBadRows};
+    if (row0 < 0 || row1 - row0 < 1 || row1 > n_rows) return Refusal{DEMC_EINVAL, bad_rows};
     if (args) return args;
-    if (sharded) return Refusal{DEMC_EINVAL, kPwSharded};
+    if (sharded) return Refusal{DEMC_EINVAL, sharded_text};
     return Refusal();
 }
 

@@ -282,6 +282,8 @@ include("DEMCHIPQuantile.jl")
 include("DEMCHIPCov.jl")
 # ... and model comparison (include/demc_pointwise.h): `waic`, `pointwise_loglik`, `compare_waic`, likewise
 include("DEMCHIPPointwise.jl")
+# ... and PSIS-LOO with its khat diagnostic (the header beside it): `loo`, `compare_loo`, likewise
+include("DEMCHIPLoo.jl")
 
 "final state of the particle objects behind handle `h` (bundle_samples reads accept/lp from them; Θ for completeness)"
 function pull_state!(h, particles, Pl, D, shapes, lens, offs)
