@@ -38,6 +38,8 @@ PW_MAX_CELLS = 1 << 27  # DEMC_PW_MAX_CELLS
 LOO_EXPORTS = ["demc_loo"]  # include/demc_loo.h: PSIS-LOO over the history
 LOO_NTOTAL, LOO_NPOINT = 8, 6  # DEMC_LOO_NTOTAL, DEMC_LOO_NPOINT
 LOO_MAX_DRAWS = 1 << 22  # DEMC_LOO_MAX_DRAWS
+BRIDGE_EXPORTS = ["demc_bridge"]  # include/demc_bridge.h: the marginal likelihood by bridge sampling over the history
+BRIDGE_NOUT, BRIDGE_MAX_D, BRIDGE_MAX_DRAWS, BRIDGE_MAX_ITER = 12, 64, 1 << 22, 1000  # DEMC_BRIDGE_NOUT, _MAX_D, _MAX_DRAWS, _MAX_ITER
 COMM_ID_BYTES = 128
 _NOT_STATUS = {"demc_last_error": C.c_char_p, "demc_multi_last_error": C.c_char_p, "demc_multi_shard": C.c_void_p}
 
@@ -158,6 +160,7 @@ def load():
     L.demc_pointwise_loglik.argtypes = [H, _dp, C.c_int64, _dp]
     L.demc_waic.argtypes = [H, C.c_int64, C.c_int64, _dp, _dp]
     L.demc_loo.argtypes = [H, C.c_int64, C.c_int64, _dp, _dp]
+    L.demc_bridge.argtypes = [H, C.c_int64, C.c_int64, C.c_int64, C.c_uint64, _dp, _dp, _dp, _dp]
     L.demc_step.argtypes = [H, C.c_int64, C.c_int32]
     L.demc_update.argtypes = [H, C.c_int64, C.c_int32]
     L.demc_migration_due.argtypes = [C.POINTER(DemcConfig), C.c_int64]
@@ -190,7 +193,7 @@ def load():
     L.demc_multi_size.argtypes = [H]
     L.demc_multi_shard.argtypes = [H, C.c_int32]
     L.demc_multi_step.argtypes = [H, C.c_int64, C.c_int32]
-    for name in EXPORTS + SUMMARY_EXPORTS + QUANTILE_EXPORTS + COV_EXPORTS + PW_EXPORTS + LOO_EXPORTS:  # every entry point returns an int32 status, except the error strings and the shard accessor
+    for name in EXPORTS + SUMMARY_EXPORTS + QUANTILE_EXPORTS + COV_EXPORTS + PW_EXPORTS + LOO_EXPORTS + BRIDGE_EXPORTS:  # every entry point returns an int32 status, except the error strings and the shard accessor
         getattr(L, name).restype = _NOT_STATUS.get(name, C.c_int32)
     _lib = L
     return L
@@ -243,6 +246,7 @@ class HipEngine:
         self.D = self.cfg.D
         self.n_obs = 1
         self.family = None  # the DEMC_FAM_* code of set_model (None: no model, or one set from source / by a simulator)
+        self.has_model = self.simulated = False  # a model of any kind is set; it is a simulation likelihood (set_model_sim)
 
     def close(self):
         if getattr(self, "h", None):
@@ -271,6 +275,7 @@ class HipEngine:
                                        0 if hyper is None else hyper.size))
         self.n_obs = int(dims[0]) if dims.size else 1  # observations of the model (the per-observation calls size their outputs by it)
         self.family = int(family)
+        self.has_model, self.simulated = True, False
 
     def set_model_source(self, source, data, dims, hyper=None):
         """user log-density plug-in: HIP source defining demc_user_obs(...) (include/demc.h), JIT-compiled for gfx950"""
@@ -280,6 +285,7 @@ class HipEngine:
         self._ck(self.L.demc_set_model_source(self.h, source.encode(), _d(data), dims.ctypes.data_as(_lp), dims.size,
                                               _d(hyper), 0 if hyper is None else hyper.size))
         self.family = None
+        self.has_model, self.simulated = True, False
 
     def set_model_source_row(self, source, data, dims, hyper=None, has_prior=False):
         """whole-row plug-in: HIP source defining demc_user_loglike_row(...) [and demc_user_prior_row(...)] (include/demc.h)"""
@@ -289,6 +295,7 @@ class HipEngine:
         self._ck(self.L.demc_set_model_source_row(self.h, source.encode(), _d(data), dims.ctypes.data_as(_lp), dims.size,
                                                   _d(hyper), 0 if hyper is None else hyper.size, 1 if has_prior else 0))
         self.family = None
+        self.has_model, self.simulated = True, False
 
     def set_model_sim(self, simulator, estimator, n_sim, data, hyper=None, source=None):
         """simulation-based likelihood (demc_set_model_sim, include/demc.h): `simulator` / `estimator` are the DEMC_SIM_* /
@@ -303,6 +310,7 @@ class HipEngine:
         self._ck(self.L.demc_set_model_sim(self.h, simulator, estimator, n_sim, None if source is None else source.encode(),
                                            _d(data), n_obs, _d(hyper), 0 if hyper is None else hyper.size))
         self.family = None
+        self.has_model, self.simulated = True, True
 
     def set_priors(self, kind, a, b, ref=None):
         kind = np.ascontiguousarray(kind, dtype=np.int32)
@@ -444,6 +452,36 @@ class HipEngine:
         pt = np.empty((self.n_obs, LOO_NPOINT)) if pointwise else None
         self._ck(self.L.demc_loo(self.h, row0, row1, _d(tot), _d(pt)))
         return tot, pt
+
+    def bridge_served(self):
+        """what demc_bridge would refuse about this handle whatever the rows, asked BEFORE a run (summarize(..., bridge=True)): raises
+        the DemcError the call itself would end in -- no model, a simulation likelihood, a sharded handle, D above the cap.  The call
+        remains the judge."""
+        who = "demc_bridge: "
+        if not self.has_model:
+            raise DemcError(EINVAL, who + "no model is set on this handle")
+        if self.simulated:
+            raise DemcError(EUNSUPPORTED, who + "a simulation likelihood (demc_set_model_sim) gives a noisy log posterior; bridge sampling needs an exact one")
+        if self.cfg.n_groups_total != self.cfg.n_groups:
+            raise DemcError(EINVAL, who + "sharded handle")
+        if self.D > BRIDGE_MAX_D:
+            raise DemcError(EINVAL, who + f"D = {self.D} is above the cap of {BRIDGE_MAX_D}")
+
+    def bridge(self, row0, row1, n_prop=0, seed=0, diagnostics=False):
+        """the log marginal likelihood by bridge sampling over history rows [row0,row1), formed on the device (demc_bridge of
+        include/demc_bridge.h): the first half of the rows fits a Normal proposal on the real line, the second half and
+        n_prop proposal draws (0: as many) feed the iteration -> out[12] in the order of chains.BRIDGE_OUT; with diagnostics
+        (out, prop[N2][D+3] = theta, lp, logJ, log g, post[N1][3] = lp, logJ, log g, (m[D], L[D][D]))"""
+        out = np.full(BRIDGE_NOUT, np.nan)
+        if not diagnostics:
+            self._ck(self.L.demc_bridge(self.h, row0, row1, n_prop, seed, _d(out), None, None, None))
+            return out
+        R = max(int(row1) - int(row0), 0)
+        n1 = (R - R // 2) * self.P
+        n2 = n_prop if n_prop > 0 else n1
+        prop, post, fit = np.full((max(n2, 1), self.D + 3), np.nan), np.full((max(n1, 1), 3), np.nan), np.full(self.D + self.D * self.D, np.nan)
+        self._ck(self.L.demc_bridge(self.h, row0, row1, n_prop, seed, _d(out), _d(prop), _d(post), _d(fit)))
+        return out, prop[:n2], post[:n1], (fit[:self.D].copy(), fit[self.D:].reshape(self.D, self.D).copy())
 
     def step(self, iter0, n_iters=1):
         self._ck(self.L.demc_step(self.h, iter0, n_iters))

@@ -3,7 +3,8 @@ summary statistics the reference's tests read from describe(chains)[1] (:mean, :
 its Monte-Carlo standard error and the autocorrelation MCMCChains adds to them (DESIGN.md section 5.5 is the definition; the device
 computes the same numbers from the history without exporting it: demc_summarize), the quantile table of describe(chains)
 (demc_quantiles on the device), cov(chains) / cor(chains) (demc_covariance), and WAIC from
-the per-observation log-densities (demc_waic), and PSIS-LOO from the same terms (demc_loo)."""
+the per-observation log-densities (demc_waic), PSIS-LOO from the same terms (demc_loo), and the marginal likelihood by
+bridge sampling from two vectors of log ratios (demc_bridge)."""
 import math
 
 import numpy as np
@@ -20,12 +21,14 @@ class Summary:
     then acceptance and lp.  `rho` (or None): [series][lags] autocorrelations, NaN beyond the lags that were evaluated.
     `quantiles` (or None): [series][len(probs)] quantiles at `probs`, chains pooled.  `cov_matrix` / `cor_matrix`
     (or None): the covariance and correlation of the series `cov_names`, chains pooled.  `waic` (or None): the Waic
-    record of the same rows.  `loo` (or None): the Loo record of the same rows."""
+    record of the same rows.  `loo` (or None): the Loo record of the same rows.
+    `bridge` (or None): the Bridge record of the same rows."""
 
     def __init__(self, names, values, internals=("acceptance", "lp"), rho=None, quantiles=None, probs=None, cov=None, cor=None,
-                 cov_names=None, waic=None, loo=None):
+                 cov_names=None, waic=None, loo=None, bridge=None):
         self.waic = waic
         self.loo = loo
+        self.bridge = bridge
         self.names = list(names)
         self.values = np.asarray(values, dtype=np.float64).reshape(len(self.names), len(SUMMARY_COLS))
         self.internals = list(internals)
@@ -465,3 +468,225 @@ def compare_loo(a, b):
     with np.errstate(all="ignore"):
         se = float(np.sqrt(N * (((d - d.sum() / N) ** 2).sum() / np.longdouble(N - 1)))) if N > 1 else float("nan")
     return dict(elpd_diff=float(d.sum()), se_diff=se)
+
+
+# ---- the marginal likelihood by bridge sampling (demc_bridge on the device) --------------------------------
+
+BRIDGE_OUT = ("logml", "re2_prop", "re2_post_iid", "n_iter", "converged", "n_fit", "n1", "n2", "l_star", "n_zero_prop", "n_nonfinite",
+              "rel_change")  # demc_bridge's out, in order (DEMC_BRIDGE_NOUT)
+BRIDGE_STREAM = 7  # the Philox stream of the proposal draws
+BRIDGE_TOL, BRIDGE_MAX_ITER = 1e-10, 1000
+
+
+class Bridge:
+    """The twelve values of demc_bridge by name (BRIDGE_OUT) and, when the diagnostics were asked for, the device's own stages:
+    prop[N2][D+3] = (theta, lp, logJ, log g) of the proposal draws, post[N1][3] = (lp, logJ, log g) of the estimate half, fit = (m, L).
+    `rho` is the autocorrelation factor se() is scaled by when none is given to compare_bridge (1: independent draws)."""
+
+    def __init__(self, out, prop=None, post=None, fit=None, rho=1.0):
+        out = np.asarray(out, dtype=np.float64).reshape(len(BRIDGE_OUT))
+        for nm, v in zip(BRIDGE_OUT, out):
+            setattr(self, nm, float(v))
+        self.out = out
+        self.prop, self.post, self.fit = prop, post, fit
+        self.rho = float(rho)
+
+    def se(self, rho=1.0):
+        """the approximate standard error of logml: sqrt(re2_prop + rho re2_post_iid), rho the autocorrelation factor of the posterior
+        draws (kept draws / effective draws; 1: independent)"""
+        return math.sqrt(self.re2_prop + rho * self.re2_post_iid)
+
+    def __repr__(self):
+        s = f"Bridge(logml={self.logml:.4f} (se {self.se(self.rho):.4f}), {int(self.n_iter)} iterations"
+        if not self.converged:
+            s += ", NOT converged"
+        if self.n_zero_prop:
+            s += f", {int(self.n_zero_prop)} of {int(self.n2)} proposal draws outside the support"
+        if self.n_nonfinite:
+            s += f", {int(self.n_nonfinite)} log ratios not finite"
+        return s + ")"
+
+
+def _bridge_bounds(D, lo, hi):
+    lo = np.full(D, -np.inf) if lo is None else np.asarray(lo, dtype=np.float64).reshape(D)
+    hi = np.full(D, np.inf) if hi is None else np.asarray(hi, dtype=np.float64).reshape(D)
+    return lo, hi, (lo > -np.inf).astype(int) + 2 * (hi < np.inf).astype(int)  # 0 none, 1 lower, 2 upper, 3 both
+
+
+def _bridge_logjac(xi, lo, hi, kind):
+    lj = np.zeros(xi.shape[0])
+    for k in range(xi.shape[1]):
+        x = xi[:, k]
+        if kind[k] in (1, 2):
+            lj = lj + x
+        elif kind[k] == 3:
+            a = np.abs(x)
+            lj = lj + (math.log(hi[k] - lo[k]) - a - 2.0 * np.log1p(np.exp(-a)))
+    return lj
+
+
+def bridge_transform(theta, lo=None, hi=None):
+    """theta[n][D] and the bounds -> (xi[n][D], logJ[n]) of DESIGN.md 5.10; a draw on or outside a finite bound gives a xi that is not finite"""
+    theta = np.asarray(theta, dtype=np.float64)
+    lo, hi, kind = _bridge_bounds(theta.shape[1], lo, hi)
+    xi = theta.copy()
+    with np.errstate(all="ignore"):
+        for k in range(theta.shape[1]):
+            t = theta[:, k]
+            if kind[k] == 1:
+                xi[:, k] = np.log(t - lo[k])
+            elif kind[k] == 2:
+                xi[:, k] = np.log(hi[k] - t)
+            elif kind[k] == 3:
+                u = (t - lo[k]) / (hi[k] - lo[k])
+                xi[:, k] = np.log(u) - np.log1p(-u)
+        return xi, _bridge_logjac(xi, lo, hi, kind)
+
+
+def bridge_inverse(xi, lo=None, hi=None):
+    """xi[n][D] -> (theta[n][D], logJ[n])"""
+    xi = np.asarray(xi, dtype=np.float64)
+    lo, hi, kind = _bridge_bounds(xi.shape[1], lo, hi)
+    th = xi.copy()
+    with np.errstate(all="ignore"):
+        for k in range(xi.shape[1]):
+            x = xi[:, k]
+            if kind[k] == 1:
+                th[:, k] = lo[k] + np.exp(x)
+            elif kind[k] == 2:
+                th[:, k] = hi[k] - np.exp(x)
+            elif kind[k] == 3:
+                th[:, k] = lo[k] + (hi[k] - lo[k]) / (1.0 + np.exp(-x))
+        return th, _bridge_logjac(xi, lo, hi, kind)
+
+
+def bridge_cholesky(V):
+    """the lower factor of V column by column, the sums in index order (csrc/demc_bridgeplan.hpp); ValueError at a pivot that is not positive"""
+    V = np.asarray(V, dtype=np.float64)
+    D = V.shape[0]
+    L = np.zeros((D, D))
+    for j in range(D):
+        s = V[j, j]
+        for k in range(j):
+            s -= L[j, k] * L[j, k]
+        if not (s > 0.0) or not math.isfinite(s):
+            raise ValueError(f"bridge_cholesky: pivot {j} of {D} is not positive")
+        L[j, j] = math.sqrt(s)
+        for i in range(j + 1, D):
+            t = V[i, j]
+            for k in range(j):
+                t -= L[i, k] * L[j, k]
+            L[i, j] = t / L[j, j]
+    return L
+
+
+def bridge_fit(xi):
+    """xi[n][D] of the fit half -> (m[D], L[D][D]): the mean, and the lower Cholesky factor of the covariance (n - 1 divisor, the
+    corrected two-pass form of DESIGN.md 5.7, sums in np.longdouble)"""
+    x = np.asarray(xi, dtype=np.float64).astype(np.longdouble)
+    n = x.shape[0]
+    mhat = x.sum(axis=0) / n
+    c = x - mhat
+    s = c.sum(axis=0)
+    S = c.T @ c - np.outer(s, s) / n
+    return (mhat + s / n).astype(np.float64), bridge_cholesky((S / (n - 1)).astype(np.float64))
+
+
+def bridge_logg(xi, m, L):
+    """log g(xi) = -|L^-1 (xi - m)|^2 / 2 - sum_k log L_kk - (D / 2) log 2 pi, by forward substitution"""
+    xi, m, L = np.asarray(xi, dtype=np.float64), np.asarray(m, dtype=np.float64), np.asarray(L, dtype=np.float64)
+    n, D = xi.shape
+    y = np.zeros((n, D))
+    for k in range(D):
+        t = xi[:, k] - m[k]
+        for c in range(k):
+            t = t - L[k, c] * y[:, c]
+        y[:, k] = t / L[k, k]
+    return -0.5 * (y * y).sum(axis=1) - (np.log(np.diag(L)).sum() + 0.5 * D * math.log(2.0 * math.pi))
+
+
+def philox4x32_10(ctr, key):
+    """Philox4x32-10 over numpy arrays: ctr = four arrays of 32-bit words, key = two words (csrc/demc_philox.hpp) -> four uint64 arrays"""
+    M32 = np.uint64(0xFFFFFFFF)
+    c = [np.asarray(w, dtype=np.uint64) & M32 for w in ctr]
+    k0, k1 = int(key[0]) & 0xFFFFFFFF, int(key[1]) & 0xFFFFFFFF
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c[0], np.uint64(0xCD9E8D57) * c[2]
+        c = [(p1 >> np.uint64(32)) ^ c[1] ^ np.uint64(k0), p1 & M32, (p0 >> np.uint64(32)) ^ c[3] ^ np.uint64(k1), p0 & M32]
+        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    return c
+
+
+def bridge_normals(n, D, seed):
+    """z[n][D]: draw j takes Philox block k at (key = seed, stream 7, sweep 0, iteration 0, entity j, block k); u1 = u53(x, y),
+    u2 = u53(z, w); z_2k = sqrt(-2 log(1 - u1)) cos(2 pi u2), z_2k+1 = ... sin(2 pi u2)"""
+    nb = (D + 1) // 2
+    ent, blk = np.meshgrid(np.arange(n, dtype=np.uint64), np.arange(nb, dtype=np.uint64), indexing="ij")
+    zero = np.zeros_like(ent)
+    c = philox4x32_10([blk, ent, zero, zero + np.uint64(BRIDGE_STREAM << 24)], (seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF))
+    u53 = lambda lo, hi: (((hi << np.uint64(32)) | lo) >> np.uint64(11)).astype(np.float64) * 2.0 ** -53  # noqa: E731
+    u1, u2 = u53(c[0], c[1]), u53(c[2], c[3])
+    rad = np.sqrt(-2.0 * np.log(1.0 - u1))
+    z = np.empty((n, 2 * nb))
+    z[:, 0::2] = rad * np.cos(2.0 * math.pi * u2)
+    z[:, 1::2] = rad * np.sin(2.0 * math.pi * u2)
+    return z[:, :D]
+
+
+def bridge_draws(m, L, n, seed, lo=None, hi=None):
+    """the n proposal draws of DESIGN.md 5.10 -> (theta[n][D], logJ[n], log g[n]): xi = m + L z with bridge_normals' z, the inverse
+    transform, and log g = -|z|^2 / 2 - sum_k log L_kk - (D / 2) log 2 pi"""
+    m, L = np.asarray(m, dtype=np.float64), np.asarray(L, dtype=np.float64)
+    D = m.size
+    z = bridge_normals(n, D, seed)
+    xi = m[None, :] + z @ np.tril(L).T
+    theta, lj = bridge_inverse(xi, lo, hi)
+    return theta, lj, -0.5 * (z * z).sum(axis=1) - (np.log(np.diag(L)).sum() + 0.5 * D * math.log(2.0 * math.pi))
+
+
+def bridge_from_logs(l1, l2, n_fit=float("nan"), lp2=None):
+    """DESIGN.md 5.10 from the two log-ratio vectors: l1[N1] over the estimate half, l2[N2] over the proposal draws -> Bridge.  The sums
+    run in np.longdouble and are rounded to float64; r, the terms and the test of convergence are float64 as on the device.  lp2 (the
+    log posterior of the proposal draws) only feeds the count n_zero_prop; without it the -Inf among l2 are counted."""
+    l1, l2 = np.asarray(l1, dtype=np.float64).ravel(), np.asarray(l2, dtype=np.float64).ravel()
+    N1, N2 = l1.size, l2.size
+    nan, inf = float("nan"), float("inf")
+    s1, s2 = N1 / (N1 + N2), N2 / (N1 + N2)
+    n_zero = int(np.isneginf(l2 if lp2 is None else np.asarray(lp2)).sum())
+    n_bad = int((np.isnan(l1) | np.isposinf(l1)).sum() + (np.isnan(l2) | np.isposinf(l2)).sum())
+    ok1 = l1[~np.isnan(l1)]
+    l_star = float(ok1.max()) if ok1.size else nan
+    if n_bad or not math.isfinite(l_star):
+        return Bridge([nan, nan, nan, 0, 0, n_fit, N1, N2, l_star, n_zero, n_bad, nan])
+    mean = lambda v: float(v.astype(np.longdouble).sum() / v.size)  # noqa: E731
+    with np.errstate(all="ignore"):
+        e1, e2 = np.exp(l1 - l_star), np.exp(l_star - l2)
+        big = np.isposinf(e2)
+        f1_of = lambda r: np.where(big, 0.0, 1.0 / (s1 + (s2 * r) * np.where(big, 1.0, e2)))  # noqa: E731
+        r, n_iter, conv, rel = 1.0, 0, 0, 0.0
+        while n_iter < BRIDGE_MAX_ITER:
+            rn = mean(f1_of(r)) / mean(1.0 / (s1 * e1 + s2 * r))
+            n_iter += 1
+            change = abs(rn - r)
+            rel = change / abs(rn)
+            r = rn
+            if change <= BRIDGE_TOL * abs(rn):
+                conv = 1
+                break
+            if not (math.isfinite(rn) and rn > 0.0):
+                break
+        f1, f2 = f1_of(r), 1.0 / ((s1 * e1) / r + s2)
+        m1, m2 = mean(f1), mean(f2)
+        ss = lambda f, m: float(((f - m) ** 2).astype(np.longdouble).sum())  # noqa: E731
+        re1 = ss(f1, m1) / (N2 - 1) / (m1 * m1) / N2 if N2 > 1 else nan
+        re2 = ss(f2, m2) / (N1 - 1) / (m2 * m2) / N1 if N1 > 1 else nan
+        return Bridge([math.log(r) + l_star if r > 0 else nan, re1, re2, n_iter, conv, n_fit, N1, N2, l_star, n_zero, n_bad, rel])
+
+
+def compare_bridge(a, b, prior_odds=1.0):
+    """two Bridge records of two models fitted to the SAME data -> dict(log_bf = logml_a - logml_b, se = sqrt(se_a^2 + se_b^2) with each
+    record's own rho, prob_a and prob_b = the posterior model probabilities under prior_odds = p(a) / p(b)): positive log_bf favours a"""
+    log_bf = a.logml - b.logml
+    t = log_bf + math.log(prior_odds)
+    pa = 1.0 / (1.0 + math.exp(-t)) if t >= 0 else math.exp(t) / (1.0 + math.exp(t))
+    return dict(log_bf=log_bf, se=math.sqrt(a.se(a.rho) ** 2 + b.se(b.rho) ** 2), prob_a=pa, prob_b=1.0 - pa)

@@ -20,6 +20,7 @@
 #include "../../include/demc_cov.h"  // demc_covariance
 #include "../../include/demc_pointwise.h"  // demc_pointwise_loglik, demc_waic
 #include "../../include/demc_loo.h"  // demc_loo
+#include "../../include/demc_bridge.h"  // demc_bridge
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -55,6 +56,7 @@
 #include "demc_cov.hpp"  // demc_covariance: likewise, demc_cov.cpp
 #include "demc_pointwise.hpp"  // demc_pointwise_loglik, demc_waic: likewise, demc_pointwise.cpp
 #include "demc_loo.hpp"  // demc_loo: likewise, demc_loo.cpp (with its host-only plan, demc_looplan.hpp)
+#include "demc_bridge.hpp"  // demc_bridge: likewise, demc_bridge.cpp (with its host-only plan, demc_bridgeplan.hpp)
 #include "demc_devmem.hpp"  // owners of the device memory, pinned memory, events and modules the handle holds
 #include "demc_prep.hpp"  // host-only: a model's data and constants, the prior table and its run-length forms, every refusal of those
 #include "demc_instances.hpp"  // one table per templated kernel, built from the lists above: every choice of an instance goes through them
@@ -69,6 +71,7 @@ using namespace demc;
 #define DEMC_ARCH_STR "gfx950"  // the Makefile passes its ARCH, so that the JIT-compiled plug-in matches the library
 #endif
 static_assert(kPwFamSim == FAM_SIM, "demc_pwplan.hpp names the simulation likelihood by the runtime's family");
+static_assert(kBridgeFamSim == FAM_SIM, "demc_bridgeplan.hpp names the simulation likelihood by the runtime's family");
 static_assert(kPrepOdeMaxT == kOdeMaxT && kPrepOdeMaxSubsteps == kOdeMaxSubsteps && kPrepSimMaxN == kSimMaxN && kPrepSimChoiceMaxN == kSimChoiceMaxN,
               "demc_prep.hpp refuses by the kernels' caps");
 
@@ -1401,6 +1404,8 @@ static HistView hist_view(const demc_handle* h, int64_t row0, int64_t row1) {
     return HistView{h->hist, h->acc_hist, h->lp_hist, h->id_hist, h->P, (long long)row0, (long long)row1, (long long)h->c.group_offset * h->c.Np,
                     h->c.D, h->hist_ld};
 }
+// the one place the covariance is planned: demc_covariance over the history, demc_bridge over the fit half of its xi buffer
+static CovPlan cov_plan(long long N, int D, const int32_t* cols, int n_cols) { return plan_cov(N, D, cols, n_cols); }
 static Refusal check_window(const demc_handle* h, PostCall call, int64_t row0, int64_t row1, Refusal args = Refusal()) {
     return check_history_window(call, h->hist != nullptr, row0, row1, h->c.n_rows, h->c.n_groups_total != h->c.n_groups, std::move(args));
 }
@@ -1440,7 +1445,7 @@ int32_t demc_covariance(demc_handle* h, int64_t row0, int64_t row1, const int32_
     if (!mean_out && !cov_out && !cor_out) return fail(h, DEMC_EINVAL, "demc_covariance: mean_out, cov_out and cor_out are all NULL");
     int sel[kCovMaxCols];
     if (Refusal r = check_window(h, POST_COVARIANCE, row0, row1, select_columns(h->c.D, cols, (int)n_cols, sel))) return fail(h, r);
-    const CovPlan plan = plan_cov((row1 - row0) * h->P, h->c.D, cols, (int)n_cols);
+    const CovPlan plan = cov_plan((row1 - row0) * h->P, h->c.D, cols, (int)n_cols);
     if (plan.refused) return fail(h, plan.refused);
     std::string msg;
     const int rc = cov_run(hist_view(h, row0, row1), plan, h->stream, mean_out, cov_out, cor_out, msg);
@@ -1503,6 +1508,30 @@ int32_t demc_loo(demc_handle* h, int64_t row0, int64_t row1, double* total_out, 
     if (plan.refused) return fail(h, plan.refused);
     std::string msg;
     const int rc = loo_run(mv, hist_view(h, row0, row1), plan, h->stream, total_out, pointwise_out, msg);
+    return rc == DEMC_OK ? DEMC_OK : fail(h, rc, msg);
+    });
+}
+
+// Bridge sampling (include/demc_bridge.h): every refusal and the plan are demc_bridgeplan.hpp's, the run is demc_bridge.cpp's; the
+// callback hands it evaluate_rows, the path behind demc_logpost and demc_set_state, for P rows it has laid out on the device.
+int32_t demc_bridge(demc_handle* h, int64_t row0, int64_t row1, int64_t n_prop, uint64_t seed, double* out, double* prop_out, double* post_out,
+                    double* fit_out) {
+    return guarded(h, [&]() -> int32_t {
+    if (!h) return DEMC_EINVAL;
+    USE_DEVICE(h);
+    BridgeCall c;
+    c.stored = h->hist != nullptr; c.row0 = row0; c.row1 = row1; c.n_rows = h->c.n_rows; c.family = h->m.family; c.has_out = out != nullptr;
+    c.sharded = h->c.n_groups_total != h->c.n_groups; c.n_prop = n_prop; c.D = h->c.D; c.P = h->P;
+    const BridgePlan plan = plan_bridge(c);
+    if (plan.refused) return fail(h, plan.refused);
+    int32_t cols[kCovMaxCols];
+    for (int k = 0; k < h->c.D; ++k) cols[k] = k;
+    const CovPlan fit = cov_plan(plan.n_fit, h->c.D, cols, h->c.D);  // (every scalar of xi, none of the two internal series)
+    if (fit.refused) return fail(h, fit.refused);
+    HIPCHK(hipStreamSynchronize(h->stream));
+    std::string msg;
+    const int rc = bridge_run(hist_view(h, row0, row1), h->dimtab, plan, fit, seed, h->stream,
+                              [h](double* theta_dev, double* lp_dev) { return evaluate_rows(h, theta_dev, lp_dev); }, out, prop_out, post_out, fit_out, msg);
     return rc == DEMC_OK ? DEMC_OK : fail(h, rc, msg);
     });
 }

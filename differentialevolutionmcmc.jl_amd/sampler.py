@@ -3,7 +3,7 @@ C-ABI engine.  The per-iteration work -- step!/pstep! (main.jl:84-107) -- happen
 import numpy as np
 
 from . import _ffi
-from .chains import COV_MAX_COLS, Chains, Loo, Summary, Waic, series_cov, series_quantiles
+from .chains import COV_MAX_COLS, Bridge, Chains, Loo, Summary, Waic, series_cov, series_quantiles
 from .families import PRIOR_NORMAL_REF, Priors, SimulatedLikelihood, SourceLikelihood
 from .structs import (DE, HIPBackend, LOGLIKE_MODES, MCMCThreads, SCHEDULES, DEModel, Particle, maximize)
 
@@ -200,7 +200,10 @@ def _run(model, de, n_iter, backend, progress, engine_factory, summary=None):
     eng = (engine_factory or _ffi.HipEngine)(**cfg)
     want_waic = summary is not None and len(summary) > 5 and summary[5]
     want_loo = summary is not None and len(summary) > 6 and summary[6]
+    want_bridge = summary is not None and len(summary) > 7 and summary[7]
     try:
+        if want_bridge and not hasattr(eng, "bridge"):  # (no host form: the host route is what the call exists to avoid)
+            raise _ffi.DemcError(_ffi.EUNSUPPORTED, "summarize(..., bridge=True) needs an engine with bridge(row0, row1, n_prop, seed) (demc_bridge)")
         if want_loo and not hasattr(eng, "loo"):  # (no host form either: the terms exist on the device only)
             raise _ffi.DemcError(_ffi.EUNSUPPORTED, "summarize(..., loo=True) needs an engine with loo(row0, row1, pointwise): the per-observation "
                                                     "log-densities exist on the device only (demc_loo)")
@@ -212,6 +215,8 @@ def _run(model, de, n_iter, backend, progress, engine_factory, summary=None):
             eng.waic_served()
         if want_loo and hasattr(eng, "loo_served"):  # likewise demc_loo
             eng.loo_served()
+        if want_bridge and hasattr(eng, "bridge_served"):  # likewise demc_bridge
+            eng.bridge_served()
         theta, init_rows = sample_init(model, de, n_iter, lay, P)
         if de.n_initial > 0:
             eng.set_history_rows(0, init_rows)
@@ -240,6 +245,9 @@ def _run(model, de, n_iter, backend, progress, engine_factory, summary=None):
             lay["waic"] = Waic(*eng.waic(summary[0], summary[1], want_waic == "pointwise"))
         if want_loo:  # PSIS-LOO of the same kept rows (demc_loo)
             lay["loo"] = Loo(*eng.loo(summary[0], summary[1], want_loo == "pointwise"))
+        if want_bridge:  # the marginal likelihood from the same kept rows (demc_bridge)
+            opts = dict(want_bridge) if isinstance(want_bridge, dict) else {}
+            lay["bridge"] = Bridge(eng.bridge(summary[0], summary[1], int(opts.get("n_prop", 0)), int(opts.get("seed", 0))))
         if (summary is not None and hasattr(eng, "summarize") and (len(summary) < 4 or summary[3] is None or hasattr(eng, "quantiles"))
                 and (cov_cols is None or hasattr(eng, "covariance"))):
             # summarize(): the statistics (and the quantiles and the covariance, when asked for) on the device, no export at all
@@ -277,8 +285,8 @@ def _cov_cols(names, cor):
     return sel, [names.index(nm) for nm in sel]
 
 
-def summarize(model, de, *args, max_lag=0, quantiles=None, cor=False, waic=False, loo=False, progress=False, engine_factory=None, **kwargs):
-    """summarize(model, de, [HIPBackend(...)], n_iter, max_lag=0, quantiles=None, cor=False, waic=False, loo=False): the run of sample() followed by the summary
+def summarize(model, de, *args, max_lag=0, quantiles=None, cor=False, waic=False, loo=False, bridge=False, progress=False, engine_factory=None, **kwargs):
+    """summarize(model, de, [HIPBackend(...)], n_iter, max_lag=0, quantiles=None, cor=False, waic=False, loo=False, bridge=False): the run of sample() followed by the summary
     statistics of the rows bundle_samples keeps (offset = burnin or 0, quirk q1 included) -- computed on the device by
     demc_summarize, so that the history is never exported.  Returns a Summary (chains.py); equal to
     sample(...).summarystats(max_lag) for the same seed.  quantiles: a tuple of probs (chains.DEFAULT_QUANTILES) -- the same run
@@ -291,16 +299,27 @@ def summarize(model, de, *args, max_lag=0, quantiles=None, cor=False, waic=False
     keeps the N x 4 table too (what compare_waic reads).  There is no host form of this one: an engine without waic raises
     DemcError(EUNSUPPORTED).  loo: True -- the same run also forms PSIS-LOO over the kept rows on the device (demc_loo) and
     Summary.loo holds the Loo record; "pointwise" keeps the N x 6 table with khat per observation (what compare_loo reads).  A family
-    the call cannot serve is refused before the first step, as for waic."""
+    the call cannot serve is refused before the first step, as for waic.  bridge: True or dict(n_prop=, seed=) -- the same run also forms
+    the log marginal likelihood over the kept rows on the device by bridge sampling (demc_bridge) and Summary.bridge holds
+    the Bridge record (what compare_bridge reads); its rho, the factor se() scales the posterior term by, is taken as kept draws / ESS of lp
+    from the same table -- a stated approximation, not a spectral estimate."""
     backend, n_iter = _parse(args)
     Ns = n_iter - de.burnin if de.discard_burnin else n_iter
     offset = de.burnin if de.discard_burnin else 0
     probs = None if quantiles is None else tuple(float(q) for q in quantiles)
     want_cov = None if cor is False or cor is None else (True if cor is True else tuple(cor))
-    lay, res, state = _run(model, de, n_iter, backend, progress, engine_factory, summary=(offset, offset + Ns, max_lag, probs, want_cov, waic, loo))
+    if isinstance(bridge, dict) and set(bridge) - {"n_prop", "seed"}:
+        raise ValueError("bridge= takes True or dict(n_prop=, seed=)")
+    lay, res, state = _run(model, de, n_iter, backend, progress, engine_factory,
+                           summary=(offset, offset + Ns, max_lag, probs, want_cov, waic, loo, True if bridge is True else (dict(bridge) if isinstance(bridge, dict) else bridge)))
     out = _summary_of(model, de, lay, res, state, n_iter, max_lag, probs, want_cov)
     out.waic = lay.get("waic")
     out.loo = lay.get("loo")
+    out.bridge = lay.get("bridge")
+    if out.bridge is not None:  # the autocorrelation factor of the estimate half: kept draws / ESS of lp, from the table of the same rows
+        ess = out["lp"]["ess"]
+        kept = Ns * de.n_groups * de.Np
+        out.bridge.rho = max(1.0, kept / ess) if np.isfinite(ess) and ess > 0 else 1.0
     return out
 
 

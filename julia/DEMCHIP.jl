@@ -284,6 +284,8 @@ include("DEMCHIPCov.jl")
 include("DEMCHIPPointwise.jl")
 # ... and PSIS-LOO with its khat diagnostic (the header beside it): `loo`, `compare_loo`, likewise
 include("DEMCHIPLoo.jl")
+# ... and the marginal likelihood by bridge sampling (the header beside it): `bridge`, `compare_bridge`, likewise
+include("DEMCHIPBridge.jl")
 
 "final state of the particle objects behind handle `h` (bundle_samples reads accept/lp from them; Θ for completeness)"
 function pull_state!(h, particles, Pl, D, shapes, lens, offs)
