@@ -40,6 +40,8 @@ LOO_NTOTAL, LOO_NPOINT = 8, 6  # DEMC_LOO_NTOTAL, DEMC_LOO_NPOINT
 LOO_MAX_DRAWS = 1 << 22  # DEMC_LOO_MAX_DRAWS
 BRIDGE_EXPORTS = ["demc_bridge"]  # include/demc_bridge.h: the marginal likelihood by bridge sampling over the history
 BRIDGE_NOUT, BRIDGE_MAX_D, BRIDGE_MAX_DRAWS, BRIDGE_MAX_ITER = 12, 64, 1 << 22, 1000  # DEMC_BRIDGE_NOUT, _MAX_D, _MAX_DRAWS, _MAX_ITER
+RANK_EXPORTS = ["demc_rankstats", "demc_rank_series"]  # include/demc_rank.h: ess_bulk / ess_tail / rank-normalised rhat, one ranked series
+RANK_COLS, RANK_KIND_RANK, RANK_KIND_SCORE, RANK_KIND_FOLDED = 8, 0, 1, 2  # DEMC_RANK_COLS, DEMC_RANK_KIND_*
 COMM_ID_BYTES = 128
 _NOT_STATUS = {"demc_last_error": C.c_char_p, "demc_multi_last_error": C.c_char_p, "demc_multi_shard": C.c_void_p}
 
@@ -161,6 +163,8 @@ def load():
     L.demc_waic.argtypes = [H, C.c_int64, C.c_int64, _dp, _dp]
     L.demc_loo.argtypes = [H, C.c_int64, C.c_int64, _dp, _dp]
     L.demc_bridge.argtypes = [H, C.c_int64, C.c_int64, C.c_int64, C.c_uint64, _dp, _dp, _dp, _dp]
+    L.demc_rankstats.argtypes = [H, C.c_int64, C.c_int64, C.c_int32, _dp]
+    L.demc_rank_series.argtypes = [H, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _dp]
     L.demc_step.argtypes = [H, C.c_int64, C.c_int32]
     L.demc_update.argtypes = [H, C.c_int64, C.c_int32]
     L.demc_migration_due.argtypes = [C.POINTER(DemcConfig), C.c_int64]
@@ -193,7 +197,7 @@ def load():
     L.demc_multi_size.argtypes = [H]
     L.demc_multi_shard.argtypes = [H, C.c_int32]
     L.demc_multi_step.argtypes = [H, C.c_int64, C.c_int32]
-    for name in EXPORTS + SUMMARY_EXPORTS + QUANTILE_EXPORTS + COV_EXPORTS + PW_EXPORTS + LOO_EXPORTS + BRIDGE_EXPORTS:  # every entry point returns an int32 status, except the error strings and the shard accessor
+    for name in EXPORTS + SUMMARY_EXPORTS + QUANTILE_EXPORTS + COV_EXPORTS + PW_EXPORTS + LOO_EXPORTS + BRIDGE_EXPORTS + RANK_EXPORTS:  # every entry point returns an int32 status, except the error strings and the shard accessor
         getattr(L, name).restype = _NOT_STATUS.get(name, C.c_int32)
     _lib = L
     return L
@@ -452,6 +456,22 @@ class HipEngine:
         pt = np.empty((self.n_obs, LOO_NPOINT)) if pointwise else None
         self._ck(self.L.demc_loo(self.h, row0, row1, _d(tot), _d(pt)))
         return tot, pt
+
+    def rankstats(self, row0, row1, max_lag=0):
+        """ess_bulk, ess_tail and the rank-normalised rhat of history rows [row0,row1) formed on the device (demc_rankstats of
+        include/demc_rank.h): the pooled history of every series sorted and ranked, the normal scores, the tail
+        indicators and the folded series summarised by demc_summarize's kernels -> out[D+2][8] in the order of chains.RANK_COLS"""
+        out = np.full((self.D + 2, RANK_COLS), np.nan)
+        self._ck(self.L.demc_rankstats(self.h, row0, row1, max_lag, _d(out)))
+        return out
+
+    def rank_series(self, row0, row1, series, kind=RANK_KIND_RANK):
+        """one series of the pool of rows [row0,row1) (demc_rank_series): kind 0 the average ranks, 1 the normal scores, 2 the average
+        ranks of |x - med| -> out[n][P], slot-keyed as get_history is (what a rank plot needs, at 1 / (D + 2) of an export)"""
+        n = max(int(row1) - int(row0), 0)
+        out = np.full((max(n, 1), self.P), np.nan)
+        self._ck(self.L.demc_rank_series(self.h, row0, row1, series, kind, _d(out)))
+        return out[:n]
 
     def bridge_served(self):
         """what demc_bridge would refuse about this handle whatever the rows, asked BEFORE a run (summarize(..., bridge=True)): raises

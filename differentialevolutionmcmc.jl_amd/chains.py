@@ -4,7 +4,8 @@ its Monte-Carlo standard error and the autocorrelation MCMCChains adds to them (
 computes the same numbers from the history without exporting it: demc_summarize), the quantile table of describe(chains)
 (demc_quantiles on the device), cov(chains) / cor(chains) (demc_covariance), and WAIC from
 the per-observation log-densities (demc_waic), PSIS-LOO from the same terms (demc_loo), and the marginal likelihood by
-bridge sampling from two vectors of log ratios (demc_bridge)."""
+bridge sampling from two vectors of log ratios (demc_bridge), and the rank-normalised diagnostics ess_bulk,
+ess_tail and rhat of the pooled, ranked history (demc_rankstats)."""
 import math
 
 import numpy as np
@@ -22,10 +23,12 @@ class Summary:
     `quantiles` (or None): [series][len(probs)] quantiles at `probs`, chains pooled.  `cov_matrix` / `cor_matrix`
     (or None): the covariance and correlation of the series `cov_names`, chains pooled.  `waic` (or None): the Waic
     record of the same rows.  `loo` (or None): the Loo record of the same rows.
-    `bridge` (or None): the Bridge record of the same rows."""
+    `bridge` (or None): the Bridge record of the same rows.  `rank` (or None): the RankStats record of the same
+    rows -- ess_bulk, ess_tail and the rank-normalised rhat."""
 
     def __init__(self, names, values, internals=("acceptance", "lp"), rho=None, quantiles=None, probs=None, cov=None, cor=None,
-                 cov_names=None, waic=None, loo=None, bridge=None):
+                 cov_names=None, waic=None, loo=None, bridge=None, rank=None):
+        self.rank = rank
         self.waic = waic
         self.loo = loo
         self.bridge = bridge
@@ -325,6 +328,134 @@ class Chains:
             rows.append(vals)
             rhos.append(rho)
         return Summary(self.names, rows, self.internals, np.stack(rhos) if rho_len > 0 else None)
+
+    def rankstats(self, max_lag=0):
+        """The RankStats of this object computed on the host (numpy): what demc_rankstats computes on the device for a history that
+        was never exported."""
+        return RankStats(self.names, [series_rankstats(self.value[:, j, :], max_lag) for j in range(len(self.names))], self.internals)
+
+
+# ---- rank-normalised diagnostics (DESIGN.md section 5.11; demc_rankstats on the device) -------------------------------------------
+RANK_COLS = ("rhat", "ess_bulk", "ess_tail", "rhat_bulk", "rhat_folded", "ess_q05", "ess_q95", "distinct")  # demc_rankstats' out (DEMC_RANK_COLS)
+RANK_PROBS = (0.5, 0.05, 0.95)  # med, q05, q95
+
+_PPND_A = (2.5090809287301226727e+3, 3.3430575583588128105e+4, 6.7265770927008700853e+4, 4.5921953931549871457e+4,
+           1.3731693765509461125e+4, 1.9715909503065514427e+3, 1.3314166789178437745e+2, 3.3871328727963666080e0)
+_PPND_B = (5.2264952788528545610e+3, 2.8729085735721942674e+4, 3.9307895800092710610e+4, 2.1213794301586595867e+4,
+           5.3941960214247511077e+3, 6.8718700749205790830e+2, 4.2313330701600911252e+1, 1.0)
+_PPND_C = (7.74545014278341407640e-4, 2.27238449892691845833e-2, 2.41780725177450611770e-1, 1.27045825245236838258e0,
+           3.64784832476320460504e0, 5.76949722146069140550e0, 4.63033784615654529590e0, 1.42343711074968357734e0)
+_PPND_D = (1.05075007164441684324e-9, 5.47593808499534494600e-4, 1.51986665636164571966e-2, 1.48103976427480074590e-1,
+           6.89767334985100004550e-1, 1.67638483018380384940e0, 2.05319162663775882187e0, 1.0)
+_PPND_E = (2.01033439929228813265e-7, 2.71155556874348757815e-5, 1.24266094738807843860e-3, 2.65321895265761230930e-2,
+           2.96560571828504891230e-1, 1.78482653991729133580e0, 5.46378491116411436990e0, 6.65790464350110377720e0)
+_PPND_F = (2.04426310338993978564e-15, 1.42151175831644588870e-7, 1.84631831751005468180e-5, 7.86869131145613259100e-4,
+           1.48753612908506148525e-2, 1.36929880922735805310e-1, 5.99832206555887937690e-1, 1.0)
+
+
+def _horner(r, c):  # s = s r + c, a multiplication then an addition: the operation order of csrc/demc_ppnd.hpp
+    s = np.full_like(r, c[0])
+    for ck in c[1:]:
+        s = s * r + ck
+    return s
+
+
+def ppnd16(p):
+    """the inverse of the standard normal distribution function, Wichura's AS 241 (PPND16), vectorised in the operation order of
+    csrc/demc_ppnd.hpp: the text the device runs, restated in numpy.  p = 0 -> -inf, 1 -> +inf, outside [0, 1] or NaN -> NaN"""
+    p = np.asarray(p, dtype=np.float64)
+    shape = p.shape
+    p = p.reshape(-1)
+    out = np.full(p.shape, float("nan"))
+    with np.errstate(all="ignore"):
+        ok = (p >= 0.0) & (p <= 1.0)
+        q = p - 0.5
+        mid = ok & (np.abs(q) <= 0.425)
+        qm = q[mid]
+        r = 0.180625 - qm * qm
+        out[mid] = qm * _horner(r, _PPND_A) / _horner(r, _PPND_B)
+        tail = ok & ~mid
+        pt, qt = p[tail], q[tail]
+        r = np.sqrt(-np.log(np.where(qt < 0.0, pt, 1.0 - pt)))
+        z = np.empty_like(r)
+        near = r <= 5.0
+        rn = r[near] - 1.6
+        z[near] = _horner(rn, _PPND_C) / _horner(rn, _PPND_D)
+        rf = r[~near] - 5.0
+        z[~near] = _horner(rf, _PPND_E) / _horner(rf, _PPND_F)
+        z[~(r < 1.0e300)] = float("inf")
+        out[tail] = np.where(qt < 0.0, -z, z)
+    return out.reshape(shape)
+
+
+def series_keys(x):
+    """the 64-bit keys of DESIGN.md 5.6, compared unsigned: the IEEE order with -0.0 before +0.0 and the NaNs beyond the infinities"""
+    b = np.ascontiguousarray(x, dtype=np.float64).view(np.uint64)
+    return b ^ np.where(b >> np.uint64(63) != 0, _ALL, _SIGN)
+
+
+def series_ranks(x):
+    """x (any shape; the chains are pooled) -> (r with x's shape, distinct, has_nan): the average
+    rank r = L + (E + 1) / 2 of every value among the keys of the pool, the number of distinct keys, whether a key is a NaN's"""
+    x = np.asarray(x, dtype=np.float64)
+    k = series_keys(x).reshape(-1)
+    if k.size < 1:
+        raise ValueError("series_ranks needs at least one value")
+    ks = np.sort(k)
+    lo = np.searchsorted(ks, k, side="left")
+    hi = np.searchsorted(ks, k, side="right")
+    r = lo.astype(np.float64) + ((hi - lo).astype(np.float64) + 1.0) / 2.0
+    distinct = 1 + int(np.count_nonzero(ks[1:] != ks[:-1]))
+    return r.reshape(x.shape), distinct, bool(ks[0] < _KEY_NEG_INF or ks[-1] > _KEY_POS_INF)
+
+
+def normal_scores(r, N):
+    """step 3: z = Phi^-1((r - 3/8) / (N + 1/4)), evaluated as written"""
+    return ppnd16((np.asarray(r, dtype=np.float64) - 0.375) / (float(N) + 0.25))
+
+
+def series_rankstats(x, max_lag=0):
+    """DESIGN.md 5.11 for one series x[n][m] (iterations x chains) on the host -> (rhat, ess_bulk, ess_tail, rhat_bulk, rhat_folded,
+    ess_q05, ess_q95, distinct): the keys sorted, AS 241 for the scores, series_summary and series_quantiles for the rest -- what
+    demc_rankstats computes on the device"""
+    x = np.asarray(x, dtype=np.float64)
+    nan = float("nan")
+    N = x.size
+    r, distinct, has_nan = series_ranks(x)
+    if has_nan:
+        return (nan,) * len(RANK_COLS)
+    bulk = series_summary(normal_scores(r, N), max_lag)[0]
+    med, q05, q95 = (float(v) for v in series_quantiles(x, RANK_PROBS))
+    with np.errstate(all="ignore"):
+        zeta = np.abs(x - med)
+    r2, _, nan2 = series_ranks(zeta)
+    rhat_folded = nan if nan2 else series_summary(normal_scores(r2, N), max_lag)[0][2]
+    e05 = series_summary((x <= q05).astype(np.float64), max_lag)[0][3]
+    e95 = series_summary((x <= q95).astype(np.float64), max_lag)[0][3]
+    rhat = nan if math.isnan(bulk[2]) or math.isnan(rhat_folded) else max(bulk[2], rhat_folded)
+    ess_tail = nan if math.isnan(e05) or math.isnan(e95) else min(e05, e95)
+    return (float(rhat), float(bulk[3]), float(ess_tail), float(bulk[2]), float(rhat_folded), float(e05), float(e95), float(distinct))
+
+
+class RankStats:
+    """The rank-normalised diagnostics of a run (Vehtari et al. 2021): `values[j]` = (rhat, ess_bulk, ess_tail,
+    rhat_bulk, rhat_folded, ess_q05, ess_q95, distinct) of series names[j] -- the parameters, then acceptance and lp."""
+
+    def __init__(self, names, values, internals=("acceptance", "lp")):
+        self.names = list(names)
+        self.values = np.asarray(values, dtype=np.float64).reshape(len(self.names), len(RANK_COLS))
+        self.internals = list(internals)
+
+    def __getitem__(self, name):
+        return dict(zip(RANK_COLS, (float(v) for v in self.values[self.names.index(name)])))
+
+    def describe(self):
+        """per parameter name {rhat, ess_bulk, ess_tail}: the three columns MCMCChains.summarystats reports"""
+        return {nm: {c: self[nm][c] for c in RANK_COLS[:3]} for nm in self.names if nm not in self.internals}
+
+    def __repr__(self):
+        rows = [f"  {nm:>12s}  rhat {v[0]:.4f}  ess_bulk {v[1]:.1f}  ess_tail {v[2]:.1f}" for nm, v in zip(self.names, self.values)]
+        return "RankStats(\n" + "\n".join(rows) + "\n)"
 
 
 # ---- PSIS-LOO (DESIGN.md section 5.9; demc_loo on the device) ------------------------------------------------------------------

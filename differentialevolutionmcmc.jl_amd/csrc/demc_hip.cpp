@@ -21,6 +21,7 @@
 #include "../../include/demc_pointwise.h"  // demc_pointwise_loglik, demc_waic
 #include "../../include/demc_loo.h"  // demc_loo
 #include "../../include/demc_bridge.h"  // demc_bridge
+#include "../../include/demc_rank.h"  // demc_rankstats, demc_rank_series
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -57,6 +58,7 @@
 #include "demc_pointwise.hpp"  // demc_pointwise_loglik, demc_waic: likewise, demc_pointwise.cpp
 #include "demc_loo.hpp"  // demc_loo: likewise, demc_loo.cpp (with its host-only plan, demc_looplan.hpp)
 #include "demc_bridge.hpp"  // demc_bridge: likewise, demc_bridge.cpp (with its host-only plan, demc_bridgeplan.hpp)
+#include "demc_rank.hpp"  // demc_rankstats, demc_rank_series: likewise, demc_rank.cpp (with its host-only plan, demc_rankplan.hpp)
 #include "demc_devmem.hpp"  // owners of the device memory, pinned memory, events and modules the handle holds
 #include "demc_prep.hpp"  // host-only: a model's data and constants, the prior table and its run-length forms, every refusal of those
 #include "demc_instances.hpp"  // one table per templated kernel, built from the lists above: every choice of an instance goes through them
@@ -1406,6 +1408,10 @@ static HistView hist_view(const demc_handle* h, int64_t row0, int64_t row1) {
 }
 // the one place the covariance is planned: demc_covariance over the history, demc_bridge over the fit half of its xi buffer
 static CovPlan cov_plan(long long N, int D, const int32_t* cols, int n_cols) { return plan_cov(N, D, cols, n_cols); }
+// ... and the one place a summary is planned: demc_summarize over the history, the two rank calls over their derived history
+static SummaryPlan sum_plan(long long n, long long P, int D, int max_lag, long long rho_len, bool wants_rho) {
+    return plan_summary(n, P, D, max_lag, rho_len, wants_rho);
+}
 static Refusal check_window(const demc_handle* h, PostCall call, int64_t row0, int64_t row1, Refusal args = Refusal()) {
     return check_history_window(call, h->hist != nullptr, row0, row1, h->c.n_rows, h->c.n_groups_total != h->c.n_groups, std::move(args));
 }
@@ -1416,7 +1422,7 @@ int32_t demc_summarize(demc_handle* h, int64_t row0, int64_t row1, int32_t max_l
     USE_DEVICE(h);
     if (Refusal r = check_window(h, POST_SUMMARIZE, row0, row1)) return fail(h, r);
     if (!(rho_out && rho_len > 0)) rho_out = nullptr;
-    const SummaryPlan plan = plan_summary(row1 - row0, h->P, h->c.D, (int)max_lag, (long long)rho_len, rho_out != nullptr);
+    const SummaryPlan plan = sum_plan(row1 - row0, h->P, h->c.D, (int)max_lag, (long long)rho_len, rho_out != nullptr);
     if (plan.refused) return fail(h, plan.refused);
     std::string msg;
     const int rc = summary_run(hist_view(h, row0, row1), plan, h->stream, out, rho_out, (long long)rho_len, msg);
@@ -1509,6 +1515,39 @@ int32_t demc_loo(demc_handle* h, int64_t row0, int64_t row1, double* total_out, 
     std::string msg;
     const int rc = loo_run(mv, hist_view(h, row0, row1), plan, h->stream, total_out, pointwise_out, msg);
     return rc == DEMC_OK ? DEMC_OK : fail(h, rc, msg);
+    });
+}
+
+// The rank diagnostics (include/demc_rank.h): every refusal and the plan are demc_rankplan.hpp's, the run is demc_rank.cpp's.  The
+// derived history of a batch holds four series per series ranked; its summary is planned here, for a whole batch and for the last.
+static int32_t rank_call(demc_handle* h, int64_t row0, int64_t row1, int32_t max_lag, bool single, int series, int kind, double* out) {
+    if (Refusal r = check_rank_window(h->hist != nullptr, row0, row1, h->c.n_rows, h->c.n_groups_total != h->c.n_groups, h->P,
+                                      rank_args(out != nullptr, (int)max_lag, single, series, kind, h->c.D)))
+        return fail(h, r);
+    const RankPlan plan = plan_rank(row1 - row0, h->P, single ? 1 : h->c.D + 2);
+    if (plan.refused) return fail(h, plan.refused);
+    const SummaryPlan full = sum_plan(plan.n, plan.P, kRankDerived * plan.batch, (int)max_lag, 0, false);
+    const SummaryPlan last = sum_plan(plan.n, plan.P, kRankDerived * plan.last_batch, (int)max_lag, 0, false);
+    if (full.refused) return fail(h, full.refused);
+    if (last.refused) return fail(h, last.refused);
+    std::string msg;
+    const int rc = rank_run(hist_view(h, row0, row1), plan, full, last, single ? series : -1, kind, h->stream, out, msg);
+    return rc == DEMC_OK ? DEMC_OK : fail(h, rc, msg);
+}
+
+int32_t demc_rankstats(demc_handle* h, int64_t row0, int64_t row1, int32_t max_lag, double* out) {
+    return guarded(h, [&]() -> int32_t {
+    if (!h) return DEMC_EINVAL;
+    USE_DEVICE(h);
+    return rank_call(h, row0, row1, max_lag, false, -1, -1, out);
+    });
+}
+
+int32_t demc_rank_series(demc_handle* h, int64_t row0, int64_t row1, int32_t series, int32_t kind, double* out) {
+    return guarded(h, [&]() -> int32_t {
+    if (!h) return DEMC_EINVAL;
+    USE_DEVICE(h);
+    return rank_call(h, row0, row1, 0, true, (int)series, (int)kind, out);
     });
 }
 

@@ -40,22 +40,20 @@ int launch_all(SumKParams& p, const SummaryPlan& plan, hipStream_t st, std::stri
 
 }  // namespace
 
-int summary_run(const HistView& v, const SummaryPlan& plan, hipStream_t st, double* out, double* rho_out, long long rho_len, std::string& err) {
-    const char* who = "demc_summarize";
-    SumKParams p{};
+int summary_enqueue(const char* who, const HistView& v, const SummaryPlan& plan, hipStream_t st, Scratch& s, SumKParams& p, std::string& err) {
+    p = SumKParams{};
     p.hist = v.hist; p.acc = v.acc; p.lp = v.lp; p.idh = v.idh;
     p.P = v.P; p.row0 = v.row0; p.n = v.row1 - v.row0; p.h = plan.h; p.id0 = v.id0;
     p.D = v.D; p.ld = v.ld; p.JT = plan.JT; p.L = plan.L; p.rho_cols = plan.rho_cols;
     const int D2 = v.D + 2;
 
-    Scratch s;
     double* small = nullptr;  // mean | bh | W | vplus | p_prev | p_sum | out[6]: one allocation, one fill
     int* flags = nullptr;     // K | stopped
     bool ok = s.get(&p.inv, plan.n_inv) && s.get(&p.mu, plan.n_mu) && s.get(&p.part_sum, plan.n_part) && s.get(&p.part_ss, plan.n_part) &&
               s.get(&p.part_g, plan.n_part_g) && s.get(&small, plan.n_small) && s.get(&flags, plan.n_flags);
     if (ok && !plan.lds) ok = s.get(&p.xg, plan.n_xg);
     if (ok && plan.rho_cols > 0) ok = s.get(&p.rho, plan.n_rho);
-    if (!ok) { err = "demc_summarize: out of device memory for the scratch buffers"; return DEMC_ENOMEM; }
+    if (!ok) { err = std::string(who) + ": out of device memory for the scratch buffers"; return DEMC_ENOMEM; }
     p.mean = small; p.bh = small + D2; p.W = small + 2 * D2; p.vplus = small + 3 * D2; p.p_prev = small + 4 * D2;
     p.p_sum = small + 5 * D2; p.out = small + 6 * D2;
     p.K = flags; p.stopped = flags + D2;
@@ -64,7 +62,15 @@ int summary_run(const HistView& v, const SummaryPlan& plan, hipStream_t st, doub
     if (e == hipSuccess) e = hipMemsetAsync(flags, 0, plan.n_flags * sizeof(int), st);
     if (e == hipSuccess && p.rho) e = hipMemsetAsync(p.rho, 0xFF, plan.n_rho * sizeof(double), st);  // all ones: a NaN
     if (!hip_ok(who, e, err)) return DEMC_EHIP;
-    const int rc = plan.lds ? launch_all<true>(p, plan, st, err) : launch_all<false>(p, plan, st, err);
+    return plan.lds ? launch_all<true>(p, plan, st, err) : launch_all<false>(p, plan, st, err);
+}
+
+int summary_run(const HistView& v, const SummaryPlan& plan, hipStream_t st, double* out, double* rho_out, long long rho_len, std::string& err) {
+    const char* who = "demc_summarize";
+    const int D2 = v.D + 2;
+    Scratch s;
+    SumKParams p;
+    const int rc = summary_enqueue(who, v, plan, st, s, p, err);
     if (rc != DEMC_OK) return rc;
     std::vector<double> rho_host(p.rho ? plan.n_rho : 0);
     if (!finish(who, st, {{out, p.out, (size_t)D2 * 6 * sizeof(double)}, {p.rho ? rho_host.data() : nullptr, p.rho, plan.n_rho * sizeof(double)}}, err))

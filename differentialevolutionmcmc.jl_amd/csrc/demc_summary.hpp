@@ -62,6 +62,10 @@ struct SumKParams {
 
 // host: what plan_summary planned for the rows of `v`, on `stream`; 0 or a DEMC_* code with a message
 int summary_run(const HistView& v, const SummaryPlan& plan, hipStream_t stream, double* out, double* rho_out, long long rho_len, std::string& err);
+// host: the launches of summary_run without its end, for a caller that reads the table on the device (demc_rankstats): on return
+// `p` names the buffers, p.out the table [D+2][6]; they live in `s`, and nothing has been waited for.  `who` names the call in `err`.
+struct Scratch;
+int summary_enqueue(const char* who, const HistView& v, const SummaryPlan& plan, hipStream_t stream, Scratch& s, SumKParams& p, std::string& err);
 
 #ifdef DEMC_SUMMARY_KERNELS  // (demc_summary.cpp only: the runtime's unit sees the declarations above and no device code)
 // ---- one pass over id_hist: inv[i][id - id0] = slot

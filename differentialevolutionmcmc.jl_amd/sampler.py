@@ -3,7 +3,7 @@ C-ABI engine.  The per-iteration work -- step!/pstep! (main.jl:84-107) -- happen
 import numpy as np
 
 from . import _ffi
-from .chains import COV_MAX_COLS, Bridge, Chains, Loo, Summary, Waic, series_cov, series_quantiles
+from .chains import COV_MAX_COLS, Bridge, Chains, Loo, RankStats, Summary, Waic, series_cov, series_quantiles
 from .families import PRIOR_NORMAL_REF, Priors, SimulatedLikelihood, SourceLikelihood
 from .structs import (DE, HIPBackend, LOGLIKE_MODES, MCMCThreads, SCHEDULES, DEModel, Particle, maximize)
 
@@ -201,6 +201,7 @@ def _run(model, de, n_iter, backend, progress, engine_factory, summary=None):
     want_waic = summary is not None and len(summary) > 5 and summary[5]
     want_loo = summary is not None and len(summary) > 6 and summary[6]
     want_bridge = summary is not None and len(summary) > 7 and summary[7]
+    want_rank = summary is not None and len(summary) > 8 and summary[8]
     try:
         if want_bridge and not hasattr(eng, "bridge"):  # (no host form: the host route is what the call exists to avoid)
             raise _ffi.DemcError(_ffi.EUNSUPPORTED, "summarize(..., bridge=True) needs an engine with bridge(row0, row1, n_prop, seed) (demc_bridge)")
@@ -248,7 +249,9 @@ def _run(model, de, n_iter, backend, progress, engine_factory, summary=None):
         if want_bridge:  # the marginal likelihood from the same kept rows (demc_bridge)
             opts = dict(want_bridge) if isinstance(want_bridge, dict) else {}
             lay["bridge"] = Bridge(eng.bridge(summary[0], summary[1], int(opts.get("n_prop", 0)), int(opts.get("seed", 0))))
-        if (summary is not None and hasattr(eng, "summarize") and (len(summary) < 4 or summary[3] is None or hasattr(eng, "quantiles"))
+        if want_rank and hasattr(eng, "rankstats"):  # ess_bulk / ess_tail / rank-normalised rhat of the same kept rows (demc_rankstats)
+            lay["rank"] = eng.rankstats(summary[0], summary[1], summary[2])
+        if (summary is not None and (not want_rank or "rank" in lay) and hasattr(eng, "summarize") and (len(summary) < 4 or summary[3] is None or hasattr(eng, "quantiles"))
                 and (cov_cols is None or hasattr(eng, "covariance"))):
             # summarize(): the statistics (and the quantiles and the covariance, when asked for) on the device, no export at all
             stats = eng.summarize(summary[0], summary[1], summary[2])[0]
@@ -285,8 +288,8 @@ def _cov_cols(names, cor):
     return sel, [names.index(nm) for nm in sel]
 
 
-def summarize(model, de, *args, max_lag=0, quantiles=None, cor=False, waic=False, loo=False, bridge=False, progress=False, engine_factory=None, **kwargs):
-    """summarize(model, de, [HIPBackend(...)], n_iter, max_lag=0, quantiles=None, cor=False, waic=False, loo=False, bridge=False): the run of sample() followed by the summary
+def summarize(model, de, *args, max_lag=0, quantiles=None, cor=False, waic=False, loo=False, bridge=False, rank=False, progress=False, engine_factory=None, **kwargs):
+    """summarize(model, de, [HIPBackend(...)], n_iter, max_lag=0, quantiles=None, cor=False, waic=False, loo=False, bridge=False, rank=False): the run of sample() followed by the summary
     statistics of the rows bundle_samples keeps (offset = burnin or 0, quirk q1 included) -- computed on the device by
     demc_summarize, so that the history is never exported.  Returns a Summary (chains.py); equal to
     sample(...).summarystats(max_lag) for the same seed.  quantiles: a tuple of probs (chains.DEFAULT_QUANTILES) -- the same run
@@ -302,7 +305,10 @@ def summarize(model, de, *args, max_lag=0, quantiles=None, cor=False, waic=False
     the call cannot serve is refused before the first step, as for waic.  bridge: True or dict(n_prop=, seed=) -- the same run also forms
     the log marginal likelihood over the kept rows on the device by bridge sampling (demc_bridge) and Summary.bridge holds
     the Bridge record (what compare_bridge reads); its rho, the factor se() scales the posterior term by, is taken as kept draws / ESS of lp
-    from the same table -- a stated approximation, not a spectral estimate."""
+    from the same table -- a stated approximation, not a spectral estimate.  rank: True -- the same run also ranks the pooled kept rows
+    of every series on the device (demc_rankstats) and Summary.rank holds the RankStats record: ess_bulk, ess_tail and
+    the rank-normalised rhat, equal to sample(...).rankstats(max_lag); an engine without rankstats (an injected one) exports as sample()
+    does and ranks on the host.  With rank=False the call is what it was."""
     backend, n_iter = _parse(args)
     Ns = n_iter - de.burnin if de.discard_burnin else n_iter
     offset = de.burnin if de.discard_burnin else 0
@@ -311,8 +317,10 @@ def summarize(model, de, *args, max_lag=0, quantiles=None, cor=False, waic=False
     if isinstance(bridge, dict) and set(bridge) - {"n_prop", "seed"}:
         raise ValueError("bridge= takes True or dict(n_prop=, seed=)")
     lay, res, state = _run(model, de, n_iter, backend, progress, engine_factory,
-                           summary=(offset, offset + Ns, max_lag, probs, want_cov, waic, loo, True if bridge is True else (dict(bridge) if isinstance(bridge, dict) else bridge)))
-    out = _summary_of(model, de, lay, res, state, n_iter, max_lag, probs, want_cov)
+                           summary=(offset, offset + Ns, max_lag, probs, want_cov, waic, loo, True if bridge is True else (dict(bridge) if isinstance(bridge, dict) else bridge), bool(rank)))
+    out = _summary_of(model, de, lay, res, state, n_iter, max_lag, probs, want_cov, want_rank=bool(rank) and "rank" not in lay)
+    if "rank" in lay:
+        out.rank = RankStats(out.names, lay["rank"])
     out.waic = lay.get("waic")
     out.loo = lay.get("loo")
     out.bridge = lay.get("bridge")
@@ -323,7 +331,7 @@ def summarize(model, de, *args, max_lag=0, quantiles=None, cor=False, waic=False
     return out
 
 
-def _summary_of(model, de, lay, res, state, n_iter, max_lag, probs, want_cov):
+def _summary_of(model, de, lay, res, state, n_iter, max_lag, probs, want_cov, want_rank=False):
     if state is None:
         names = get_names(model, lay["shapes"])
         if want_cov is not None:
@@ -334,6 +342,8 @@ def _summary_of(model, de, lay, res, state, n_iter, max_lag, probs, want_cov):
         return Summary(names, res[0], quantiles=res[1], probs=probs)
     chains = bundle_samples(model, de, lay, res, n_iter)
     out = chains.summarystats(max_lag)
+    if want_rank:  # (an engine without rankstats: the definition on the host, from the exported rows)
+        out.rank = chains.rankstats(max_lag)
     if probs is not None:
         out.probs = probs
         out.quantiles = np.stack([series_quantiles(chains.value[:, j, :], probs) for j in range(len(chains.names))])

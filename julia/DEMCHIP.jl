@@ -286,6 +286,8 @@ include("DEMCHIPPointwise.jl")
 include("DEMCHIPLoo.jl")
 # ... and the marginal likelihood by bridge sampling (the header beside it): `bridge`, `compare_bridge`, likewise
 include("DEMCHIPBridge.jl")
+# ... and the rank-normalised diagnostics ess_bulk / ess_tail / rhat (the header beside it): `rankstats`, `rank_series`, likewise
+include("DEMCHIPRank.jl")
 
 "final state of the particle objects behind handle `h` (bundle_samples reads accept/lp from them; Θ for completeness)"
 function pull_state!(h, particles, Pl, D, shapes, lens, offs)

@@ -9,7 +9,7 @@ The run of `sample`, followed by `describe(chains)` computed on the device (demc
 the history: rows `offset+1 : offset+Ns` of `bundle_samples` (src/main.jl:222-231, offset = burnin or 0).  Returns
 `(names, table)` with `table[j, :] = (mean, std, rhat, ess, mcse, pairs)` of series `names[j]` -- the names of `get_names`:
 the parameters, then acceptance and lp.  ess is the split-chain form without rank normalisation and without Stan's antithetic tail term:
-MCMCChains' `ess_rhat` differs from it by those two steps.
+MCMCChains' `ess_rhat` differs from it by those two steps; `rankstats` (DEMCHIPRank.jl) gives the rank-normalised columns.
 """
 function summarize(model::DEModel, de::DE, b::HIPBackend, n_iter::Int; model_spec::AnyModelSpec, max_lag::Int = 0, kwargs...)
     groups = sample_init(model, de, n_iter)
