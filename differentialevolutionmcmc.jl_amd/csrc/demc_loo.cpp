@@ -123,7 +123,7 @@ __global__ __launch_bounds__(kLooWG) void k_loo_column(PwKParams p, const double
     flags = (int)loo_reduce(L.redk, (u64)flags, [](u64 a, u64 b) { return a | b; });
     const double Mall = loo_max(L, Mx);
     const double Eall = loo_sum(L, E != 0.0 ? E * exp(Mx - Mall) : 0.0);
-    const double lppd = Mall + log(Eall) - log((double)S);
+    const double lppd = Mall + (log(Eall) - log((double)S));  // (a constant column: Eall == S, lppd is the term itself and p_loo is 0)
     double* out = p.point + (size_t)(p.order ? p.order[obs0 + blockIdx.x] : obs0 + blockIdx.x) * DEMC_LOO_NPOINT;
     if (flags) {
         if (t == 0) {

@@ -192,3 +192,202 @@ def check_table(pt, ref, label, exact_tail=True):
             err = np.abs(pt[f, c] - ref[f, c]) / np.maximum(1.0, np.abs(ref[f, c]))
         worst[name] = float(err.max()) / BAR if err.size else 0.0
     return worst
+
+
+# ---- the path of the select in k_loo_column, restated ---------------------------------------------------------------------------
+# Used only to prove that a test's input reaches the branch it is there for (as geometry() is in the rank tests); never a reference
+# for a result.
+LOO_BITS, LOO_DIGITS = 11, 6
+_ALL, _SIGN = np.uint64(0xFFFFFFFFFFFFFFFF), np.uint64(1 << 63)
+
+
+def keys_of(col):
+    """the integer keys of section 5.6, as uint64"""
+    b = np.ascontiguousarray(col, dtype=np.float64).view(np.uint64)
+    return b ^ np.where(b >> np.uint64(63) != 0, _ALL, _SIGN)
+
+
+def _digit(d):
+    """digit d is bits [dsh, top): 11 bits each, the last one the nine bits [0, 9)"""
+    return (64 - LOO_BITS * (d + 1) if d < LOO_DIGITS - 1 else 0), 64 - LOO_BITS * d
+
+
+def select_path(col, M):
+    """step (2) of k_loo_column as the kernel text walks it -> dict(early, stop_digit (None: unresolved), counted, skipped (digits
+    counted and skipped up to the stop), nc (the keys step (3) compacts))"""
+    k = keys_of(col)
+    kmin, kmax = int(k.min()), int(k.max())
+    prefix, rank, below = 0, int(M), 0
+    counted = skipped = 0
+    for d in range(LOO_DIGITS):
+        dsh, top = _digit(d)
+        if kmin >> dsh == kmax >> dsh:
+            prefix = (kmin >> dsh) << dsh
+            skipped += 1
+            continue
+        counted += 1
+        mask = (1 << (top - dsh)) - 1
+        sel = k if d == 0 else k[(k >> np.uint64(top)) == np.uint64(prefix >> top)]
+        hist = np.bincount(((sel >> np.uint64(dsh)) & np.uint64(mask)).astype(np.int64), minlength=1 << LOO_BITS)
+        part = hist.reshape(256, 8).sum(axis=1)
+        acc, g = 0, 0
+        while g < 255 and rank >= acc + part[g]:  # eight bins at a time, then bin by bin
+            acc += int(part[g])
+            g += 1
+        b = 8 * g
+        while b < 8 * g + 7 and rank >= acc + hist[b]:
+            acc += int(hist[b])
+            b += 1
+        cnt = int(hist[b])
+        below += acc
+        rank -= acc
+        prefix |= b << dsh
+        if below + cnt <= LOO_CAP:
+            return dict(early=True, stop_digit=d, counted=counted, skipped=skipped, nc=below + cnt)
+    return dict(early=False, stop_digit=None, counted=counted, skipped=skipped, nc=below)  # lim = key_c - 1: the keys below the cutoff
+
+
+def select_path_direct(col, M):
+    """the same answer without a walk: k_M is the (M + 1)-th smallest key; the stop is the first digit on which the keys differ whose
+    bins up to k_M's hold at most 8192 keys"""
+    k = keys_of(col)
+    kM = np.sort(k)[M]
+    lo, hi = k.min(), k.max()
+    counted = skipped = 0
+    for d in range(LOO_DIGITS):
+        dsh = np.uint64(_digit(d)[0])
+        if lo >> dsh == hi >> dsh:
+            skipped += 1
+            continue
+        counted += 1
+        n = int(((k >> dsh) <= (kM >> dsh)).sum())
+        if n <= LOO_CAP:
+            return dict(early=True, stop_digit=d, counted=counted, skipped=skipped, nc=n)
+    return dict(early=False, stop_digit=None, counted=counted, skipped=skipped, nc=int((k < kM).sum()))
+
+
+def select_paths(ll):
+    """select_path of every column of ll[S][N], checked on the way against the closed form and against what each outcome means"""
+    S, N = ll.shape
+    M = plan(N, S)["M"]
+    assert M > 0
+    out = []
+    for i in range(N):
+        col = np.ascontiguousarray(ll[:, i])
+        p, q = select_path(col, M), select_path_direct(col, M)
+        assert p == q, (i, p, q)
+        k = keys_of(col)
+        n_le = int((k <= np.sort(k)[M]).sum())
+        if p["early"]:
+            assert M < p["nc"] <= LOO_CAP, (i, p)
+        elif p["counted"]:
+            assert p["nc"] <= M and n_le > LOO_CAP, (i, p, n_le)
+        else:  # no digit differs: a constant column, whatever its length (the keys up to the cutoff are all of them)
+            assert p["nc"] == 0 and n_le == S and p["skipped"] == LOO_DIGITS, (i, p, n_le)
+        out.append(p)
+    return out
+
+
+def reach(paths):
+    """how many columns stop at each digit ('u': unresolved) -> dict"""
+    out = {}
+    for p in paths:
+        key = p["stop_digit"] if p["early"] else "u"
+        out[key] = out.get(key, 0) + 1
+    return out
+
+
+# ---- column families with ties, crowds and narrow ranges --------------------------------------------------------------------------
+# Gaussian (D = 2), N = 65.  Ties are repeated draws -- equal theta gives equal terms bit for bit in every column -- and the repeats
+# sit at random cells of the window.
+N_FAMILY = 65
+CROWD_K = (12, 24, 34, 45, 51, 52)  # (52: the crowd's terms tie in more columns than at 51 -- a second, wider reach of the unresolved branch)
+CROWD_SEED = {51: 9907, 52: 9906}  # seeds at which the DEVICE's terms of the three draws tie (all 9000 equal) in at least four columns
+
+
+def family_data(rng, N=N_FAMILY):
+    y = rng.normal(0.3, 1.2, N)
+    y[0] = 50.0  # beside ordinary points: the floor is active in this column
+    return y
+
+
+def tied_draws(rng, distinct, repeated):
+    """distinct[n][2] and the draws of repeated = [((mu, sigma), copies), ...], shuffled over the window"""
+    th = np.concatenate([np.asarray(distinct, dtype=np.float64).reshape(-1, 2)] + [np.tile(np.array(t, dtype=np.float64), (c, 1)) for t, c in repeated])
+    return th[rng.permutation(th.shape[0])]
+
+
+def crowd(k, S=9216, copies=3000, seed=None):
+    """three draws 2^-k apart in sigma, `copies` times each, beside S - 3 copies well-spread draws (fewer than M): the cutoff falls
+    in the crowd, and the crowd's terms part only at a digit that deepens with k"""
+    rng = np.random.default_rng((CROWD_SEED.get(k, 9900) if seed is None else seed) + k)
+    y = family_data(rng)
+    rep = [((0.55, 0.8 * (1.0 + j * 2.0 ** -k)), copies) for j in range(3)]
+    return y, tied_draws(rng, gaussian_draws(rng, S - 3 * copies), rep)
+
+
+def one_draw(S=9216, copies=8500, at=(0.55, 0.8), seed=9910):
+    """one draw `copies` times: more than 8192 equal keys, which no bin can separate"""
+    rng = np.random.default_rng(seed)
+    y = family_data(rng)
+    return y, tied_draws(rng, gaussian_draws(rng, S - copies), [(at, copies)])
+
+
+def four_times(S=2000, seed=9920):
+    """every draw four times: the cutoff falls inside a run"""
+    rng = np.random.default_rng(seed)
+    y = family_data(rng)
+    d = gaussian_draws(rng, S // 4)
+    return y, tied_draws(rng, np.empty((0, 2)), [(tuple(t), 4) for t in d])
+
+
+def two_values(seed=9930):
+    """S = 130: one draw 100 times, another 30 times -- either way the M + 1 = 27 smallest terms tie, the cutoff is the minimum"""
+    rng = np.random.default_rng(seed)
+    y = family_data(rng)
+    return y, tied_draws(rng, np.empty((0, 2)), [((0.25, 1.1), 100), ((0.4, 0.9), 30)])
+
+
+def constant(S, seed=9940):
+    rng = np.random.default_rng(seed)
+    return family_data(rng), np.tile(np.array([0.25, 1.1]), (S, 1))
+
+
+def mixed_sign(S=9216, seed=9950):
+    """narrow sigma about 0.3: the term of a point 0.226 from mu changes sign across the draws"""
+    rng = np.random.default_rng(seed)
+    h = N_FAMILY // 2
+    y = np.concatenate([0.3 + rng.choice([-0.226, 0.226], h) + rng.normal(0.0, 0.02, h), rng.normal(0.3, 0.3, N_FAMILY - h)])
+    th = np.stack([rng.normal(0.3, 0.1, S), np.maximum(rng.normal(0.3, 0.03, S), 0.1)], axis=1)
+    return y, th
+
+
+def narrow(S=2000, jitter=1e-12, seed=9960):
+    """draws 1e-12 apart: every key of a column shares its leading two or three digits.  (At 1e-13 the quartile excess of some
+    columns falls to 3e-13, under the 2^-40 the tests ask of it; at 1e-12 the smallest is 3e-12.)"""
+    rng = np.random.default_rng(seed)
+    y = family_data(rng)
+    i, j = rng.integers(0, 1000, S), rng.integers(0, 1000, S)
+    return y, np.stack([0.3 * (1.0 + jitter * i), 1.0 + jitter * j], axis=1)
+
+
+def quartile_excess(ll):
+    """e_q of the definition for every column of ll[S][N] in FP64 (NaN where no fit is tried)"""
+    S, N = ll.shape
+    M = tail_len(S)
+    out = np.full(N, np.nan)
+    for i in range(N):
+        ls = np.sort(ll[:, i])
+        x = ls[0] - ls
+        x_cut = max(ls[0] - ls[M], LOG_MIN)
+        xt = x[x > x_cut][::-1]
+        if xt.size > 4:
+            out[i] = (np.exp(xt) - np.exp(x_cut))[int(math.floor(xt.size / 4.0 + 0.5)) - 1]
+    return out
+
+
+HOST_FAMILIES = {  # name -> (y, theta): what tests/test_loo_host.py walks with gaussian_terms, and tests/test_gpu_loo.py on the device
+    **{f"crowd k={k}": (lambda k=k: crowd(k)) for k in CROWD_K},
+    "one draw 8500 times": one_draw, "every draw four times": four_times, "two values": two_values,
+    "constant S=130": lambda: constant(130), "constant S=26": lambda: constant(26), "mixed sign": mixed_sign, "narrow": narrow,
+}

@@ -349,3 +349,78 @@ def test_loo_kernels_use_no_scratch(tmp_path, demc):
     assert sum("k_loo_terms" in k[0] for k in ks) == 14
     for name, regs, _, wg, scratch in ks:
         assert scratch == 0 and regs <= 512 // -(-wg // 256), (name, regs, wg, scratch)
+
+
+# ---- the select's path restated, and the twin on tied, crowded and constant columns ----------------------------------------------------
+@pytest.mark.parametrize("name", list(LC.HOST_FAMILIES))
+def test_select_path_restatements_agree(name):
+    """select_path (the kernel's walk) against select_path_direct (the closed form) on every column family, with what each outcome
+    means: early -> M < nc <= 8192; unresolved after a counted digit -> nc <= M and more than 8192 keys up to the cutoff; no digit
+    counted at all -> a constant column (LC.select_paths asserts all three)"""
+    y, th = LC.HOST_FAMILIES[name]()
+    assert y.shape == (LC.N_FAMILY,) and th.shape[1] == 2
+    paths = LC.select_paths(LC.gaussian_terms(y, th))
+    print(name, "S =", th.shape[0], "stop digits:", LC.reach(paths), "nc > 4096:", sum(p["nc"] > 4096 for p in paths),
+          "nc == 0:", sum(p["nc"] == 0 for p in paths), "skipped:", sorted({p["skipped"] for p in paths}))
+
+
+def test_select_path_on_hand_made_keys():
+    """the two forms on columns whose path is known by construction"""
+    M = LC.tail_len(9216)
+    col = np.full(9216, -1.0)
+    col[:100] = -np.linspace(2.0, 3.0, 100)  # 100 < M distinct terms under 9116 equal ones: unresolved, the 100 compacted
+    for f in (LC.select_path, LC.select_path_direct):
+        p = f(col, M)
+        assert not p["early"] and p["nc"] == 100 and p["stop_digit"] is None, p
+    col[:100] = np.nextafter(-1.0, -2.0)  # one ulp under the crowd: only the nine-bit last digit differs
+    for f in (LC.select_path, LC.select_path_direct):
+        assert f(col, M) == dict(early=False, stop_digit=None, counted=1, skipped=5, nc=100)
+    col[:1000] = np.nextafter(-1.0, -2.0)  # the cutoff now lies among the 1000: they fit, stop at the last digit
+    for f in (LC.select_path, LC.select_path_direct):
+        assert f(col, M) == dict(early=True, stop_digit=5, counted=1, skipped=5, nc=1000)
+    col = np.concatenate([np.linspace(-3.0, -2.0, 5000), np.linspace(0.5, 1.0, 4216)])  # both signs: the first digit separates them
+    for f in (LC.select_path, LC.select_path_direct):
+        assert f(col, M) == dict(early=True, stop_digit=0, counted=1, skipped=0, nc=5000)
+
+
+SMALL_TIES = {  # scaled-down copies: the twin has no 8192-key cap, so the proportions matter and the sizes do not
+    "crowd k=12": lambda: LC.crowd(12, S=520, copies=160), "crowd k=51": lambda: LC.crowd(51, S=520, copies=160),
+    "one draw 850 of 1000": lambda: LC.one_draw(S=1000, copies=850), "every draw four times": lambda: LC.four_times(S=520),
+    "two values": LC.two_values, "constant S=130": lambda: LC.constant(130), "constant S=26": lambda: LC.constant(26),
+}
+SMALL_COLS = [0, 1, 2, 3, 4, 5]  # y = 50 first
+
+
+@pytest.mark.parametrize("name", list(SMALL_TIES))
+def test_numpy_twin_on_ties_against_the_definition_at_40_digits(demc, name):
+    y, th = SMALL_TIES[name]()
+    S = th.shape[0]
+    assert S <= 2000
+    ll = LC.gaussian_terms(y[SMALL_COLS], th)
+    got = demc.loo_from_loglik(ll).pointwise
+    ref = LC.ref_table(ll)
+    worst = LC.check_table(got, ref, name)  # n_tail and l_cut exactly
+    print(name, "S =", S, "worst error in units of 1e-9 max(1, |ref|):", worst, "n_tail:", ref[:, 4].astype(int).tolist())
+    assert all(v <= 1.0 for v in worst.values()), worst
+    M = LC.tail_len(S)
+    assert len(np.unique(th, axis=0)) < S, "no repeated draw"
+    if name.startswith("crowd"):
+        assert S - 3 * 160 < M and (ref[:, 4] < M).all()  # the cutoff falls in the crowd
+    elif name.startswith("one draw"):
+        assert S - 850 > M and (ref[:, 4] < M).any() and (ref[:, 4] == M).any()  # ... in some columns, among the distinct draws in others
+    elif name.startswith("every draw"):
+        assert M % 4 and (ref[1:, 4] == M - M % 4).all() and ref[0, 4] < M - M % 4  # inside a run; y = 50: the floor besides
+    elif name == "two values":
+        assert (ref[:, 4] == 0).all() and np.isposinf(ref[:, 2]).all() and np.array_equal(ref[:, 5], ll.min(axis=0))
+    else:
+        assert np.array_equal(got[:, 0], ll[0]) and np.array_equal(got[:, 3], ll[0]) and np.array_equal(got[:, 5], ll[0])
+        assert (got[:, 1] == 0).all() and (got[:, 4] == 0).all() and np.isposinf(got[:, 2]).all()
+
+
+def test_narrow_columns_keep_a_fit(demc):
+    """the reference alone: every quartile excess of the narrow family is at least 2^-40, so one ulp of exp cannot switch a fit off"""
+    y, th = LC.narrow()
+    ll = LC.gaussian_terms(y, th)
+    eq = LC.quartile_excess(ll)
+    assert np.isfinite(eq).all() and eq.min() >= 2.0 ** -40, eq.min()
+    assert np.isfinite(demc.loo_from_loglik(ll).pointwise[:, 2]).all()
