@@ -775,10 +775,12 @@ def bridge_draws(m, L, n, seed, lo=None, hi=None):
     return theta, lj, -0.5 * (z * z).sum(axis=1) - (np.log(np.diag(L)).sum() + 0.5 * D * math.log(2.0 * math.pi))
 
 
-def bridge_from_logs(l1, l2, n_fit=float("nan"), lp2=None):
+def bridge_from_logs(l1, l2, n_fit=float("nan"), lp2=None, trace=None):
     """DESIGN.md 5.10 from the two log-ratio vectors: l1[N1] over the estimate half, l2[N2] over the proposal draws -> Bridge.  The sums
     run in np.longdouble and are rounded to float64; r, the terms and the test of convergence are float64 as on the device.  lp2 (the
-    log posterior of the proposal draws) only feeds the count n_zero_prop; without it the -Inf among l2 are counted."""
+    log posterior of the proposal draws) only feeds the count n_zero_prop; without it the -Inf among l2 are counted.  An iterate that
+    is not a positive finite number stops the iteration (counted, not converged, NaN outputs).  trace: a list that receives
+    (r_{t+1}, |r_{t+1} - r_t| / |r_{t+1}|) of every iteration (NaN for the change of an iterate that stops it)."""
     l1, l2 = np.asarray(l1, dtype=np.float64).ravel(), np.asarray(l2, dtype=np.float64).ravel()
     N1, N2 = l1.size, l2.size
     nan, inf = float("nan"), float("inf")
@@ -798,19 +800,24 @@ def bridge_from_logs(l1, l2, n_fit=float("nan"), lp2=None):
         while n_iter < BRIDGE_MAX_ITER:
             rn = mean(f1_of(r)) / mean(1.0 / (s1 * e1 + s2 * r))
             n_iter += 1
+            if not (math.isfinite(rn) and rn > 0.0):  # 0 by underflow, +Inf, NaN: the iteration stops, counted and not converged
+                if trace is not None:
+                    trace.append((rn, nan))
+                return Bridge([nan, nan, nan, n_iter, 0, n_fit, N1, N2, l_star, n_zero, n_bad, nan])
             change = abs(rn - r)
             rel = change / abs(rn)
             r = rn
+            if trace is not None:
+                trace.append((rn, rel))
             if change <= BRIDGE_TOL * abs(rn):
                 conv = 1
-                break
-            if not (math.isfinite(rn) and rn > 0.0):
                 break
         f1, f2 = f1_of(r), 1.0 / ((s1 * e1) / r + s2)
         m1, m2 = mean(f1), mean(f2)
         ss = lambda f, m: float(((f - m) ** 2).astype(np.longdouble).sum())  # noqa: E731
-        re1 = ss(f1, m1) / (N2 - 1) / (m1 * m1) / N2 if N2 > 1 else nan
-        re2 = ss(f2, m2) / (N1 - 1) / (m2 * m2) / N1 if N1 > 1 else nan
+        # (np.float64 divides as the device does: a mean whose square underflows gives Inf or NaN, not an exception)
+        re1 = float(np.float64(ss(f1, m1)) / (N2 - 1) / np.float64(m1 * m1) / N2) if N2 > 1 else nan
+        re2 = float(np.float64(ss(f2, m2)) / (N1 - 1) / np.float64(m2 * m2) / N1) if N1 > 1 else nan
         return Bridge([math.log(r) + l_star if r > 0 else nan, re1, re2, n_iter, conv, n_fit, N1, N2, l_star, n_zero, n_bad, rel])
 
 

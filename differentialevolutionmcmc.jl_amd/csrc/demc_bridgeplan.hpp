@@ -219,16 +219,19 @@ inline double bridge_lognorm(const double* L, int D) {
 
 // ---- the outputs ----------------------------------------------------------------------------------------------------------------
 
-// out[DEMC_BRIDGE_NOUT] from the device state after the last kernel
+// out[DEMC_BRIDGE_NOUT] from the device state after the last kernel.  An iterate r that is not a positive finite number (0 by
+// underflow, +Inf, NaN) has stopped the iteration: the count includes that iteration, converged is 0 whatever the flag says (the
+// kernel's test |change| <= tol |r| holds at r = +Inf), and logml, the error terms and the last change are NaN, as under n_nonfinite.
 inline void bridge_outputs(const BridgePlan& p, const double* val, const unsigned long long* word, double* out) {
     const double nan = std::numeric_limits<double>::quiet_NaN();
-    const bool bad = word[BW_NONFINITE] > 0 || !std::isfinite(val[BV_LSTAR]);
     const double r = val[BV_R];
+    const bool r_ok = std::isfinite(r) && r > 0.0;
+    const bool bad = word[BW_NONFINITE] > 0 || !std::isfinite(val[BV_LSTAR]) || !r_ok;
     out[0] = bad ? nan : std::log(r) + val[BV_LSTAR];
     out[1] = bad ? nan : val[BV_SS1] / (double)(p.N2 - 1) / (val[BV_MEAN1] * val[BV_MEAN1]) / (double)p.N2;
     out[2] = bad ? nan : val[BV_SS2] / (double)(p.N1 - 1) / (val[BV_MEAN2] * val[BV_MEAN2]) / (double)p.N1;
     out[3] = (double)word[BW_ITER];
-    out[4] = word[BW_FLAG] == BF_CONVERGED ? 1.0 : 0.0;
+    out[4] = word[BW_FLAG] == BF_CONVERGED && r_ok ? 1.0 : 0.0;
     out[5] = (double)p.n_fit;
     out[6] = (double)p.N1;
     out[7] = (double)p.N2;

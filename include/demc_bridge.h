@@ -23,7 +23,9 @@ extern "C" {
  * anew by the handle's own evaluate path (what demc_logpost returns), in chunks of P rows; with
  *   l1_i = lp_i + logJ_i - log g(xi_i) (estimate half),   l2_j likewise (proposal draws),   l* = max_i l1_i,   x = l - l*,
  * r_0 = 1 and r_{t+1} = mean_j[1 / (s1 + s2 r_t exp(-x2_j))] / mean_i[1 / (s1 exp(x1_i) + s2 r_t)], s1 = N1 / (N1 + N2), s2 = 1 - s1,
- * runs until |r_{t+1} - r_t| <= 1e-10 |r_{t+1}| or DEMC_BRIDGE_MAX_ITER iterations; logml = log r + l*.
+ * runs until |r_{t+1} - r_t| <= 1e-10 |r_{t+1}| or DEMC_BRIDGE_MAX_ITER iterations; logml = log r + l*.  An iterate r_{t+1} that is
+ * not finite or not > 0 (0 by underflow where the two densities do not overlap, +Inf, NaN) stops the iteration: n_iter counts that
+ * iteration, converged is 0, and logml, the error terms and the last change are NaN, as under n_nonfinite.
  * out[DEMC_BRIDGE_NOUT]:
  *   0 logml          1 re2_prop = var(f1) / mean(f1)^2 / N2      2 re2_post_iid = var(f2) / mean(f2)^2 / N1
  *     (f1_j = 1 / (s1 + s2 r exp(-x2_j)), f2_i = 1 / (s1 exp(x1_i) / r + s2), the variances with the N - 1 divisor: the approximate

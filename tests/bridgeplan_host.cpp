@@ -6,6 +6,8 @@
 //
 // bridgeplan_host --dump reads one request per line from stdin and prints what the header answers:
 //   T theta lo hi        -> xi logJ theta_back (%.17g; inf / -inf / nan as printf writes them)
+//   G R P D n_prop       -> plan_bridge's geometry for rows [0, R) of P draws: n_fit= N1= N2= W1= W2= chunks1= chunks2= pad2= last2= draw_blocks=
+//                           solve_blocks= lds_bytes=, or refused=<code> message=<text>
 #include "demc_bridgeplan.hpp"
 
 #include <cstdio>
@@ -219,6 +221,21 @@ void outputs() {
     word[BW_NONFINITE] = 1; word[BW_FLAG] = BF_STOPPED; word[BW_ITER] = 0;
     bridge_outputs(p, val, word, out);
     CHECK(std::isnan(out[0]) && std::isnan(out[1]) && std::isnan(out[2]) && std::isnan(out[11]) && out[3] == 0 && out[4] == 0 && out[10] == 1 && out[8] == -10.0);
+    // an iterate that is not a positive finite number: the iteration stopped there and is counted, nothing converged whatever the flag
+    // says (the kernel's test holds at +Inf), logml, the error terms and the last change are NaN, the counts and l* stay
+    const double inf = std::numeric_limits<double>::infinity(), nan = std::numeric_limits<double>::quiet_NaN();
+    for (double r : {0.0, -0.0, inf, nan, -1.0, -inf})
+        for (unsigned long long flag : {(unsigned long long)BF_STOPPED, (unsigned long long)BF_CONVERGED, (unsigned long long)BF_RUNNING}) {
+            word[BW_NONFINITE] = 0; word[BW_FLAG] = flag; word[BW_ITER] = 23; word[BW_ZERO] = 3;
+            val[BV_R] = r; val[BV_REL] = r == 0.0 ? inf : nan;
+            bridge_outputs(p, val, word, out);
+            CHECK(std::isnan(out[0]) && std::isnan(out[1]) && std::isnan(out[2]) && std::isnan(out[11]));
+            CHECK(out[3] == 23 && out[4] == 0 && out[5] == 65 && out[6] == 65 && out[7] == 65 && out[8] == -10.0 && out[9] == 3 && out[10] == 0);
+        }
+    // ... and the smallest positive r is a result like any other
+    word[BW_FLAG] = BF_CONVERGED; val[BV_R] = std::numeric_limits<double>::denorm_min(); val[BV_REL] = 0.0;
+    bridge_outputs(p, val, word, out);
+    CHECK(out[0] == std::log(val[BV_R]) - 10.0 && out[4] == 1 && std::isfinite(out[1]) && std::isfinite(out[2]) && out[11] == 0.0);
 }
 
 int dump() {
@@ -226,7 +243,23 @@ int dump() {
     while (std::getline(std::cin, line)) {
         std::istringstream in(line);
         std::string what, a, b, c;
-        in >> what >> a >> b >> c;
+        in >> what;
+        if (what == "G") {
+            BridgeCall k = good();
+            long long R = 0, P = 0, D = 0, n_prop = 0;
+            in >> R >> P >> D >> n_prop;
+            k.row0 = 0; k.row1 = k.n_rows = R; k.P = P; k.D = (int)D; k.n_prop = n_prop;
+            const BridgePlan g = plan_bridge(k);
+            if (g.refused) { std::printf("refused=%d message=%s\n", g.refused.code, g.refused.message.c_str()); continue; }
+            std::vector<int32_t> cols((size_t)D);  // the fit as the runtime plans it: every scalar of xi
+            for (long long j = 0; j < D; ++j) cols[(size_t)j] = (int32_t)j;
+            const CovPlan f = plan_cov(g.n_fit, (int)D, cols.data(), (int)D);
+            std::printf("n_fit=%lld N1=%lld N2=%lld W1=%d W2=%d chunks1=%lld chunks2=%lld pad2=%lld last2=%lld draw_blocks=%d solve_blocks=%d lds_bytes=%zu "
+                        "cov_chunks=%lld cov_workers=%d\n",
+                        g.n_fit, g.N1, g.N2, g.W1, g.W2, g.chunks1, g.chunks2, g.pad2, g.last2, g.draw_blocks, g.solve_blocks, g.lds_bytes, f.chunks, f.W);
+            continue;
+        }
+        in >> a >> b >> c;
         if (what != "T") { std::printf("?\n"); continue; }
         const double th = std::strtod(a.c_str(), nullptr), lo = std::strtod(b.c_str(), nullptr), hi = std::strtod(c.c_str(), nullptr);
         const double xi = bridge_forward(th, lo, hi);

@@ -146,7 +146,24 @@ def test_edge_rules_exactly(demc):
         got = demc.bridge_from_logs(a, b)
         assert got.n_nonfinite == 2 and math.isnan(got.logml) and math.isnan(got.re2_prop) and math.isnan(got.re2_post_iid) and got.n_iter == 0 and not got.converged
         assert got.l_star == (np.nanmax(a) if bad != INF or vec == 1 else INF)
-    assert math.isnan(demc.bridge_from_logs(np.full(5, -INF), l2).logml)
+    none = demc.bridge_from_logs(np.full(5, -INF), l2)
+    assert math.isnan(none.logml) and none.l_star == -INF and none.n_iter == 0 and not none.converged and none.n_nonfinite == 0 and math.isnan(none.rel_change)
+    # an iterate that is not a positive finite number stops the iteration: counted, not converged, NaN outputs, n_nonfinite 0, and no
+    # exception.  Proposal draws 2000 or 760 log units below l*: every e^(-x2) is +Inf, every term of the numerator is 0, r_1 = 0
+    for drop in (2000.0, 760.0):
+        trace = []
+        got = demc.bridge_from_logs(l1, np.full(30, l1.max() - drop), n_fit=17, trace=trace)
+        assert got.n_iter == 1 and not got.converged and got.n_nonfinite == 0 and got.n_zero_prop == 0 and got.l_star == l1.max() and got.n_fit == 17
+        assert all(math.isnan(v) for v in (got.logml, got.re2_prop, got.re2_post_iid, got.rel_change)) and math.isnan(got.se())
+        assert len(trace) == 1 and trace[0][0] == 0.0 and math.isnan(trace[0][1])
+        assert "NOT converged" in repr(got)
+    # ... and a mean of f1 whose square underflows divides as the device's FP64 does (0 / 0 = NaN), it does not raise either
+    tiny = demc.bridge_from_logs(np.array([0.0, -1.0]), np.array([-700.0, -700.0]))
+    assert math.isfinite(tiny.logml) and math.isnan(tiny.re2_prop) and math.isfinite(tiny.re2_post_iid) and tiny.n_iter == 1000 and not tiny.converged
+    # the record of a converged call carries its trace: the last entry is (r, rel_change)
+    trace = []
+    again = demc.bridge_from_logs(l1, l2, trace=trace)
+    assert again.out.tobytes() == base.out.tobytes() and len(trace) == base.n_iter and trace[-1][1] == base.rel_change and math.log(trace[-1][0]) + base.l_star == base.logml
     one = demc.bridge_from_logs(l1, l2[:1])
     assert math.isnan(one.re2_prop) and math.isfinite(one.logml) and math.isnan(one.se())
     assert base.se(1.0) == math.sqrt(base.re2_prop + base.re2_post_iid) and base.se(4.0) == math.sqrt(base.re2_prop + 4.0 * base.re2_post_iid)
@@ -239,6 +256,48 @@ def test_transform_of_the_header_is_the_twins(demc):
     for (t, lo, hi), (xi, lj, back) in zip(th_all, rows):
         x, j = demc.bridge_transform(np.array([[t]]), [lo], [hi])
         assert _bars([xi, lj], [x[0, 0], j[0]]) <= 1e-3 and abs(back - t) <= 1e-12 * max(1.0, abs(t))  # the same operations: a few ulps of libm
+
+
+def test_geometry_restated_is_the_planners(demc):
+    """bridge_cases.geometry, which every GPU case asserts its path through, against plan_bridge (and plan_cov for the fit) itself"""
+    grid = [(R, P, D, n) for R in (2, 3, 7, 130) for P in (3, 13, 16, 512) for D in (1, 2) for n in (0, 1, 63, 64, 65, 1024, 1025, 2049, 262144, 262145, 1 << 22)]
+    shapes = BC.GPU_SHAPES + grid
+    for shape, plan in zip(shapes, BC.plan_geometry(shapes)):
+        g = BC.geometry(*shape)
+        assert {k: g[k] for k in BC.GEOMETRY_KEYS} == plan, (shape, g, plan)
+    g = BC.geometry(BC.WIN_R, BC.WIN_P, 2, 2049)
+    assert (g["W1"], g["W2"], g["logs_blocks"], g["N2"] - (g["logs_blocks"] - 1) * BC.BRIDGE_WG, g["cov_chunks"], g["solve_blocks"]) == (2, 3, 9, 1, 3, 17)
+    g = BC.geometry(2, BC.CAP_P, 2, BC.CAP_N2)
+    assert (g["W2"], g["W1"], g["chunks2"]) == (256, 1, 513) and BC.geometry(2, BC.CAP_P, 2, BC.CAP_N2 - 1)["W2"] == 256 and BC.geometry(2, BC.CAP_P, 2, BC.CAP_N2 - 1025)["W2"] == 255
+    assert -(-BC.CAP_N2 // (256 * BC.BRIDGE_WG)) == 5 and -(-(BC.CAP_N2 - 1) // (256 * BC.BRIDGE_WG)) == 4  # a thread's fifth element
+    run = subprocess.run([BC.program(), "--dump"], input="G 2 3 3 0\nG 4 3 65 0\n", capture_output=True, text=True, timeout=120)
+    assert run.stdout.splitlines() == [f"refused={demc._ffi.EINVAL} message=demc_bridge: the fit half holds N_fit = 3 draws, the covariance of the proposal needs more than D = 3; pass a wider window",
+                                       f"refused={demc._ffi.EINVAL} message=demc_bridge: D = 65 is above the cap of 64 (DEMC_BRIDGE_MAX_D: the covariance of the proposal)"], run.stdout
+
+
+# ---- the split windows of the iteration, on the twins alone -----------------------------------------------------------------------------
+@pytest.mark.parametrize("name", list(BC.WINDOWS))
+def test_split_windows_meet_their_conditions(demc, orc, name):
+    """each window of the device's iteration tests meets the condition it exists for, on the twins with the oracle's log posterior"""
+    w = BC.WINDOWS[name]
+    prob, rows = BC.split_window(name)
+    o = orc.Oracle(n_groups=1, Np=4, D=prob["D"], n_rows=1)
+    setup_engine(o, prob)
+    trace = []
+    b, l1, l2 = BC.twin_bridge(demc, rows, prob["lo"], prob["hi"], o.logpost, n_prop=w["n_prop"], seed=BC.WINDOW_DRAW_SEED, trace=trace)
+    o.close()
+    print(f"{name}: {b!r}, n_iter {int(b.n_iter)}, the last changes {[f'{t[1]:.3g}' for t in trace[-3:]]}")
+    BC.window_condition(name, b, trace)
+    assert np.isfinite(l1).all() and np.isfinite(l2).all() and b.n_nonfinite == 0 and b.n_zero_prop == 0
+    if w["kind"] == "limit":
+        # the sequence is stable, not oscillating: 40 digits and FP64 stop on the same value, so the device's logml is held to the bar too
+        ref = BC.mp_bridge(l1, l2)
+        bars = [_bars([b.logml], [ref[0]]), _bars([b.re2_prop], [ref[1]]), _bars([b.re2_post_iid], [ref[2]])]
+        print(f"{name}: against 40 digits {bars} bars, mpmath ran {ref[3]} iterations")
+        assert ref[3] == 1000 and max(bars) <= 1.0
+    if w["kind"] == "stops":
+        assert all(math.isnan(v) for v in (b.logml, b.re2_prop, b.re2_post_iid, b.rel_change)) and math.isfinite(b.l_star)
+        assert (b.n_fit, b.n1, b.n2) == ((w["R"] // 2) * w["P"], (w["R"] - w["R"] // 2) * w["P"], w["n_prop"])
 
 
 # ---- closed forms, on the twins alone ---------------------------------------------------------------------------------------------------

@@ -4,7 +4,11 @@ set_history_rows; nothing is stepped unless a test says so.
 1. stage by stage with diagnostics=True, each stage against the numpy twin fed with the device's own previous stage: the fit, the draws,
    the two evaluations (against eng.logpost), the iteration; everything at loo_cases.BAR = 1e-9 of max(1, |ref|), the -Inf pattern and the
    counts exactly, n_iter within one.
-2. the closed forms, 3. repeatability and side effects, 4. the refusals, summarize(..., bridge=True), compare_bridge."""
+2. the closed forms, 3. repeatability and side effects, 4. the refusals, summarize(..., bridge=True), compare_bridge.
+5. the same stage-by-stage check past one workgroup of every kernel: each case first asserts, through bridge_cases.geometry (held to the
+   planner by tests/test_bridge_host.py), the plan numbers it is there for.
+6. the iteration where it is slow, at its limit, where an iterate is not a positive finite number, and where the logs are not finite:
+   the split windows of bridge_cases.WINDOWS, each meeting its condition again on the device's own logs."""
 import ctypes as C
 import math
 
@@ -19,8 +23,9 @@ pytestmark = pytest.mark.gpu
 BAR = BC.BAR
 
 
-def check_stages(demc, eng, prob, row0, row1, label, n_prop=0, seed=11):
-    """every stage of the call against its twin -> (out, prop, post, (m, L))"""
+def check_stages(demc, eng, prob, row0, row1, label, n_prop=0, seed=11, keep=None):
+    """every stage of the call against its twin -> (out, prop, post, (m, L)); keep: a dict that receives got and ref (the device's record
+    and the twin's on the device's own logs), trace (the twin's iterates, as bridge_from_logs gives them) and worst (bars per stage)"""
     D, P = eng.D, eng.P
     lo, hi = np.asarray(prob["lo"], dtype=np.float64), np.asarray(prob["hi"], dtype=np.float64)
     out, prop, post, (m, L) = eng.bridge(row0, row1, n_prop, seed, diagnostics=True)
@@ -51,10 +56,14 @@ def check_stages(demc, eng, prob, row0, row1, label, n_prop=0, seed=11):
     # the iteration and the error terms, from the device's own logs
     l1 = (post[:, 0] + post[:, 1]) - post[:, 2]
     l2 = (prop[:, D] + prop[:, D + 1]) - prop[:, D + 2]
-    ref = demc.bridge_from_logs(l1, l2, n_fit=fit.shape[0], lp2=prop[:, D])
+    trace = []
+    ref = demc.bridge_from_logs(l1, l2, n_fit=fit.shape[0], lp2=prop[:, D], trace=trace)
     got = demc.Bridge(out)
+    if keep is not None:
+        keep.update(got=got, ref=ref, trace=trace, worst=worst)
     for name in ("logml", "re2_prop", "re2_post_iid"):
         worst[name] = BC.err_in_bars(np.array([getattr(got, name)]), np.array([getattr(ref, name)]))
+    assert math.isnan(got.rel_change) == math.isnan(ref.rel_change), (label, got.rel_change, ref.rel_change)
     assert got.l_star == ref.l_star or (math.isnan(got.l_star) and math.isnan(ref.l_star)), (label, got.l_star, ref.l_star)
     assert (got.n_zero_prop, got.n_nonfinite, got.converged) == (ref.n_zero_prop, ref.n_nonfinite, ref.converged), label
     assert abs(got.n_iter - ref.n_iter) <= 1, (label, got.n_iter, ref.n_iter)
@@ -292,3 +301,170 @@ def test_summarize_with_bridge_and_compare(demc):
     model, de, _ = _binomial_model(demc, rng, demc.Beta(1.0, 1.0))
     assert demc.summarize(model, de, demc.HIPBackend(seed=2), 300).bridge is None
     assert demc.summarize(model, de, demc.HIPBackend(seed=2), 300, bridge=True).bridge.n2 == 100 * 16 - 50 * 16
+
+
+# ---- 5. past one workgroup: every case first asserts, through bridge_cases.geometry, the path it is there for -----------------------------
+def _gaussian_engine(demc, seed, n, P):
+    rng = np.random.default_rng(seed)
+    prob = make_problem("gaussian", rng, N=50)
+    eng, _ = TP.engine(demc, prob, n, P, rows=BC.spread_rows(rng, prob, n, P))
+    return eng, prob
+
+
+@pytest.mark.parametrize("n_prop", [0, 2049, 257])
+def test_two_reduction_workgroups(demc, n_prop):
+    """N_fit = N1 = 1040: two workgroups of k_bridge_part on the posterior side, and on the proposal side two (n_prop = 0), three with one
+    element in the ninth workgroup of k_bridge_logs / k_bridge_exp (2049), or one with the grid sized by N1 (257); seventeen blocks of the
+    solve; three chunks of the covariance"""
+    R, P = BC.WIN_R, BC.WIN_P
+    label = f"two reduction workgroups, n_prop = {n_prop}"
+    want = {0: dict(N2=1040, W2=2, logs_blocks=5), 2049: dict(N2=2049, W2=3, logs_blocks=9), 257: dict(N2=257, W2=1, logs_blocks=5)}[n_prop]
+    g = BC.asserted_geometry(label, R, P, 2, n_prop, n_fit=1040, N1=1040, W1=2, solve_blocks=17, cov_chunks=3, **want)
+    if n_prop == 2049:
+        assert g["N2"] - (g["logs_blocks"] - 1) * BC.BRIDGE_WG == 1
+    if n_prop == 257:
+        assert g["logs_blocks"] == -(-g["N1"] // BC.BRIDGE_WG) > -(-g["N2"] // BC.BRIDGE_WG)
+    eng, prob = _gaussian_engine(demc, 32000, R, P)
+    out = check_stages(demc, eng, prob, 0, R, label, n_prop=n_prop)[0]
+    assert out[4] == 1 and (out[5], out[6], out[7]) == (1040, 1040, g["N2"])
+    eng.close()
+
+
+@pytest.mark.parametrize("n_prop", [63, 64, 65, 128])
+def test_draw_blocks_and_padding(demc, n_prop):
+    """N2 against pad2 and the 64 lanes of a block of k_bridge_draw: at N2 = 64 the second block holds the one padding row only"""
+    R, P = 6, 13
+    label = f"draw blocks and padding, n_prop = {n_prop}"
+    want = {63: dict(chunks2=5, pad2=65, last2=11, draw_blocks=2), 64: dict(chunks2=5, pad2=65, last2=12, draw_blocks=2),
+            65: dict(chunks2=5, pad2=65, last2=13, draw_blocks=2), 128: dict(chunks2=10, pad2=130, last2=11, draw_blocks=3)}[n_prop]
+    BC.asserted_geometry(label, R, P, 2, n_prop, N2=n_prop, **want)
+    eng, prob = _gaussian_engine(demc, 32100, R, P)
+    check_stages(demc, eng, prob, 0, R, label, n_prop=n_prop)
+    eng.close()
+
+
+@pytest.mark.parametrize("R,P", [(64, 16), (54, 19)])
+def test_covariance_chunk_edge(demc, R, P):
+    """cov_run through the one-cell HistView of the xi buffer at one full chunk of 512 cells and at one cell past it"""
+    n_fit = (R // 2) * P
+    label = f"covariance chunk edge, N_fit = {n_fit}"
+    g = BC.asserted_geometry(label, R, P, 2, 0, n_fit=n_fit, cov_chunks=-(-n_fit // 512), cov_workers=-(-n_fit // 512))
+    assert n_fit in (512, 513) and g["cov_chunks"] == n_fit - 511
+    eng, prob = _gaussian_engine(demc, 32200 + P, R, P)
+    keep = {}
+    check_stages(demc, eng, prob, 0, R, label, keep=keep)
+    assert keep["worst"]["m"] <= 1.0 and keep["worst"]["L"] <= 1.0
+    eng.close()
+
+
+@pytest.mark.parametrize("D,R", [(63, 2), (63, 8), (64, 2), (64, 8)])
+def test_widest_proposal(demc, D, R):
+    """D = 63 and 64 (the cap: 32 KB of LDS in the draw and the solve), the four kinds of bounds assigned cyclically, at N_fit = D + 1 --
+    the least the plan admits; the estimate half then lies so far out in g that r_1 = 0 and the rule of the stopped iterate applies --
+    and at N_fit = 4 (D + 1).  Odd D: block 31 gives z_62 alone, its sine is unused (theta is held to the twin's draws at the bar)."""
+    P = D + 1
+    label = f"widest proposal, D = {D}, N_fit = {(R // 2) * P}"
+    g = BC.asserted_geometry(label, R, P, D, 0, n_fit=(R // 2) * P, lds_bytes=D * 64 * 8, draw_blocks=-(-(R // 2) * P // 64), solve_blocks=-(-(R // 2) * P // 64))
+    assert g["lds_bytes"] <= 32768 and (D + 1) // 2 == 32 and g["n_fit"] > D
+    prob, centre = BC.wide_problem(D)
+    rng = np.random.default_rng(53000 + D + R)
+    eng, _ = TP.engine(demc, prob, R, P, rows=centre + 0.05 * rng.normal(0, 1, (R, P, D)))
+    keep = {}
+    check_stages(demc, eng, prob, 0, R, label, keep=keep)
+    got, ref = keep["got"], keep["ref"]
+    assert got.n_iter == ref.n_iter or R == 8
+    if R == 2:
+        assert ref.n_iter == 1 and got.converged == 0 and got.n_nonfinite == 0 and all(math.isnan(v) for v in (got.logml, got.re2_prop, got.re2_post_iid, got.rel_change))
+    else:
+        assert got.converged == 1
+    eng.close()
+
+
+def test_the_cap_of_the_reduction(demc):
+    """N2 = 262 145 = 256 * 256 * 4 + 1: kBridgeMaxW binds and thread 0 of workgroup 0 takes a fifth element; 513 chunks of P = 512"""
+    R, P, n_prop = 2, BC.CAP_P, BC.CAP_N2
+    label = "the cap of the reduction"
+    g = BC.asserted_geometry(label, R, P, 2, n_prop, N2=n_prop, W2=256, W1=1, chunks2=513, pad2=513 * 512, last2=1, n_fit=512, N1=512)
+    assert -(-g["N2"] // (g["W2"] * BC.BRIDGE_WG)) == 5 and BC.geometry(R, P, 2, n_prop - 1)["W2"] == 256 and -(-(n_prop - 1) // (256 * BC.BRIDGE_WG)) == 4
+    eng, prob = _gaussian_engine(demc, 32300, R, P)
+    out = check_stages(demc, eng, prob, 0, R, label, n_prop=n_prop)[0]
+    assert out[7] == n_prop and out[4] == 1
+    eng.close()
+
+
+# ---- 6. the iteration where it is slow, where it runs to its limit, where r stops, and where the logs are not finite ------------------------
+@pytest.mark.parametrize("name", list(BC.WINDOWS))
+def test_iteration_on_split_windows(demc, name):
+    """the windows of bridge_cases.WINDOWS, each meeting its condition again on the device's own logs.  slow: converged within one
+    iteration of the twin after more than one batch of eight.  iteration limit: 1000 iterations and not converged on both sides; the
+    window's sequence is stable (tests/test_bridge_host.py: 40 digits and FP64 end on the same value), so logml and the error terms are
+    held to the bar as everywhere.  r stops: r_1 = 0; the outputs follow DESIGN.md 5.10 step 5 field by field."""
+    w = BC.WINDOWS[name]
+    R, P = w["R"], w["P"]
+    prob, rows = BC.split_window(name)
+    g = BC.asserted_geometry(name, R, P, 2, w["n_prop"], N1=(R - R // 2) * P, N2=w["n_prop"] or (R - R // 2) * P,
+                             **(dict(W1=2, W2=3 if w["n_prop"] else 2) if R == BC.WIN_R else dict(W1=1, W2=1)))
+    eng, _ = TP.engine(demc, prob, R, P, rows=rows)
+    keep = {}
+    out = check_stages(demc, eng, prob, 0, R, name, n_prop=w["n_prop"], seed=BC.WINDOW_DRAW_SEED, keep=keep)[0]
+    got, ref, trace = keep["got"], keep["ref"], keep["trace"]
+    BC.window_condition(name, ref, trace)
+    print(f"{name}: device {int(got.n_iter)} iterations, twin {int(ref.n_iter)}; the twin's last changes {[f'{t[1]:.3g}' for t in trace[-3:]]}")
+    if w["kind"] == "slow":
+        assert got.converged == 1 and abs(got.n_iter - ref.n_iter) <= 1 and got.n_iter > BC.BRIDGE_BATCH and math.isfinite(got.logml)
+    elif w["kind"] == "limit":
+        assert got.n_iter == ref.n_iter == 1000 and got.converged == 0 and all(math.isfinite(v) for v in out[[0, 1, 2, 8, 11]]) and got.rel_change > 1e-10
+    else:
+        assert got.n_iter == ref.n_iter and got.converged == 0 and got.n_nonfinite == 0 and got.l_star == ref.l_star and math.isfinite(got.l_star)
+        assert np.isnan(out[[0, 1, 2, 11]]).all() and (out[5], out[6], out[7]) == (g["n_fit"], g["N1"], g["N2"]) and out[9] == ref.n_zero_prop
+        same = np.array_equal(np.isnan(out), np.isnan(ref.out)) and np.array_equal(out[~np.isnan(out)], ref.out[~np.isnan(ref.out)])
+        assert same, (out, ref.out)  # device and twin agree field by field
+    eng.close()
+
+
+@pytest.mark.parametrize("which", ["a few", "all"])
+def test_minus_inf_among_l1(demc, which):
+    """LNR with the upper bound of tau lifted (the recipe of the proposal-side test): tau above the data's fastest time in a few draws of
+    the estimate half -- their l1 is -Inf, the term 1 / (s2 r), logml finite and at the bar -- then in all of them: no l1 is finite,
+    l* = -Inf, no iteration runs, nothing is counted as not finite, and the outputs are NaN"""
+    rng = np.random.default_rng(31500)
+    prob = make_problem("lnr", rng, N=65, na=2)
+    rt_min = float(np.asarray(prob["data"][65:]).min())
+    prob["hi"] = [np.inf] * 3
+    prob["pk"], prob["pa"], prob["pb"] = [1, 1, 1], [0, 0, 0.0], [3, 3, 3.0]
+    n, P = 6, 13
+    BC.asserted_geometry(f"-Inf among l1, {which}", n, P, 3, 0, n_fit=39, N1=39, N2=39, W1=1, W2=1)
+    rows = posterior_like(rng, prob, n, P)
+    rows[..., 2] = rt_min * rng.uniform(0.55, 0.99, (n, P))
+    outside = [(3, 0), (4, 7), (5, 12)] if which == "a few" else [(r, s) for r in range(3, 6) for s in range(P)]
+    for r, s in outside:
+        rows[r, s, 2] = rt_min * rng.uniform(1.01, 1.2)
+    eng, _ = TP.engine(demc, prob, n, P, rows=rows)
+    keep = {}
+    out, prop, post, _ = check_stages(demc, eng, prob, 0, n, f"lnr, tau above the fastest time in {which} of the estimate half", keep=keep)
+    got = keep["got"]
+    assert np.isneginf(post[:, 0]).sum() == len(outside) and np.isfinite(post[:, 1:]).all() and got.n_nonfinite == 0
+    if which == "a few":
+        assert math.isfinite(got.logml) and got.converged == 1 and math.isfinite(got.l_star)
+    else:
+        assert got.l_star == -math.inf and got.n_iter == 0 and got.converged == 0 and np.isnan(out[[0, 1, 2, 11]]).all()
+    eng.close()
+
+
+def test_a_nan_observation_makes_every_log_ratio_nan(demc):
+    """demc_set_model takes Gaussian data as it comes: one NaN observation makes every lp NaN, so the rule of DESIGN.md 5.10 step 5 for
+    a NaN among l1 or l2 is reachable through the C surface: all N1 + N2 are counted, no iteration runs, l* is NaN (no l1 but NaNs)"""
+    rng = np.random.default_rng(31600)
+    prob = make_problem("gaussian", rng, N=50)
+    prob["data"] = np.array(prob["data"], dtype=np.float64)
+    n, P = 6, 13
+    rows = BC.spread_rows(rng, prob, n, P)
+    prob["data"][7] = np.nan
+    BC.asserted_geometry("a NaN observation", n, P, 2, 0, N1=39, N2=39, W1=1, W2=1)
+    eng, _ = TP.engine(demc, prob, n, P, rows=rows)
+    keep = {}
+    out, prop, post, _ = check_stages(demc, eng, prob, 0, n, "gaussian with a NaN observation", keep=keep)
+    got = keep["got"]
+    assert np.isnan(post[:, 0]).all() and np.isnan(prop[:, 2]).all() and np.isfinite(prop[:, :2]).all()
+    assert got.n_nonfinite == 39 + 39 and got.n_iter == 0 and got.converged == 0 and math.isnan(got.l_star) and np.isnan(out[[0, 1, 2, 11]]).all() and got.n_zero_prop == 0
+    eng.close()
