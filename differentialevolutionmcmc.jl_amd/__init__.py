@@ -6,7 +6,7 @@ any sampling call raises -- there is no CPU fallback.
 """
 from . import _ffi, families
 from ._ffi import DemcError, HipEngine, MultiEngine
-from .chains import (Bridge, Chains, Loo, RankStats, Summary, Waic, bridge_draws, bridge_fit, bridge_from_logs, bridge_transform, compare_bridge, compare_loo,
+from .chains import (Bridge, Chains, Hpd, Loo, RankStats, Summary, Waic, bridge_draws, bridge_fit, bridge_from_logs, bridge_transform, compare_bridge, compare_loo,
                      compare_waic, loo_from_loglik, waic_from_loglik)
 from .families import (Beta, BinomialLikelihood, Cauchy, Exponential, Flat, Gamma, GaussianLikelihood, LogNormal, HierBinomialLikelihood,
                        HierGaussianLikelihood, LBALikelihood, LNRLikelihood, LotkaVolterraLikelihood, MvNormalFullLikelihood,
@@ -21,4 +21,4 @@ DEMCMC = __name__
 
 __all__ = ["DE", "Particle", "DEModel", "sample", "MCMCThreads", "HIPBackend", "fixed_gamma", "variable_gamma",
            "random_gamma", "evaluate_fun", "compute_posterior", "optimize", "get_optimal", "resample", "as_union",
-           "mh_update", "maximize", "minimize", "Chains", "Summary", "RankStats", "Waic", "compare_waic", "waic_from_loglik", "Loo", "compare_loo", "loo_from_loglik", "Bridge", "compare_bridge", "bridge_from_logs", "bridge_transform", "bridge_fit", "bridge_draws", "summarize", "Priors", "HipEngine", "MultiEngine", "DemcError"]
+           "mh_update", "maximize", "minimize", "Chains", "Summary", "RankStats", "Hpd", "Waic", "compare_waic", "waic_from_loglik", "Loo", "compare_loo", "loo_from_loglik", "Bridge", "compare_bridge", "bridge_from_logs", "bridge_transform", "bridge_fit", "bridge_draws", "summarize", "Priors", "HipEngine", "MultiEngine", "DemcError"]

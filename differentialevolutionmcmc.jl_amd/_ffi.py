@@ -42,6 +42,8 @@ BRIDGE_EXPORTS = ["demc_bridge"]  # include/demc_bridge.h: the marginal likeliho
 BRIDGE_NOUT, BRIDGE_MAX_D, BRIDGE_MAX_DRAWS, BRIDGE_MAX_ITER = 12, 64, 1 << 22, 1000  # DEMC_BRIDGE_NOUT, _MAX_D, _MAX_DRAWS, _MAX_ITER
 RANK_EXPORTS = ["demc_rankstats", "demc_rank_series"]  # include/demc_rank.h: ess_bulk / ess_tail / rank-normalised rhat, one ranked series
 RANK_COLS, RANK_KIND_RANK, RANK_KIND_SCORE, RANK_KIND_FOLDED = 8, 0, 1, 2  # DEMC_RANK_COLS, DEMC_RANK_KIND_*
+HPD_EXPORTS = ["demc_hpd"]  # include/demc_hpd.h: highest-density intervals off the sorted pool
+HPD_COLS, HPD_MAX_ALPHAS = 4, 16  # DEMC_HPD_COLS, DEMC_HPD_MAX_ALPHAS
 COMM_ID_BYTES = 128
 _NOT_STATUS = {"demc_last_error": C.c_char_p, "demc_multi_last_error": C.c_char_p, "demc_multi_shard": C.c_void_p}
 
@@ -165,6 +167,7 @@ def load():
     L.demc_bridge.argtypes = [H, C.c_int64, C.c_int64, C.c_int64, C.c_uint64, _dp, _dp, _dp, _dp]
     L.demc_rankstats.argtypes = [H, C.c_int64, C.c_int64, C.c_int32, _dp]
     L.demc_rank_series.argtypes = [H, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _dp]
+    L.demc_hpd.argtypes = [H, C.c_int64, C.c_int64, _dp, C.c_int32, _dp]
     L.demc_step.argtypes = [H, C.c_int64, C.c_int32]
     L.demc_update.argtypes = [H, C.c_int64, C.c_int32]
     L.demc_migration_due.argtypes = [C.POINTER(DemcConfig), C.c_int64]
@@ -197,7 +200,7 @@ def load():
     L.demc_multi_size.argtypes = [H]
     L.demc_multi_shard.argtypes = [H, C.c_int32]
     L.demc_multi_step.argtypes = [H, C.c_int64, C.c_int32]
-    for name in EXPORTS + SUMMARY_EXPORTS + QUANTILE_EXPORTS + COV_EXPORTS + PW_EXPORTS + LOO_EXPORTS + BRIDGE_EXPORTS + RANK_EXPORTS:  # every entry point returns an int32 status, except the error strings and the shard accessor
+    for name in EXPORTS + SUMMARY_EXPORTS + QUANTILE_EXPORTS + COV_EXPORTS + PW_EXPORTS + LOO_EXPORTS + BRIDGE_EXPORTS + RANK_EXPORTS + HPD_EXPORTS:  # every entry point returns an int32 status, except the error strings and the shard accessor
         getattr(L, name).restype = _NOT_STATUS.get(name, C.c_int32)
     _lib = L
     return L
@@ -472,6 +475,15 @@ class HipEngine:
         out = np.full((max(n, 1), self.P), np.nan)
         self._ck(self.L.demc_rank_series(self.h, row0, row1, series, kind, _d(out)))
         return out[:n]
+
+    def hpd(self, row0, row1, alphas=(0.05,)):
+        """highest-density intervals of history rows [row0,row1) read off the sorted pool on the device (demc_hpd of
+        include/demc_hpd.h), chains pooled, one per series and alpha -> out[D+2][len(alphas)][4] in the order of
+        chains.HPD_COLS, equal to chains.series_hpd of the same rows bit for bit"""
+        alphas = np.ascontiguousarray(alphas, dtype=np.float64).reshape(-1)
+        out = np.full((self.D + 2, max(len(alphas), 1), HPD_COLS), np.nan)
+        self._ck(self.L.demc_hpd(self.h, row0, row1, _d(alphas), len(alphas), _d(out)))
+        return out[:, :len(alphas)]
 
     def bridge_served(self):
         """what demc_bridge would refuse about this handle whatever the rows, asked BEFORE a run (summarize(..., bridge=True)): raises

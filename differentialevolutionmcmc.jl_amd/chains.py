@@ -5,7 +5,8 @@ computes the same numbers from the history without exporting it: demc_summarize)
 (demc_quantiles on the device), cov(chains) / cor(chains) (demc_covariance), and WAIC from
 the per-observation log-densities (demc_waic), PSIS-LOO from the same terms (demc_loo), and the marginal likelihood by
 bridge sampling from two vectors of log ratios (demc_bridge), and the rank-normalised diagnostics ess_bulk,
-ess_tail and rhat of the pooled, ranked history (demc_rankstats)."""
+ess_tail and rhat of the pooled, ranked history (demc_rankstats), and the highest-density intervals of
+hpd(chains) read off the sorted pool (demc_hpd)."""
 import math
 
 import numpy as np
@@ -24,11 +25,13 @@ class Summary:
     (or None): the covariance and correlation of the series `cov_names`, chains pooled.  `waic` (or None): the Waic
     record of the same rows.  `loo` (or None): the Loo record of the same rows.
     `bridge` (or None): the Bridge record of the same rows.  `rank` (or None): the RankStats record of the same
-    rows -- ess_bulk, ess_tail and the rank-normalised rhat."""
+    rows -- ess_bulk, ess_tail and the rank-normalised rhat.  `hpd` (or None): the Hpd record of the same rows --
+    the highest-density intervals at the alphas the run was summarised with."""
 
     def __init__(self, names, values, internals=("acceptance", "lp"), rho=None, quantiles=None, probs=None, cov=None, cor=None,
-                 cov_names=None, waic=None, loo=None, bridge=None, rank=None):
+                 cov_names=None, waic=None, loo=None, bridge=None, rank=None, hpd=None):
         self.rank = rank
+        self.hpd = hpd
         self.waic = waic
         self.loo = loo
         self.bridge = bridge
@@ -334,6 +337,13 @@ class Chains:
         was never exported."""
         return RankStats(self.names, [series_rankstats(self.value[:, j, :], max_lag) for j in range(len(self.names))], self.internals)
 
+    def hpd(self, alpha=0.05):
+        """The Hpd of this object computed on the host (numpy): MCMCChains' hpd(chains; alpha) with the chains pooled, one row per
+        series with lower and upper -- what demc_hpd computes on the device for a history that was never exported.
+        alpha: one value or a tuple of them."""
+        alphas = hpd_alphas(alpha)
+        return Hpd(self.names, [series_hpd(self.value[:, j, :], alphas) for j in range(len(self.names))], alphas, self.internals)
+
 
 # ---- rank-normalised diagnostics (DESIGN.md section 5.11; demc_rankstats on the device) -------------------------------------------
 RANK_COLS = ("rhat", "ess_bulk", "ess_tail", "rhat_bulk", "rhat_folded", "ess_q05", "ess_q95", "distinct")  # demc_rankstats' out (DEMC_RANK_COLS)
@@ -456,6 +466,81 @@ class RankStats:
     def __repr__(self):
         rows = [f"  {nm:>12s}  rhat {v[0]:.4f}  ess_bulk {v[1]:.1f}  ess_tail {v[2]:.1f}" for nm, v in zip(self.names, self.values)]
         return "RankStats(\n" + "\n".join(rows) + "\n)"
+
+
+# ---- highest-density intervals (demc_hpd on the device) ------------------------------------------------------
+HPD_COLS = ("lower", "upper", "first", "m")  # demc_hpd's out (DEMC_HPD_COLS): first is the 0-based sorted position of lower
+HPD_MAX_ALPHAS = 16  # DEMC_HPD_MAX_ALPHAS
+
+
+def hpd_alphas(alpha):
+    alphas = tuple(float(a) for a in (alpha if isinstance(alpha, (tuple, list, np.ndarray)) else (alpha,)))
+    if not 1 <= len(alphas) <= HPD_MAX_ALPHAS or not all(math.isfinite(a) and 0.0 < a < 1.0 for a in alphas):
+        raise ValueError(f"hpd takes between 1 and {HPD_MAX_ALPHAS} alphas, each strictly inside (0, 1)")
+    return alphas
+
+
+def hpd_candidates(N, alpha):
+    """m = max(1, ceil(alpha N)): the product is one rounded double multiplication of alpha, as passed, by float(N)"""
+    return max(1, math.ceil(float(np.float64(alpha) * np.float64(N))))
+
+
+def series_hpd(x, alphas):
+    """DESIGN.md 5.12 for one series x (any shape; the chains are pooled) on the host -> [len(alphas)][4] over HPD_COLS: the pool
+    sorted by key, the m = max(1, ceil(alpha N)) candidates [y[i], y[N - m + i]], their widths by one subtraction each, and the
+    first minimum in the order of Julia's findmin -- what demc_hpd computes on the device"""
+    x = np.asarray(x, dtype=np.float64)
+    k = np.sort(series_keys(x).reshape(-1))
+    N = k.size
+    if N < 1:
+        raise ValueError("series_hpd needs at least one value")
+    has_nan = bool(k[0] < _KEY_NEG_INF or k[-1] > _KEY_POS_INF)
+    y = (k ^ np.where(k >> np.uint64(63) != 0, _SIGN, _ALL)).view(np.float64)  # y[0] <= ... <= y[N - 1], -0.0 before +0.0
+    nan = float("nan")
+    out = np.empty((len(alphas), len(HPD_COLS)))
+    for a, alpha in enumerate(alphas):
+        m = hpd_candidates(N, alpha)
+        assert 1 <= m <= N
+        if has_nan:
+            out[a] = (nan, nan, nan, float(m))
+            continue
+        with np.errstate(all="ignore"):
+            w = y[N - m:] - y[:m]  # inf - inf of one sign: NaN
+        isnan = np.isnan(w)
+        if isnan.any():  # a NaN width ranks below every number: the first of them (np.argmin is not asked what it does with NaN)
+            i = int(np.flatnonzero(isnan)[0])
+        else:  # compared by value; among equal widths the smallest i
+            i = int(np.flatnonzero(w == w.min())[0])
+        out[a] = (y[i], y[N - m + i], float(i), float(m))
+    return out
+
+
+class Hpd:
+    """The highest-density intervals of a run (MCMCChains' hpd, chains pooled): `values[j][k]` = (lower, upper, first,
+    m) of series names[j] -- the parameters, then acceptance and lp -- at alphas[k]."""
+
+    def __init__(self, names, values, alphas, internals=("acceptance", "lp")):
+        self.names = list(names)
+        self.alphas = tuple(float(a) for a in alphas)
+        self.values = np.asarray(values, dtype=np.float64).reshape(len(self.names), len(self.alphas), len(HPD_COLS))
+        self.internals = list(internals)
+
+    def __getitem__(self, name):
+        """the four columns by name; with several alphas {alpha: columns}"""
+        rows = [dict(zip(HPD_COLS, (float(v) for v in row))) for row in self.values[self.names.index(name)]]
+        return rows[0] if len(rows) == 1 else dict(zip(self.alphas, rows))
+
+    def describe(self):
+        """per parameter name {lower, upper} (with several alphas {alpha: {lower, upper}}): the two columns MCMCChains.hpd reports"""
+        def two(d):
+            return {c: d[c] for c in HPD_COLS[:2]}
+        return {nm: two(self[nm]) if len(self.alphas) == 1 else {a: two(d) for a, d in self[nm].items()}
+                for nm in self.names if nm not in self.internals}
+
+    def __repr__(self):
+        rows = [f"  {nm:>12s}  " + "  ".join(f"{100 * (1 - a):g}% [{v[0]:.4f}, {v[1]:.4f}]" for a, v in zip(self.alphas, vs))
+                for nm, vs in zip(self.names, self.values)]
+        return "Hpd(\n" + "\n".join(rows) + "\n)"
 
 
 # ---- PSIS-LOO (DESIGN.md section 5.9; demc_loo on the device) ------------------------------------------------------------------

@@ -22,6 +22,7 @@
 #include "../../include/demc_loo.h"  // demc_loo
 #include "../../include/demc_bridge.h"  // demc_bridge
 #include "../../include/demc_rank.h"  // demc_rankstats, demc_rank_series
+#include "../../include/demc_hpd.h"  // demc_hpd
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -1520,11 +1521,13 @@ int32_t demc_loo(demc_handle* h, int64_t row0, int64_t row1, double* total_out, 
 
 // The rank diagnostics (include/demc_rank.h): every refusal and the plan are demc_rankplan.hpp's, the run is demc_rank.cpp's.  The
 // derived history of a batch holds four series per series ranked; its summary is planned here, for a whole batch and for the last.
+// the one place the sort is planned: the two rank calls over their series, demc_hpd over one series of its window
+static RankPlan sort_plan(long long n, long long P, int series) { return plan_rank(n, P, series); }
 static int32_t rank_call(demc_handle* h, int64_t row0, int64_t row1, int32_t max_lag, bool single, int series, int kind, double* out) {
     if (Refusal r = check_rank_window(h->hist != nullptr, row0, row1, h->c.n_rows, h->c.n_groups_total != h->c.n_groups, h->P,
                                       rank_args(out != nullptr, (int)max_lag, single, series, kind, h->c.D)))
         return fail(h, r);
-    const RankPlan plan = plan_rank(row1 - row0, h->P, single ? 1 : h->c.D + 2);
+    const RankPlan plan = sort_plan(row1 - row0, h->P, single ? 1 : h->c.D + 2);
     if (plan.refused) return fail(h, plan.refused);
     const SummaryPlan full = sum_plan(plan.n, plan.P, kRankDerived * plan.batch, (int)max_lag, 0, false);
     const SummaryPlan last = sum_plan(plan.n, plan.P, kRankDerived * plan.last_batch, (int)max_lag, 0, false);
@@ -1548,6 +1551,23 @@ int32_t demc_rank_series(demc_handle* h, int64_t row0, int64_t row1, int32_t ser
     if (!h) return DEMC_EINVAL;
     USE_DEVICE(h);
     return rank_call(h, row0, row1, 0, true, (int)series, (int)kind, out);
+    });
+}
+
+// Highest-density intervals (include/demc_hpd.h): every refusal and the plan are demc_hpdplan.hpp's, on top of the sort of one series
+// as demc_rankplan.hpp plans it; the run is demc_rank.cpp's, where the kernels of the sort live.
+int32_t demc_hpd(demc_handle* h, int64_t row0, int64_t row1, const double* alphas, int32_t n_alphas, double* out) {
+    return guarded(h, [&]() -> int32_t {
+    if (!h) return DEMC_EINVAL;
+    USE_DEVICE(h);
+    if (Refusal r = check_hpd_window(h->hist != nullptr, row0, row1, h->c.n_rows, h->c.n_groups_total != h->c.n_groups, h->P,
+                                     hpd_args(out != nullptr, alphas, (int)n_alphas)))
+        return fail(h, r);
+    const HpdPlan plan = plan_hpd(sort_plan(row1 - row0, h->P, 1), h->c.D + 2, alphas, (int)n_alphas);
+    if (plan.refused) return fail(h, plan.refused);
+    std::string msg;
+    const int rc = hpd_run(hist_view(h, row0, row1), plan, h->stream, out, msg);
+    return rc == DEMC_OK ? DEMC_OK : fail(h, rc, msg);
     });
 }
 

@@ -1,6 +1,7 @@
 // demc_rank.cpp -- the kernels of demc_rankstats and demc_rank_series (demc_rank.hpp says what each does; DESIGN.md 5.11 is the
 // definition) and the host code that strings them together, in a translation unit of their own: the other code objects of the
-// library do not change when this one does.
+// library do not change when this one does.  demc_hpd lives here too: it is the sort of round 0, whose kernels are
+// local to this unit, followed by two kernels of its own.
 #include "demc_rank.hpp"
 
 #include <algorithm>
@@ -308,11 +309,90 @@ __global__ __launch_bounds__(64) void k_rank_final(RankKParams p, const double* 
     o[7] = (double)p.word[(size_t)b * 3 + 2];
 }
 
+// ---- demc_hpd: the sorted keys of round 0, then one pass over the window widths ---------------------------------------
+
+struct HpdBest {  // a candidate and its width; i < 0: none yet
+    double w;
+    long long i;
+};
+
+// the one of two candidates that Julia's findmin meets first: a NaN width ranks below every number, other widths compare by value,
+// equal widths (two NaNs among them) by position.  A total order over distinct i: the minimum does not depend on how it is grouped.
+__device__ __forceinline__ HpdBest hpd_min(HpdBest a, HpdBest b) {
+    const bool an = a.w != a.w, bn = b.w != b.w;
+    bool a_first;
+    if (a.i < 0 || b.i < 0) a_first = b.i < 0;
+    else if (an != bn) a_first = an;
+    else if (!an && a.w != b.w) a_first = a.w < b.w;
+    else a_first = a.i < b.i;
+    return HpdBest{a_first ? a.w : b.w, a_first ? a.i : b.i};  // (field by field: the two records stay in registers)
+}
+__device__ __forceinline__ HpdBest hpd_wave_min(HpdBest best) {
+    for (int s = 32; s > 0; s >>= 1) {
+        const HpdBest o{__shfl_xor(best.w, s, 64), __shfl_xor(best.i, s, 64)};
+        best = hpd_min(best, o);
+    }
+    return best;
+}
+// the sorted keys of series b of the batch: the buffer the passes that ran left them in
+__device__ __forceinline__ const u64* hpd_sorted(const RankKParams& p, int b) {
+    return p.keys + ((size_t)rank_src(rank_diff(p, 0, b), kRankPasses) * p.B + b) * p.N;
+}
+
+// blockIdx.y the series of the batch, blockIdx.z the alpha; lanes on consecutive candidates i: two coalesced loads, y[i] and
+// y[N - m + i], one subtraction; the best of a thread, of its wave (shuffles), of the workgroup (LDS) -> one partial per workgroup
+__global__ __launch_bounds__(kHpdWG) void k_hpd_window(RankKParams p, HpdGrid g, double* part_w, long long* part_i) {
+    __shared__ double sw[kHpdWG / 64];
+    __shared__ long long si[kHpdWG / 64];
+    const int b = blockIdx.y, k = blockIdx.z, wgs = g.wgs[k];
+    if ((int)blockIdx.x >= wgs) return;  // (uniform over the workgroup: an alpha with fewer candidates than the largest)
+    const long long m = g.m[k], top = p.N - m, stride = (long long)wgs * kHpdWG;
+    const u64* ks = hpd_sorted(p, b);
+    HpdBest best{0.0, -1};
+    for (long long i = (long long)blockIdx.x * kHpdWG + threadIdx.x; i < m; i += stride) {
+        const HpdBest c{rank_value(ks[top + i]) - rank_value(ks[i]), i};
+        best = hpd_min(best, c);
+    }
+    best = hpd_wave_min(best);
+    if ((threadIdx.x & 63) == 0) {
+        sw[threadIdx.x >> 6] = best.w;
+        si[threadIdx.x >> 6] = best.i;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int v = 1; v < kHpdWG / 64; ++v) best = hpd_min(best, HpdBest{sw[v], si[v]});
+        const size_t at = ((size_t)b * g.n_alphas + k) * g.slots + blockIdx.x;
+        part_w[at] = best.w;
+        part_i[at] = best.i;
+    }
+}
+
+// one wave per (series of the batch, alpha): the partials in index order, the NaN flag of the pool, keys back to values
+__global__ __launch_bounds__(kHpdFinalWG) void k_hpd_final(RankKParams p, HpdGrid g, const double* part_w, const long long* part_i) {
+    const int b = blockIdx.x, k = blockIdx.y;
+    const size_t base = ((size_t)b * g.n_alphas + k) * g.slots;
+    const long long m = g.m[k];
+    HpdBest best{0.0, -1};
+    for (int x = threadIdx.x; x < g.wgs[k]; x += kHpdFinalWG) best = hpd_min(best, HpdBest{part_w[base + x], part_i[base + x]});
+    best = hpd_wave_min(best);
+    if (threadIdx.x != 0) return;
+    double* o = p.out + ((size_t)(p.j0 + b) * g.n_alphas + k) * DEMC_HPD_COLS;
+    if (p.flag[b] || best.i < 0 || best.i >= m) {
+        o[0] = o[1] = o[2] = rank_nan();
+    } else {
+        const u64* ks = hpd_sorted(p, b);
+        o[0] = rank_value(ks[best.i]);
+        o[1] = rank_value(ks[p.N - m + best.i]);
+        o[2] = (double)best.i;
+    }
+    o[3] = (double)m;
+}
+
 // keys in buffer 0 -> sorted pairs in the buffer rank_src(diff, kRankPasses) names
-void sort_round(const RankKParams& p, const RankPlan& plan, int round, hipStream_t st) {
-    const dim3 stream_grid((unsigned)plan.blocks, (unsigned)p.B), tile_grid((unsigned)plan.tiles, (unsigned)p.B);
+void sort_round(const RankKParams& p, int blocks, int tiles, int passes, int round, hipStream_t st) {
+    const dim3 stream_grid((unsigned)blocks, (unsigned)p.B), tile_grid((unsigned)tiles, (unsigned)p.B);
     hipLaunchKernelGGL(k_rank_range, stream_grid, dim3(kRankWG), 0, st, p, round);
-    for (int d = 0; d < plan.passes; ++d) {  // a pass whose digit the pool shares costs three launches that return at once
+    for (int d = 0; d < passes; ++d) {  // a pass whose digit the pool shares costs three launches that return at once
         hipLaunchKernelGGL(k_rank_hist, tile_grid, dim3(kRankWave), 0, st, p, round, d);
         hipLaunchKernelGGL(k_rank_scan, dim3((unsigned)p.B), dim3(kRankScanWG), 0, st, p, round, d);
         hipLaunchKernelGGL(k_rank_scatter, tile_grid, dim3(kRankWave), 0, st, p, round, d);
@@ -356,7 +436,7 @@ int rank_run(const HistView& v, const RankPlan& plan, const SummaryPlan& full, c
         if (!hip_ok(who, e, err)) return DEMC_EHIP;
         hipLaunchKernelGGL(k_rank_keys, flat_grid, dim3(kRankWG), 0, st, p);
         marks = marks && tr.mark(st);
-        sort_round(p, plan, 0, st);
+        sort_round(p, plan.blocks, plan.tiles, plan.passes, 0, st);
         marks = marks && tr.mark(st);
         hipLaunchKernelGGL(k_rank_ties, stream_grid, dim3(kRankWG), 0, st, p, 0, plan.tg);
         if (single && kind == DEMC_RANK_KIND_RANK) break;
@@ -367,7 +447,7 @@ int rank_run(const HistView& v, const RankPlan& plan, const SummaryPlan& full, c
         hipLaunchKernelGGL(k_rank_derive, flat_grid, dim3(kRankWG), 0, st, p);
         hipLaunchKernelGGL(k_rank_keys_folded, stream_grid, dim3(kRankWG), 0, st, p);
         marks = marks && tr.mark(st);
-        sort_round(p, plan, 1, st);
+        sort_round(p, plan.blocks, plan.tiles, plan.passes, 1, st);
         marks = marks && tr.mark(st);
         hipLaunchKernelGGL(k_rank_ties, stream_grid, dim3(kRankWG), 0, st, p, 1, plan.tg);
         if (single) break;
@@ -383,6 +463,44 @@ int rank_run(const HistView& v, const RankPlan& plan, const SummaryPlan& full, c
     if (!marks) { err = std::string(who) + ": an event could not be recorded"; return DEMC_EHIP; }
     if (!finish(who, st, {{out, single ? p.rk : p.out, (single ? (size_t)plan.N : plan.n_out) * sizeof(double)}}, err)) return DEMC_EHIP;
     if (!single) tr.print(who, 5 * plan.batches, 1);
+    return DEMC_OK;
+}
+
+int hpd_run(const HistView& v, const HpdPlan& plan, hipStream_t st, double* out, std::string& err) {
+    const char* name = "demc_hpd";
+    RankKParams p{};
+    p.hist = v.hist; p.acc = v.acc; p.lp = v.lp;
+    p.P = v.P; p.row0 = v.row0; p.N = plan.N;
+    p.D = v.D; p.ld = v.ld; p.tiles = plan.tiles; p.scan_chunk = plan.scan_chunk;
+    Scratch s;
+    double* part_w = nullptr;
+    long long* part_i = nullptr;
+    if (!(s.get(&p.keys, plan.n_keys) && s.get(&p.pos, plan.n_pos) && s.get(&p.cnt, plan.n_hist) && s.get(&p.word, plan.n_word) &&
+          s.get(&p.flag, plan.n_flag) && s.get(&part_w, plan.n_part) && s.get(&part_i, plan.n_part) && s.get(&p.out, plan.n_out))) {
+        err = std::string(name) + ": out of device memory for the scratch buffers";
+        return DEMC_ENOMEM;
+    }
+    const HpdGrid& g = plan.grid;
+    PassTrace tr;  // (the diagnostic variant: per batch keys | sort | window and final)
+    bool marks = tr.mark(st);
+    for (int bi = 0; bi < plan.batches; ++bi) {
+        p.j0 = bi * plan.batch;
+        p.B = bi == plan.batches - 1 ? plan.last_batch : plan.batch;
+        hipError_t e = hipMemsetAsync(p.word, 0, plan.n_word * sizeof(u64), st);
+        if (e == hipSuccess) e = hipMemsetAsync(p.flag, 0, plan.n_flag * sizeof(int), st);
+        if (!hip_ok(name, e, err)) return DEMC_EHIP;
+        hipLaunchKernelGGL(k_rank_keys, dim3((unsigned)plan.blocks), dim3(kRankWG), 0, st, p);
+        marks = marks && tr.mark(st);
+        sort_round(p, plan.blocks, plan.tiles, plan.passes, 0, st);
+        marks = marks && tr.mark(st);
+        hipLaunchKernelGGL(k_hpd_window, dim3((unsigned)g.slots, (unsigned)p.B, (unsigned)g.n_alphas), dim3(kHpdWG), 0, st, p, g, part_w, part_i);
+        hipLaunchKernelGGL(k_hpd_final, dim3((unsigned)p.B, (unsigned)g.n_alphas), dim3(kHpdFinalWG), 0, st, p, g, (const double*)part_w,
+                           (const long long*)part_i);
+        marks = marks && tr.mark(st);
+    }
+    if (!marks) { err = std::string(name) + ": an event could not be recorded"; return DEMC_EHIP; }
+    if (!finish(name, st, {{out, p.out, plan.n_out * sizeof(double)}}, err)) return DEMC_EHIP;
+    tr.print(name, 3 * plan.batches, 1);
     return DEMC_OK;
 }
 

@@ -24,11 +24,22 @@
 //   summary_enqueue (demc_summary.cpp) on a HistView of der: the tested kernels of section 5.5.
 //   k_rank_final    gathers the eight columns of every series of the batch.
 // No floating-point atomics, no scratch memory; two calls give the same bits.
+//
+// demc_hpd (include/demc_hpd.h; the definition is DESIGN.md 5.12) is the same sort -- keys, range, then hist / scan / scatter per
+// digit, the positions riding along unused -- followed by:
+//   k_hpd_window    blockIdx.y the series of the batch, blockIdx.z the alpha, lanes on consecutive candidates i < m: y[i] and
+//                   y[N - m + i] from the buffer rank_src(diff, kRankPasses) names (which of the two it is depends on how many
+//                   passes ran), one subtraction, the running best as (width, i) under findmin's order -- NaN first, then by
+//                   value, then the smaller i --, reduced over the wave by shuffles and over the workgroup through LDS: one
+//                   partial per workgroup.  Beyond kHpdMaxBlocks workgroups a thread strides.
+//   k_hpd_final     one wave per (series, alpha): the partials in index order, the NaN flag of the pool, keys back to values,
+//                   the four columns.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <string>
 
+#include "demc_hpdplan.hpp"   // host-only: the kHpd* constants, HpdPlan, HpdGrid
 #include "demc_postplan.hpp"  // HistView, SummaryPlan
 #include "demc_rankplan.hpp"  // host-only: the kRank* constants, RankPlan, RankTargets
 
@@ -39,5 +50,9 @@ namespace demc {
 // of that one series into out[n][P].  0 or a DEMC_* code with a message.
 int rank_run(const HistView& v, const RankPlan& plan, const SummaryPlan& full, const SummaryPlan& last, int series, int kind, hipStream_t stream,
              double* out, std::string& err);
+
+// host: what plan_hpd planned for the rows of `v`, on `stream`: the table of demc_hpd into out[D+2][n_alphas][4].  0 or a DEMC_* code
+// with a message.
+int hpd_run(const HistView& v, const HpdPlan& plan, hipStream_t stream, double* out, std::string& err);
 
 }  // namespace demc

@@ -3,7 +3,7 @@ C-ABI engine.  The per-iteration work -- step!/pstep! (main.jl:84-107) -- happen
 import numpy as np
 
 from . import _ffi
-from .chains import COV_MAX_COLS, Bridge, Chains, Loo, RankStats, Summary, Waic, series_cov, series_quantiles
+from .chains import COV_MAX_COLS, Bridge, Chains, Hpd, Loo, RankStats, Summary, Waic, hpd_alphas, series_cov, series_quantiles
 from .families import PRIOR_NORMAL_REF, Priors, SimulatedLikelihood, SourceLikelihood
 from .structs import (DE, HIPBackend, LOGLIKE_MODES, MCMCThreads, SCHEDULES, DEModel, Particle, maximize)
 
@@ -202,6 +202,7 @@ def _run(model, de, n_iter, backend, progress, engine_factory, summary=None):
     want_loo = summary is not None and len(summary) > 6 and summary[6]
     want_bridge = summary is not None and len(summary) > 7 and summary[7]
     want_rank = summary is not None and len(summary) > 8 and summary[8]
+    want_hpd = summary is not None and len(summary) > 9 and summary[9]
     try:
         if want_bridge and not hasattr(eng, "bridge"):  # (no host form: the host route is what the call exists to avoid)
             raise _ffi.DemcError(_ffi.EUNSUPPORTED, "summarize(..., bridge=True) needs an engine with bridge(row0, row1, n_prop, seed) (demc_bridge)")
@@ -251,7 +252,9 @@ def _run(model, de, n_iter, backend, progress, engine_factory, summary=None):
             lay["bridge"] = Bridge(eng.bridge(summary[0], summary[1], int(opts.get("n_prop", 0)), int(opts.get("seed", 0))))
         if want_rank and hasattr(eng, "rankstats"):  # ess_bulk / ess_tail / rank-normalised rhat of the same kept rows (demc_rankstats)
             lay["rank"] = eng.rankstats(summary[0], summary[1], summary[2])
-        if (summary is not None and (not want_rank or "rank" in lay) and hasattr(eng, "summarize") and (len(summary) < 4 or summary[3] is None or hasattr(eng, "quantiles"))
+        if want_hpd and hasattr(eng, "hpd"):  # the highest-density intervals of the same kept rows (demc_hpd)
+            lay["hpd"] = eng.hpd(summary[0], summary[1], want_hpd)
+        if (summary is not None and (not want_rank or "rank" in lay) and (not want_hpd or "hpd" in lay) and hasattr(eng, "summarize") and (len(summary) < 4 or summary[3] is None or hasattr(eng, "quantiles"))
                 and (cov_cols is None or hasattr(eng, "covariance"))):
             # summarize(): the statistics (and the quantiles and the covariance, when asked for) on the device, no export at all
             stats = eng.summarize(summary[0], summary[1], summary[2])[0]
@@ -288,8 +291,8 @@ def _cov_cols(names, cor):
     return sel, [names.index(nm) for nm in sel]
 
 
-def summarize(model, de, *args, max_lag=0, quantiles=None, cor=False, waic=False, loo=False, bridge=False, rank=False, progress=False, engine_factory=None, **kwargs):
-    """summarize(model, de, [HIPBackend(...)], n_iter, max_lag=0, quantiles=None, cor=False, waic=False, loo=False, bridge=False, rank=False): the run of sample() followed by the summary
+def summarize(model, de, *args, max_lag=0, quantiles=None, cor=False, waic=False, loo=False, bridge=False, rank=False, hpd=None, progress=False, engine_factory=None, **kwargs):
+    """summarize(model, de, [HIPBackend(...)], n_iter, max_lag=0, quantiles=None, cor=False, waic=False, loo=False, bridge=False, rank=False, hpd=None): the run of sample() followed by the summary
     statistics of the rows bundle_samples keeps (offset = burnin or 0, quirk q1 included) -- computed on the device by
     demc_summarize, so that the history is never exported.  Returns a Summary (chains.py); equal to
     sample(...).summarystats(max_lag) for the same seed.  quantiles: a tuple of probs (chains.DEFAULT_QUANTILES) -- the same run
@@ -308,17 +311,24 @@ def summarize(model, de, *args, max_lag=0, quantiles=None, cor=False, waic=False
     from the same table -- a stated approximation, not a spectral estimate.  rank: True -- the same run also ranks the pooled kept rows
     of every series on the device (demc_rankstats) and Summary.rank holds the RankStats record: ess_bulk, ess_tail and
     the rank-normalised rhat, equal to sample(...).rankstats(max_lag); an engine without rankstats (an injected one) exports as sample()
-    does and ranks on the host.  With rank=False the call is what it was."""
+    does and ranks on the host.  With rank=False the call is what it was.  hpd: an alpha (0.05 for the 95 % interval) or a tuple of
+    them -- the same run also reads the highest-density intervals of the pooled kept rows of every series off the sorted pool on the
+    device (demc_hpd) and Summary.hpd holds the Hpd record, equal to sample(...).hpd(alphas) bit for bit; an engine
+    without hpd (an injected one) exports as sample() does and takes the intervals on the host.  With hpd=None the call is what it was."""
     backend, n_iter = _parse(args)
     Ns = n_iter - de.burnin if de.discard_burnin else n_iter
     offset = de.burnin if de.discard_burnin else 0
     probs = None if quantiles is None else tuple(float(q) for q in quantiles)
     want_cov = None if cor is False or cor is None else (True if cor is True else tuple(cor))
+    alphas = None if hpd is None else hpd_alphas(hpd)
     if isinstance(bridge, dict) and set(bridge) - {"n_prop", "seed"}:
         raise ValueError("bridge= takes True or dict(n_prop=, seed=)")
     lay, res, state = _run(model, de, n_iter, backend, progress, engine_factory,
-                           summary=(offset, offset + Ns, max_lag, probs, want_cov, waic, loo, True if bridge is True else (dict(bridge) if isinstance(bridge, dict) else bridge), bool(rank)))
-    out = _summary_of(model, de, lay, res, state, n_iter, max_lag, probs, want_cov, want_rank=bool(rank) and "rank" not in lay)
+                           summary=(offset, offset + Ns, max_lag, probs, want_cov, waic, loo, True if bridge is True else (dict(bridge) if isinstance(bridge, dict) else bridge), bool(rank), alphas))
+    out = _summary_of(model, de, lay, res, state, n_iter, max_lag, probs, want_cov, want_rank=bool(rank) and "rank" not in lay,
+                      want_hpd=None if "hpd" in lay else alphas)
+    if "hpd" in lay:
+        out.hpd = Hpd(out.names, lay["hpd"], alphas)
     if "rank" in lay:
         out.rank = RankStats(out.names, lay["rank"])
     out.waic = lay.get("waic")
@@ -331,7 +341,7 @@ def summarize(model, de, *args, max_lag=0, quantiles=None, cor=False, waic=False
     return out
 
 
-def _summary_of(model, de, lay, res, state, n_iter, max_lag, probs, want_cov, want_rank=False):
+def _summary_of(model, de, lay, res, state, n_iter, max_lag, probs, want_cov, want_rank=False, want_hpd=None):
     if state is None:
         names = get_names(model, lay["shapes"])
         if want_cov is not None:
@@ -344,6 +354,8 @@ def _summary_of(model, de, lay, res, state, n_iter, max_lag, probs, want_cov, wa
     out = chains.summarystats(max_lag)
     if want_rank:  # (an engine without rankstats: the definition on the host, from the exported rows)
         out.rank = chains.rankstats(max_lag)
+    if want_hpd is not None:  # (an engine without hpd: likewise)
+        out.hpd = chains.hpd(want_hpd)
     if probs is not None:
         out.probs = probs
         out.quantiles = np.stack([series_quantiles(chains.value[:, j, :], probs) for j in range(len(chains.names))])

@@ -288,6 +288,8 @@ include("DEMCHIPLoo.jl")
 include("DEMCHIPBridge.jl")
 # ... and the rank-normalised diagnostics ess_bulk / ess_tail / rhat (the header beside it): `rankstats`, `rank_series`, likewise
 include("DEMCHIPRank.jl")
+# ... and the highest-density intervals of hpd(chains) (the header beside it): `hpd`, likewise
+include("DEMCHIPHpd.jl")
 
 "final state of the particle objects behind handle `h` (bundle_samples reads accept/lp from them; Θ for completeness)"
 function pull_state!(h, particles, Pl, D, shapes, lens, offs)
